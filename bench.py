@@ -1,18 +1,21 @@
 #!/usr/bin/env python
 """bench.py -- generate_fast() throughput of the MI355X engine (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3x64] [--samples 16000]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload cfg3x64] [--samples 16000] [--dump-outputs DIR] [--full]
 
 A "step" is one ``WaveNetModel.generate_fast(--samples, first_samples=(streams, 1), temperature=1.0)`` call per GPU: every
-stream of the workload generates ``--samples`` audio samples.  Two legs are timed with the same K / W:
-  * facade (the headline ``value``): wall clock around the Python call -- uniform draw, H2D, queue reset, the persistent
-    kernels, D2H, mu-law expansion;
+stream of the workload generates ``--samples`` audio samples.  A plain run times the facade leg only -- the headline ``value``:
+wall clock around the Python call (uniform draw, H2D, queue reset, the persistent kernels, D2H, mu-law expansion) -- and
+prints its line; ``ms_per_step`` is the mean wall clock of one timed step.  ``--full`` adds everything else, as before:
   * engine_level: the same job through the C ABI with inputs and outputs resident in HBM (one wn_generate per step), with
-    HIP events around the launch for the roofline figure.
+    HIP events around the launch for the roofline figure (and the live rocprofv3 PMC passes behind it);
+  * ``verified``: the last timed buffer of both legs re-checked against the C oracle (300 samples of two streams);
+  * ``extra`` (other workloads, greedy, default init, priming, the config-5 training steps) and ``cpu_baseline``.
 ``value`` = audio samples/s summed over all streams and all GPUs.  N > 1: one process per GPU (torchrun), streams
 sharded across ranks with no data-path collective; the finished blocks are gathered to rank 0 over RCCL inside
-the timed region (that is the job's only exchange step); per-rank kernel and gather times are reported.
-``verified``: the last timed buffer of both legs re-checked against the C oracle (300 samples of two streams).
+the timed region (that is the job's only exchange step); --full reports per-rank kernel and gather times.
+``--dump-outputs DIR``: what the timed path returned in its last step, as DIR/<name>.npy (see dump_outputs); the inputs
+are seeded, so two builds run with the same arguments can be compared output for output.
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -206,7 +209,33 @@ def time_facade(cfgname, n_streams, samples, steps, warmup, dist, device):
     u = np.random.random_sample((n_streams, cut))
     if samples > cut:
         u = np.concatenate([u, np.random.random_sample((n_streams, samples - cut))], axis=1)
-    return {"wall": t1 - t0, "step_ms_median": float(np.median(step_ms)), "cfg": cfg, "W": W, "last_audio": audio, "first": first.numpy(), "uniforms": u}
+    return {"wall": t1 - t0, "step_ms_median": float(np.median(step_ms)), "cfg": cfg, "W": W, "last_audio": audio, "first": first.numpy(), "uniforms": u,
+            "gathered": gathered}
+
+
+DUMP_LIMIT_BYTES = 64 << 20   # --dump-outputs: at most this much in all
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: writes {name: array} as out_dir/<name>.npy, float32 / float64 as the timed path returned them (other dtypes as float64).
+    When they exceed `limit` bytes together, every array of one or more dimensions is cut to a fixed sample of its rows (elements of a 1-D array;
+    RandomState(0), sorted: the same rows in every run with the same arguments) so that the files stay inside the limit; raises ValueError, and
+    writes nothing, when even one row of each array would not fit.  Returns {name: shape written}."""
+    arrays = {k: (v if v.dtype in (np.float32, np.float64) else v.astype(np.float64)) for k, v in ((k, np.asarray(v)) for k, v in arrays.items())}
+    total = sum(v.nbytes for v in arrays.values())
+    if total > limit:
+        scalars = sum(v.nbytes for v in arrays.values() if v.ndim == 0)
+        frac = max(0.0, (limit - scalars) / float(total - scalars))
+        for k, v in list(arrays.items()):
+            if v.ndim >= 1 and v.shape[0] > 0:
+                keep = max(1, int(v.shape[0] * frac))
+                arrays[k] = v[np.sort(np.random.RandomState(0).choice(v.shape[0], keep, replace=False))]
+        if sum(v.nbytes for v in arrays.values()) > limit:
+            raise ValueError("--dump-outputs: %s do not fit in %d bytes even at one row each" % (sorted(arrays), limit))
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, k + ".npy"), np.ascontiguousarray(v))
+    return {k: list(v.shape) for k, v in arrays.items()}
 
 
 def verify_against_oracle(cfg, W, first, uniforms, idx=None, audio=None, streams=(0, -1), n=300, temperature=1.0):
@@ -423,10 +452,12 @@ def train5_main(a, dist, rank, local, n_gpus, global_batch=32, L=16000):
     clip0 = rank * n_local                      # this rank's shard of the fixture's batch
     idx = torch.from_numpy(ids[clip0:clip0 + n_local]).to(torch.int32).cuda(local)
     target = torch.from_numpy(tgt[clip0:clip0 + n_local].reshape(-1)).cuda(local)
-    # `verified`: one forward + backward on the fixture against the real reference's record before anything is timed (cfg5_verify); data parallel: every
-    # rank checks its clips' logit rows, and the gradients are checked AFTER the all-reduce -- the mean of the shards' gradients IS the batch's
-    ok, vdet, g = cfg5_verify(m, v6, idx, target, out_len, clip0, global_batch, precision)
-    if dist and n_gpus > 1:
+    # --full, `verified`: one forward + backward on the fixture against the real reference's record before anything is timed (cfg5_verify); data
+    # parallel: every rank checks its clips' logit rows, and the gradients are checked AFTER the all-reduce -- the mean of the shards' gradients IS the batch's
+    ok, vdet = None, None
+    if a.full:
+        ok, vdet, g = cfg5_verify(m, v6, idx, target, out_len, clip0, global_batch, precision)
+    if a.full and dist and n_gpus > 1:
         wavenet_training.average_gradients(m.parameters(), dist.group.WORLD)
         torch.cuda.synchronize()
         g = {k: (p.grad.detach().cpu().numpy() if p.grad is not None else np.zeros(tuple(p.shape), np.float32)) for k, p in m.named_parameters()}
@@ -448,6 +479,7 @@ def train5_main(a, dist, rank, local, n_gpus, global_batch=32, L=16000):
         if dist:
             wavenet_training.average_gradients(m.parameters(), group)
         opt.step()
+        return loss
 
     for _ in range(max(a.warmup, 1)):
         step()
@@ -456,13 +488,18 @@ def train5_main(a, dist, rank, local, n_gpus, global_batch=32, L=16000):
         dist.barrier()
     t0 = time.perf_counter()
     for _ in range(a.steps):
-        step()
+        loss = step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
     wall = time.perf_counter() - t0
     stats = m.wn_stats()
-    assert not stats["torch_fallbacks"] and stats["native_train_forward"] == a.steps + max(a.warmup, 1) + 1, "a timed training step left the native kernels: %r" % (stats,)
+    assert not stats["torch_fallbacks"] and stats["native_train_forward"] == a.steps + max(a.warmup, 1) + (1 if a.full else 0), \
+        "a timed training step left the native kernels: %r" % (stats,)
+    if a.dump_outputs and rank == 0:   # what the caller of the last step holds: its loss and the parameters the optimiser left
+        outs = {"loss": loss.detach().float().reshape(1).cpu().numpy()}
+        outs.update({"param." + k: p.detach().float().cpu().numpy() for k, p in m.named_parameters()})
+        dump_outputs(a.dump_outputs, outs)
     if dist:
         t = torch.tensor([wall], device="cuda", dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -481,8 +518,8 @@ def train5_main(a, dist, rank, local, n_gpus, global_batch=32, L=16000):
         print(json.dumps({
             "metric": "training step throughput, one-second 16 kHz clips per second (forward + backward + Adam), whole job",
             "value": round(global_batch / (ms * 1e-3), 2), "value_per_gpu": round(global_batch / (ms * 1e-3) / n_gpus, 2), "unit": "clips/s",
-            "n_gpus": n_gpus, "steps": a.steps, "warmup": max(a.warmup, 1), "verified": bool(ok), "verified_against": vdet,
-            "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
+            "n_gpus": n_gpus, "steps": a.steps, "warmup": max(a.warmup, 1), "verified": None if ok is None else bool(ok), "verified_against": vdet,
+            "ms_per_step": round(ms, 3), "higher_is_better": True, "scaling": "strong", "vs_baseline": None, "full": bool(a.full),
             "dtype": "bf16 matrix operands, f32 accumulation and residual stream" if bf16 else "f32",
             "data": "synthetic (seeded gain-1 random weights, uniform random class indices and targets: the fixture of tests/golden/golden_v6.npz)",
             "config": {"workload": "train5: WaveNetModel(layers=10, blocks=5, 128/128/512/256), global batch %d clips x %d samples, "
@@ -685,9 +722,14 @@ def main():
     ap.add_argument("--force-dist", action="store_true",
                     help="run through the distributed code path (RCCL process group, pick_device, gather, all-reduce of the timings) even "
                          "with ONE rank: the multi-GPU path exercised on a 1-GPU box")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--no-live-pmc", action="store_true", help="roofline.traffic from the committed PMC passes (replayed) instead of two rocprofv3 passes behind the timed region")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: the engine-level leg and its roofline (live rocprofv3 PMC passes), the oracle checks (`verified`), "
+                         "per-rank kernel / gather times, the extra workloads, priming and training legs, the CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write what the timed path returned in its last step as DIR/<name>.npy (float32 / float64, "
+                                                          "at most 64 MB in all)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the extra legs")
+    ap.add_argument("--no-live-pmc", action="store_true", help="--full: roofline.traffic from the committed PMC passes (replayed) instead of two rocprofv3 passes behind the timed region")
     a = ap.parse_args()
 
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -727,8 +769,13 @@ def main():
         from mi355_wavenet import streams
         lo, hi = streams.shard_bounds(512, rank, n_gpus)
         per_gpu = hi - lo
+    if not a.full:
+        plain_main(a, dist, rank, n_gpus, cfgname, per_gpu, local)
+        return
     eng_leg = time_engine(cfgname, per_gpu, a.samples, a.steps, a.warmup, dist, local)
     fac_leg = time_facade(cfgname, per_gpu, a.samples, a.steps, a.warmup, dist, local)
+    if a.dump_outputs and rank == 0:
+        _dump_audio(a.dump_outputs, fac_leg)
     verified = verify_against_oracle(eng_leg["cfg"], eng_leg["W"], eng_leg["first"], eng_leg["uniforms"], idx=eng_leg["last_idx"]) and \
         verify_against_oracle(fac_leg["cfg"], fac_leg["W"], fac_leg["first"], fac_leg["uniforms"], audio=fac_leg["last_audio"])
     walls = [eng_leg["wall"], fac_leg["wall"], 0.0 if verified else 1.0]
@@ -761,31 +808,16 @@ def main():
         traffic_kind = None if traffic is None else ("replayed: PMC passes of an EARLIER run of this kernel in this form, scaled to this launch's timesteps -- not a "
                                                      "measurement of this run (live passes: %s)" % (live_reason or "not attempted"))
     kname = {1: "wn_generate_kernel", 3: "wn_generate_kernel_v3m", 4: "wn_generate_kernel_v4"}.get(info["kernel_variant"], "?")
-    line = {
-        "metric": BASELINE_METRIC,
-        "value": round(value, 1), "value_per_gpu": round(red["value_per_gpu"], 1),
-        "value_is": "the WHOLE JOB: samples of all streams on all %d GPU(s) per second of the slowest rank's wall clock (the bench contract); value_per_gpu = value / n_gpus "
-                    "is the metric's per-GPU figure; per_rank[].samples_per_s is each rank against its own clock" % n_gpus,
-        "unit": "samples/s", "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
-        "ms_per_step": round(wall / a.steps * 1e3, 3), "median_ms_per_step": round(fac_leg["step_ms_median"], 3),
-        "higher_is_better": True, "scaling": a.scaling,
-        "vs_baseline": None, "dtype": "f32", "data": "synthetic (seeded random weights, uniforms from the global numpy RNG)",
-        "verified": bool(verified and any_bad == 0.0),
-        "config": {"workload": "%s: WaveNetModel(%s).generate_fast(%d, first_samples=(%d, 1), temperature=1.0) per GPU per step"
-                               % (a.workload, ", ".join("%s=%s" % kv for kv in cfg.items()), a.samples, per_gpu),
-                   "streams_per_gpu": per_gpu, "samples_per_stream_per_step": a.samples,
-                   "per_stream_samples_per_s": round(value / total_streams, 1),
-                   "timed": "wall clock around the facade call: RNG draw, H2D, queue reset, kernels, D2H, mu-law expansion; the cyclic collector stays "
-                            "enabled (objects that exist before the timed steps are gc.freeze()-d, here and in the CPU baseline); ms_per_step is the mean, median_ms_per_step the median"
-                            + ("; + RCCL gather of the audio to rank 0" if dist else ""),
-                   "chain": {k: info[k] for k in ("kernel_variant", "n_chains", "layer_split", "head_split", "n_workgroups", "lds_bytes",
-                                                  "streams_per_item", "head_replicas", "n_samplers", "dev_overrides")}},
+    line = headline(a, n_gpus, dist, per_gpu, total_streams, value, red["value_per_gpu"], wall, fac_leg, cfg, bool(verified and any_bad == 0.0))
+    line["value_is"] += "; per_rank[].samples_per_s is each rank against its own clock"
+    line["config"]["chain"] = {k: info[k] for k in ("kernel_variant", "n_chains", "layer_split", "head_split", "n_workgroups", "lds_bytes",
+                                                    "streams_per_item", "head_replicas", "n_samplers", "dev_overrides")}
+    line.update({
         "engine_level": {"value": round(engine_value, 1), "ms_per_step": round(eng_wall / a.steps * 1e3, 3),
                          "note": "the same job through the C ABI with inputs and outputs resident in HBM (one wn_generate per step"
                                  + ("; + RCCL gather of the index blocks" if dist else "") + ")",
                          "facade_over_engine": round(fac_wall / eng_wall, 4)},
         "per_rank": per_rank,
-        "rccl_ranks": dist.get_world_size() if dist else 0, "dist_backend": dist.get_backend() if dist else None,
         "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic,
                      "traffic_kind": traffic_kind,
@@ -796,7 +828,7 @@ def main():
                      "algorithmic_bytes_per_timestep": int(bytes_per_tstep), "launches_per_step": 1,
                      "note": "engine-level leg: one launch = one wn_generate job of %d timesteps = ONE persistent kernel (n_chains > 1: the "
                              "rounds of a job beyond one chain's capacity, one after the other), timed with HIP events on the launch stream" % a.samples},
-    }
+    })
     if n_gpus == 1 and not a.no_extra:
         extra = {}
         def extra_leg(c2, s2, n2, temperature=1.0, weights=None, check=True):
@@ -834,6 +866,55 @@ def main():
     if n_gpus == 1 and not a.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cfgname)
     print(json.dumps(line))
+    if dist:
+        dist.destroy_process_group()
+
+
+def _dump_audio(out_dir, fac_leg):
+    """The facade's last step as its caller receives it: float64 audio, (streams, samples); N ranks: every rank's block as gathered to rank 0."""
+    if fac_leg["gathered"] is not None:
+        audio = torch.cat(fac_leg["gathered"]).cpu().numpy()
+    else:
+        audio = fac_leg["last_audio"]
+    dump_outputs(out_dir, {"audio": audio})
+
+
+def headline(a, n_gpus, dist, per_gpu, total_streams, value, value_per_gpu, fac_wall, fac_leg, cfg, verified):
+    """The keys of the result line that a plain run and --full share: the headline figure and what it measured (--full adds its own)."""
+    return {
+        "metric": BASELINE_METRIC,
+        "value": round(value, 1), "value_per_gpu": round(value_per_gpu, 1),
+        "value_is": "the WHOLE JOB: samples of all streams on all %d GPU(s) per second of the slowest rank's wall clock (the bench contract); value_per_gpu = value / n_gpus "
+                    "is the metric's per-GPU figure" % n_gpus,
+        "unit": "samples/s", "n_gpus": n_gpus, "steps": a.steps, "warmup": a.warmup,
+        "ms_per_step": round(fac_wall / a.steps * 1e3, 3), "median_ms_per_step": round(fac_leg["step_ms_median"], 3),
+        "higher_is_better": True, "scaling": a.scaling,
+        "vs_baseline": None, "dtype": "f32", "data": "synthetic (seeded random weights, uniforms from the global numpy RNG)",
+        "verified": verified, "full": bool(a.full),
+        "config": {"workload": "%s: WaveNetModel(%s).generate_fast(%d, first_samples=(%d, 1), temperature=1.0) per GPU per step"
+                               % (a.workload, ", ".join("%s=%s" % kv for kv in cfg.items()), a.samples, per_gpu),
+                   "streams_per_gpu": per_gpu, "samples_per_stream_per_step": a.samples,
+                   "per_stream_samples_per_s": round(value / total_streams, 1),
+                   "timed": "wall clock around the facade call: RNG draw, H2D, queue reset, kernels, D2H, mu-law expansion; the cyclic collector stays "
+                            "enabled (objects that exist before the timed steps are gc.freeze()-d, here and in the CPU baseline); ms_per_step is the mean, median_ms_per_step the median"
+                            + ("; + RCCL gather of the audio to rank 0" if dist else "")},
+        "rccl_ranks": dist.get_world_size() if dist else 0, "dist_backend": dist.get_backend() if dist else None}
+
+
+def plain_main(a, dist, rank, n_gpus, cfgname, per_gpu, local):
+    """A plain run: the facade leg -- the headline figure -- and nothing else (--full adds the rest)."""
+    fac_leg = time_facade(cfgname, per_gpu, a.samples, a.steps, a.warmup, dist, local)
+    if a.dump_outputs and rank == 0:
+        _dump_audio(a.dump_outputs, fac_leg)
+    fac_wall = fac_leg["wall"]
+    if dist:   # the slowest rank's clock (barriers on both sides of the timed steps)
+        t = torch.tensor([fac_wall], device="cuda", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        fac_wall = float(t.item())
+    if rank == 0:
+        total_streams = int(sum(streams_by_rank(a.scaling, WORKLOADS[a.workload][1], n_gpus)))
+        value = total_streams * a.samples * a.steps / fac_wall   # = reduce_ranks(...)["value"]
+        print(json.dumps(headline(a, n_gpus, dist, per_gpu, total_streams, value, value / n_gpus, fac_wall, fac_leg, fac_leg["cfg"], None)))
     if dist:
         dist.destroy_process_group()
 

@@ -147,7 +147,7 @@ def test_bench_one_gpu_through_the_distributed_path(launcher):
     """bench.py --gpus 1 --force-dist: the N-GPU code path (RCCL group, pick_device, gather of index blocks and audio inside the timed
     region, all-reduce of the timings) with one rank; the line says which backend carried it."""
     env = {k: v for k, v in _env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--samples", "400", "--no-extra", "--no-cpu-baseline"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--samples", "400", "--full", "--no-extra", "--no-cpu-baseline"]
     if launcher == "plain":
         cmd = [sys.executable] + tail
     else:
@@ -160,6 +160,43 @@ def test_bench_one_gpu_through_the_distributed_path(launcher):
     assert line["verified"] is True and line["value"] > 0
     assert len(line["per_rank"]) == 1 and line["per_rank"][0]["gather_ms"] >= 0
     assert "RCCL gather" in line["config"]["timed"]
+
+
+def test_bench_plain_run_through_the_distributed_path(tmp_path):
+    """bench.py --gpus 1 --force-dist WITHOUT --full: the plain N-GPU line (wall clock all-reduced over the RCCL group, the line built on rank 0)
+    and --dump-outputs writing the audio as gathered to rank 0."""
+    env = {k: v for k, v in _env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "2", "--warmup", "1", "--samples", "400",
+           "--dump-outputs", str(tmp_path / "out")]
+    res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=600)
+    assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+    line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["n_gpus"] == 1 and line["rccl_ranks"] == 1 and line["dist_backend"] == "nccl" and line["full"] is False
+    assert line["steps"] == 2 and line["value"] > 0 and abs(line["value"] - 64 * 400 / (line["ms_per_step"] * 1e-3)) <= 1e-3 * line["value"]
+    assert "RCCL gather" in line["config"]["timed"] and line["verified"] is None and "per_rank" not in line and "engine_level" not in line
+    import c_oracle
+    audio = np.load(str(tmp_path / "out" / "audio.npy"))
+    assert audio.dtype == np.float64 and audio.shape == (64, 400)
+    assert np.isin(audio, c_oracle.expand(np.arange(256))).all()   # every sample is one of the 256 mu-law levels generate_fast returns
+
+
+def test_bench_plain_run_dumps_what_the_full_run_verifies(tmp_path):
+    """bench.py without --full: the facade leg alone (`steps` timed steps, ms_per_step, no engine leg, no oracle check) and --dump-outputs
+    writes the last step's audio; the same arguments with --full return the same audio, and --full checks it against the oracle."""
+    env = {k: v for k, v in _env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
+    common = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--samples", "400"]
+    lines = {}
+    for mode, extra in (("plain", []), ("full", ["--full", "--no-extra", "--no-cpu-baseline", "--no-live-pmc"])):
+        res = subprocess.run(common + extra + ["--dump-outputs", str(tmp_path / mode)], env=env, capture_output=True, text=True, timeout=600)
+        assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
+        lines[mode] = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
+    plain, full = lines["plain"], lines["full"]
+    assert plain["steps"] == 3 and plain["unit"] == "samples/s" and plain["higher_is_better"] is True and plain["dtype"] == "f32"
+    assert abs(plain["value"] - 64 * 400 / (plain["ms_per_step"] * 1e-3)) <= 1e-3 * plain["value"]
+    assert plain["verified"] is None and not any(k in plain for k in ("engine_level", "roofline", "extra", "cpu_baseline"))
+    assert full["verified"] is True and full["engine_level"]["value"] > 0
+    a, b = np.load(str(tmp_path / "plain" / "audio.npy")), np.load(str(tmp_path / "full" / "audio.npy"))
+    assert a.dtype == np.float64 and a.shape == (64, 400) and np.array_equal(a, b)
 
 
 @two_gpus
@@ -190,7 +227,7 @@ def test_two_ranks_on_one_device_are_refused(tmp_path):
 def test_bench_two_gpus_as_the_driver_launches_it():
     port = 29900 + os.getpid() % 1000
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--samples", "400"]
+           "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--samples", "400", "--full"]
     res = subprocess.run(cmd, env=_env(), capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])
@@ -203,7 +240,7 @@ def test_bench_two_gpus_as_the_driver_launches_it():
 def test_bench_launches_its_own_ranks():
     """`python bench.py --gpus 2` with no launcher around it (how the driver may call it): bench.py re-executes itself as two ranks."""
     env = {k: v for k, v in _env().items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--samples", "400"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--samples", "400", "--full"]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
     assert res.returncode == 0, res.stdout[-2000:] + res.stderr[-4000:]
     line = json.loads([l for l in res.stdout.splitlines() if l.startswith("{")][-1])

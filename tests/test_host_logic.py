@@ -7,6 +7,7 @@ import os
 import sys
 
 import numpy as np
+import pytest
 
 import c_oracle
 import restated
@@ -171,3 +172,31 @@ def test_bench_reads_the_pmc_counters_of_the_one_generation_kernel(tmp_path):
     con.execute("insert into counters_collection values (?, ?, ?)", ("void wn_generate_kernel_v4<64, 64, 256, 64, 3>(WnPlan, WnRun)", "WRITE_SIZE", 5.0))
     con.commit()
     assert bench.pmc_counter_from_db(db, "WRITE_SIZE") is None
+
+
+def test_bench_dump_outputs_keeps_dtypes_and_the_size_limit(tmp_path):
+    """bench.py --dump-outputs: float32 / float64 arrays as returned, anything else as float64; beyond the limit every array of two or more
+    dimensions is cut to the same seeded sample of its rows in every run (two runs of two builds stay comparable file for file)."""
+    import bench
+    audio = np.random.RandomState(1).random_sample((64, 1000))            # 512 000 bytes
+    small = {"audio": audio, "loss": np.array([1.5], np.float32), "idx": np.arange(6, dtype=np.int32).reshape(2, 3)}
+    assert bench.dump_outputs(str(tmp_path / "a"), small) == {"audio": [64, 1000], "loss": [1], "idx": [2, 3]}
+    got = {k: np.load(str(tmp_path / "a" / (k + ".npy"))) for k in small}
+    assert got["audio"].dtype == np.float64 and np.array_equal(got["audio"], audio)
+    assert got["loss"].dtype == np.float32 and got["idx"].dtype == np.float64 and np.array_equal(got["idx"], small["idx"])
+    shapes = bench.dump_outputs(str(tmp_path / "b"), {"audio": audio, "loss": small["loss"]}, limit=200000)
+    assert shapes["audio"][1] == 1000 and 1 <= shapes["audio"][0] < 64 and shapes["loss"] == [1]
+    cut = np.load(str(tmp_path / "b" / "audio.npy"))
+    assert cut.nbytes + 4 <= 200000
+    rows = [int(np.flatnonzero((audio == r).all(1))[0]) for r in cut]
+    assert rows == sorted(rows) and len(set(rows)) == len(rows)
+    bench.dump_outputs(str(tmp_path / "c"), {"audio": audio, "loss": small["loss"]}, limit=200000)
+    assert np.array_equal(np.load(str(tmp_path / "c" / "audio.npy")), cut)
+    # 1-D arrays are cut as well (elements), so the limit holds whatever the shapes; what cannot fit at one row each is refused
+    flat = np.random.RandomState(2).random_sample(100000)                  # 800 000 bytes
+    shapes = bench.dump_outputs(str(tmp_path / "d"), {"flat": flat, "loss": small["loss"]}, limit=100000)
+    got = np.load(str(tmp_path / "d" / "flat.npy"))
+    assert got.nbytes + 4 <= 100000 and shapes["flat"] == [got.size] and np.all(np.isin(got, flat))
+    with pytest.raises(ValueError):
+        bench.dump_outputs(str(tmp_path / "e"), {"wide": np.zeros((2, 1000))}, limit=1000)
+    assert not os.path.exists(str(tmp_path / "e"))

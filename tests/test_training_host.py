@@ -43,24 +43,24 @@ def test_dataset_items_equal_the_references(dataset_file):
                 assert np.array_equal(target.numpy().reshape(-1), g[tag + "_t"][row]), (tag, i)
 
 
-@pytest.mark.reference
 def test_dataset_equals_reference_class_everywhere(dataset_file):
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference tree not present")
-    _, _, ad = ref_shim.load()
-    for il, tl, stride in SETTINGS:
+    """EVERY item of every setting, train and test, against what the reference's WavenetDataset returned, and its mu-law helpers (tests/golden/golden_v7.npz,
+    make_golden_live.py: one-hot inputs stored as their classes)."""
+    g = np.load(os.path.join(HERE, "golden", "golden_v7.npz"))
+    for k, (il, tl, stride) in enumerate(SETTINGS):
         for train in (True, False):
-            ref = ad.WavenetDataset(dataset_file, item_length=il, target_length=tl, train=train, test_stride=stride)
+            tag = "ds_s%d_%s" % (k, "train" if train else "test")
             ds = audio_data.WavenetDataset(dataset_file, item_length=il, target_length=tl, train=train, test_stride=stride)
-            assert len(ds) == len(ref) and ds.start_samples == ref.start_samples
-            for i in range(len(ref)):
-                a, b = ref[i], ds[i]
-                assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+            assert len(ds) == int(g[tag + "_len"]) and list(ds.start_samples) == g[tag + "_start"].tolist(), tag
+            for i in range(len(ds)):
+                a = torch.nn.functional.one_hot(torch.from_numpy(g[tag + "_x"][i].astype(np.int64)), 256).t().float()
+                b = ds[i]
+                assert torch.equal(a, b[0]) and torch.equal(torch.from_numpy(g[tag + "_t"][i].astype(np.int64)).view(1, tl), b[1]), (tag, i)
+    # the mu-law helpers, bit for bit against the reference's quantize_data / mu_law_expansion on the same seeded uniforms
     x = np.random.RandomState(0).uniform(-1, 1, 1000)
-    assert np.array_equal(ad.quantize_data(x, 256), audio_data.quantize_data(x, 256))
-    assert np.array_equal(ad.mu_law_expansion(x, 256), audio_data.mu_law_expansion(x, 256))
+    assert np.array_equal(x, g["mulaw_x"])
+    assert np.array_equal(g["mulaw_quantized"], audio_data.quantize_data(x, 256))
+    assert np.array_equal(g["mulaw_expanded"], audio_data.mu_law_expansion(x, 256))
 
 
 def test_device_batches_equal_dataset_items(dataset_file):
@@ -137,23 +137,19 @@ def test_logger_cadence():
         model_logging.TensorboardLogger()
 
 
-@pytest.mark.reference
 def test_trainer_steps_equal_the_reference_loop(dataset_file):
     """Three optimiser steps of WavenetTrainer.train against the reference's loop body (wavenet_training.py:64-77, its two
-    legacy `.data[0]` reads dropped) run on the reference's own WaveNetModel with the same initial weights and the same
-    shuffled DataLoader order."""
-    sys.path.insert(0, os.path.join(ROOT, "oracle"))
-    import ref_shim
-    if not ref_shim.available():
-        pytest.skip("reference tree not present")
-    mdl, _, ad = ref_shim.load()
+    legacy `.data[0]` reads dropped; tests/golden/make_golden_live.py reference_loop) with the same initial weights and the same
+    shuffled DataLoader order: bit for bit against that loop run here on the facade's CPU model, and against what the loop
+    returned on the reference's own WaveNetModel (golden_v7.npz; fp32 reduction-order noise of another host's CPU kernels allowed)."""
+    import make_golden_live as mgl
+    g = np.load(os.path.join(HERE, "golden", "golden_v7.npz"))
     m = _tiny_model()
-    ref = mdl.WaveNetModel(layers=3, blocks=2, dilation_channels=8, residual_channels=8, skip_channels=16, end_channels=16,
-                           classes=256, output_length=8, kernel_size=2, bias=True)
-    ref.load_state_dict(m.state_dict())
+    ref = _tiny_model()
+    assert m.output_length == mgl.LOOP["out_len"]
     il = m.receptive_field + m.output_length - 1
-    ds = audio_data.WavenetDataset(dataset_file, item_length=il, target_length=8, test_stride=5)
-    rds = ad.WavenetDataset(dataset_file, item_length=il, target_length=8, test_stride=5)
+    ds = audio_data.WavenetDataset(dataset_file, item_length=il, target_length=8, test_stride=mgl.LOOP["test_stride"])
+    rds = audio_data.WavenetDataset(dataset_file, item_length=il, target_length=8, test_stride=mgl.LOOP["test_stride"])
 
     class Stop(Exception):
         pass
@@ -170,26 +166,15 @@ def test_trainer_steps_equal_the_reference_loop(dataset_file):
     with pytest.raises(Stop):
         tr.train(batch_size=4, epochs=1)
     # the reference's loop
-    opt = torch.optim.Adam(params=ref.parameters(), lr=0.01, weight_decay=0)
-    ref.train()
-    torch.manual_seed(11)
-    loader = torch.utils.data.DataLoader(rds, batch_size=4, shuffle=True, num_workers=0, pin_memory=False)
-    ref_losses = []
-    for step, (x, target) in enumerate(iter(loader), 1):
-        x = x.type(torch.FloatTensor)
-        target = target.view(-1).type(torch.LongTensor)
-        output = ref(x)
-        loss = torch.nn.functional.cross_entropy(output.squeeze(), target.squeeze())
-        opt.zero_grad()
-        loss.backward()
-        torch.nn.utils.clip_grad_norm_(ref.parameters(), 1.0)
-        opt.step()
-        ref_losses.append(loss.item())
-        if step == 3:
-            break
+    ref_losses = mgl.reference_loop(ref, rds, mgl.LOOP["lr"], mgl.LOOP["clip"], mgl.LOOP["batch"], mgl.LOOP["steps"], mgl.LOOP["seed"])
     assert losses == ref_losses
     for (k, a), (_, b) in zip(m.state_dict().items(), ref.state_dict().items()):
         assert torch.equal(a, b), k
+    # ... and that loop is the reference's: the same losses and parameters it left on the reference's own model
+    assert np.abs(np.asarray(losses) - g["loop_losses"]).max() <= 1e-5 * np.abs(g["loop_losses"]).max()
+    for k, a in m.state_dict().items():
+        want = g["loop_" + k]
+        assert a.shape == want.shape and float(np.abs(a.numpy() - want).max()) <= 1e-5 * max(1.0, float(np.abs(want).max())), k
     avg_loss, acc = tr.validate()
     assert np.isfinite(avg_loss) and 0.0 <= acc <= 1.0 and ds.train is True
 

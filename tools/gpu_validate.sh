@@ -1,15 +1,19 @@
 #!/bin/bash
-# Runs on the GPU box: the GPU test suite, smoke(), the default bench line.   tools/gpu_validate.sh [tag]
+# Runs on the GPU box: the GPU test suite, smoke(), the full bench line (bench.py --full).   tools/gpu_validate.sh [tag]
+# Records go to $WN_RESULTS (default: results/ in the repository root).
 TAG=${1:-latest}
-mkdir -p gpurun_out
-cd /root/repo
-( time timeout 2400 python -m pytest tests -m gpu -q -x 2>&1 | tail -6 ) 2>&1 | tee gpurun_out/pytest_gpu_$TAG.txt
-python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu | tail -2
-( time timeout 900 python bench.py 2> gpurun_out/bench_$TAG.err | tail -1 > gpurun_out/bench_$TAG.json ) 2>&1 | tail -3
-tail -5 gpurun_out/bench_$TAG.err
+cd "$(dirname "$0")/.."
+OUT=${WN_RESULTS:-results}
+mkdir -p "$OUT"
+# every GPU step runs under a time limit of its own; the first step that fails, faults or times out ends the script
+set -o pipefail
+( time timeout -k 10 2400 python -m pytest tests -m gpu -q -x 2>&1 | tail -6 ) 2>&1 | tee "$OUT/pytest_gpu_$TAG.txt" || exit 1
+timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" 2>&1 | grep -v amdgpu | tail -2 || exit 1
+( time timeout -k 10 900 python bench.py --full 2> "$OUT/bench_$TAG.err" | tail -1 > "$OUT/bench_$TAG.json" ) 2>&1 | tail -3 || { tail -5 "$OUT/bench_$TAG.err"; exit 1; }
+tail -5 "$OUT/bench_$TAG.err"
 python - <<PY
 import json
-d = json.load(open("gpurun_out/bench_$TAG.json"))
+d = json.load(open("$OUT/bench_$TAG.json"))
 e = d.get("extra", {})
 print("value", d["value"], "median ms", d.get("median_ms_per_step"), "engine", d["engine_level"]["value"], "roofline", d["roofline"]["frac"], "traffic", d["roofline"]["traffic"], d["roofline"].get("traffic_kind", "")[:40], d["roofline"].get("traffic_over_algorithmic"), "verified", d["verified"])
 for k, v in e.items():
