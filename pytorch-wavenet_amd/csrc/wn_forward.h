@@ -126,6 +126,7 @@ static __device__ __forceinline__ uint4 wn_pack_bf16x8(float4 a, float4 b) {
                         // of fp32 written and 8.9 GB read per config-5 step become 4.45 + 4.45.  One more rounding point of the bf16 step (oracle/bf16_step.py
                         // carries it); 0 keeps fp32 (A/B builds: host and kernels read the same switch).
 #endif
+static __device__ __forceinline__ float wn_gate_clamp(float x) { return x > 100.f ? 100.f : (x < -100.f ? -100.f : x); }
 template <int EPI, int NTILES = 4, bool CB16 = false>
 static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, const wn_f16v (&acc)[NTILES], long long mw, int nw, int lane, float* stage,
                                                         unsigned short* zl = nullptr, int zld = 0) {
@@ -150,7 +151,9 @@ static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, con
             const float bf = g.bias ? g.bias[nf] : 0.f, bg = g.bias ? g.bias[ng] : 0.f;
 #pragma unroll
             for (int i = 0; i < 16; ++i) {
-                const float f = acc[2 * p][i] + bf, gg = acc[2 * p + 1][i] + bg;
+                // (pre-activations clamped to +-100, where exp has long saturated to 0 / inf either way: the same bits for every finite input, and tanh / sigmoid of
+                //  +-inf are +-1 / 1, 0 instead of the NaN that wn_exp(+-inf) returns; a NaN stays NaN)
+                const float f = wn_gate_clamp(acc[2 * p][i] + bf), gg = wn_gate_clamp(acc[2 * p + 1][i] + bg);
                 // tanh(f) = 2 sigmoid(2f) - 1 on the branch-free exp of the generation kernels (absolute error ~1e-7), 1-ulp reciprocals
                 th[i] = fmaf(2.0f, __builtin_amdgcn_rcpf(1.0f + wn_exp(-2.0f * f)), -1.0f);
                 sg[i] = __builtin_amdgcn_rcpf(1.0f + wn_exp(-gg));
@@ -1073,8 +1076,9 @@ __global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_bwd_gemm_tn(WnGemmTnArgs
     }
 }
 
-// Deterministic mode: C[ka][nb] (or its transpose) = the row splits' partial tiles added in the order of the splits -- one thread per four columns.
-// Also the second half of the bias gradients' column sums (Ka = 1, one "split" per 512-row block).
+// Deterministic mode: C[ka][nb] (or its transpose) += the row splits' partial tiles added in the order of the splits -- one thread per four columns.
+// Also the second half of the bias gradients' column sums (Ka = 1, one "split" per 512-row block).  It ADDS to C, as the atomics of the other mode do:
+// both modes accumulate into whatever C holds on entry.
 __global__ __launch_bounds__(256) void wn_tn_reduce(const float* part, int n_splits, int Ka, int Nb, float* c, int ldc, int c_trans) {
     const long long e4 = (long long)blockIdx.x * 256 + threadIdx.x, per = (long long)Ka * Nb;
     if (e4 * 4 >= per) return;
@@ -1084,8 +1088,12 @@ __global__ __launch_bounds__(256) void wn_tn_reduce(const float* part, int n_spl
         s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
     }
     const int ka = (int)(e4 * 4 / Nb), nb = (int)(e4 * 4 % Nb);   // (Nb is a multiple of 4: the four columns share a row)
-    if (c_trans) { c[(size_t)nb * ldc + ka] = s.x; c[(size_t)(nb + 1) * ldc + ka] = s.y; c[(size_t)(nb + 2) * ldc + ka] = s.z; c[(size_t)(nb + 3) * ldc + ka] = s.w; }
-    else *reinterpret_cast<float4*>(c + (size_t)ka * ldc + nb) = s;
+    if (c_trans) { c[(size_t)nb * ldc + ka] += s.x; c[(size_t)(nb + 1) * ldc + ka] += s.y; c[(size_t)(nb + 2) * ldc + ka] += s.z; c[(size_t)(nb + 3) * ldc + ka] += s.w; }
+    else {
+        float4* cp = reinterpret_cast<float4*>(c + (size_t)ka * ldc + nb);
+        const float4 o = *cp;
+        *cp = make_float4(o.x + s.x, o.y + s.y, o.z + s.z, o.w + s.w);
+    }
 }
 
 // The same weight-gradient product with bf16 MATRIX OPERANDS (fp32 accumulation, fp32 atomics into the gradient): the rows of

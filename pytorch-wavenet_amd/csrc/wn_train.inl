@@ -234,6 +234,40 @@ static float* wn_det_part(hipStream_t st, size_t floats) {
     return w->buf;
 }
 
+// The weight-gradient kernels read each operand of a row split through a buffer descriptor based at the split's first row, with 32-bit byte offsets
+// and a 2 GB window (wn_rsrc): rows beyond it would read as zeros.  True when every split of `rps` rows keeps each operand it reads inside the
+// window -- batch-stride jumps included (strides >= 0, batch entries in order).
+static bool wn_tn_map_fits(const WnRowMap& map, long long m0, long long m1, int rpb, long long cols, int esize) {
+    const long long q0 = m0 / rpb, q1 = (m1 - 1) / rpb;
+    auto e = [&](long long q, long long rem) { return q * map.batch_stride + (map.t0 + rem) * map.row_stride; };
+    const long long base = e(q0, m0 - q0 * rpb);
+    for (long long q = q0; q <= q1; ++q) {   // the last row of each batch entry in range is its farthest
+        const long long hi = q == q1 ? m1 - 1 - q1 * rpb : rpb - 1;
+        if ((e(q, hi) - base + cols) * esize > 0x7fffffffll) return false;
+    }
+    return true;
+}
+static bool wn_tn_splits_fit(const WnGemmTnArgs& a, long long rps) {
+    const long long a_cols = a.ka_split > 0 ? a.ka_split : a.Ka;
+    for (long long m0 = 0; m0 < a.M; m0 += rps) {
+        const long long m1 = m0 + rps < a.M ? m0 + rps : a.M;
+        if (!a.a_idx && !wn_tn_map_fits(a.a, m0, m1, a.rows_per_batch, a_cols, a.a_bf16 ? 2 : 4)) return false;
+        if (a.ka_split > 0 && !wn_tn_map_fits(a.a1, m0, m1, a.rows_per_batch, a.Ka - a.ka_split, a.a_bf16 ? 2 : 4)) return false;
+        if (!wn_tn_map_fits(a.b, m0, m1, a.rows_per_batch, a.Nb, a.b_bf16 ? 2 : 4)) return false;
+    }
+    return true;
+}
+// More splits (rows per split a multiple of 32, as the planners make them) until every split fits its window; returns the rows per split.
+static long long wn_tn_fit_window(const WnGemmTnArgs& a, long long rps) {
+    long long splits = (a.M + rps - 1) / rps;
+    while (rps > 32 && !wn_tn_splits_fit(a, rps)) {
+        ++splits;
+        const long long r = ((a.M + splits - 1) / splits + 31) / 32 * 32;
+        if (r < rps) rps = r;
+    }
+    return rps;
+}
+
 static void wn_launch_tn(hipStream_t st, WnGemmTnArgs a, bool bf16 = false) {
     // bf16 products with Nb % 256 == 0 take the 128 x 256 tile (A streamed once per 256 columns of B); rows split by wn_tn_grid (wn_plan.h)
     const bool wide16 = bf16 && !a.a_idx && a.a_bf16 && a.b_bf16 && a.Nb % 256 == 0;   // (both operands stored as bf16: the filter/gate weight gradient on the shadow of x -- two tap views, ka_split > 0 --, the skip weight gradient on the shadow of dskip)
@@ -253,7 +287,7 @@ static void wn_launch_tn(hipStream_t st, WnGemmTnArgs a, bool bf16 = false) {
             long long splits = want_t / tiles > 1 ? want_t / tiles : 1;
             if (splits >= 8) splits -= splits % 8;
             long long rps = (a.M + splits - 1) / splits;
-            rps = (rps + 31) / 32 * 32;
+            rps = wn_tn_fit_window(a, (rps + 31) / 32 * 32);
             splits = (a.M + rps - 1) / rps;
             a.rows_per_split = rps; a.tiles_ka = a.Ka / 256; a.n_splits = (int)splits;
             a.part = wn_det_part(st, (size_t)splits * a.Ka * a.Nb);
@@ -269,7 +303,9 @@ static void wn_launch_tn(hipStream_t st, WnGemmTnArgs a, bool bf16 = false) {
     // 54.9 at 512; profiles/r05_training_step_byte_cuts.txt).  The fp32 kernel is matrix-pipe bound and wants the rows spread wider: 1024 (512: 179 -> 194 ms).
     int want = (wide || (bf16 && !a.a_idx)) ? 512 : 1024;
     { const char* wv = wn_dev_env(wide ? "WN_TN_WANT_WIDE" : "WN_TN_WANT"); if (wv && atoi(wv) > 0) want = atoi(wv); }   // (A/B runs, with WN_TESTING=1)
-    const WnTnGrid tg = wn_tn_grid(a.M, a.Ka, a.Nb, wide ? 256 : 128, want);
+    WnTnGrid tg = wn_tn_grid(a.M, a.Ka, a.Nb, wide ? 256 : 128, want);
+    { const long long rps = wn_tn_fit_window(a, tg.rows_per_split);
+      if (rps != tg.rows_per_split) { tg.rows_per_split = rps; tg.splits = (int)((a.M + rps - 1) / rps); tg.blocks = 8u * (unsigned)(tg.tiles_ka * tg.tiles_nb) * (unsigned)((tg.splits + 7) / 8); } }
     a.rows_per_split = tg.rows_per_split;
     a.tiles_ka = tg.tiles_ka; a.n_splits = tg.splits;
     const dim3 grid(tg.blocks);   // wn_tile_of: the tiles of a row split share an XCD
