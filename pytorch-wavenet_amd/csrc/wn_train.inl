@@ -392,7 +392,11 @@ extern "C" int wn_train_forward(wn_handle* h, const float* params, const int32_t
         hipLaunchKernelGGL(wn_cvt_bf16, dim3((unsigned)((n / 2 + 256) / 256)), dim3(256), 0, st, fw, bw, n);
         wn_launch_cvt_t(st, fw + h->fw_off_fg, (long long)2 * R * 2 * D, bt_fg, 2 * R, 2 * D, NL);        // [2R][2D] -> [2D][2R]
         wn_launch_cvt_t(st, fw + h->fw_off_res, (long long)D * R, bt_res, D, R, NL);                          // [D][R] -> [R][D]
-        wn_launch_cvt_t(st, fw + h->fw_off_skip, (long long)G * D * S, bt_skip, G * D, S, NL / G);            // [G*D][S] -> [S][G*D] per block
+        wn_launch_cvt_t(st, fw + h->fw_off_skip, (long long)G * D * S, bt_skip, G * D, S, NL / G);            // [G*D][S] -> [S][G*D] per full block
+        if (NL % G) {   // the last block is shorter when G does not divide NL (WN_TRAIN_SKIP_BLOCK): [cnt*D][S] -> [S][cnt*D] of its own
+            const int first = NL - NL % G;
+            wn_launch_cvt_t(st, fw + h->fw_off_skip + (size_t)first * D * S, 0, bt_skip + (size_t)first * S * D, (NL % G) * D, S, 1);
+        }
         wn_launch_cvt_t(st, fw + h->fw_off_w1, 0, bt_w1, S, E, 1);
         wn_launch_cvt_t(st, fw + h->fw_off_w2, 0, bt_w2, E, C, 1);
     }

@@ -491,6 +491,17 @@ def test_bf16_step_one_launch_per_forward_layer_equals_the_two_launch_form(monke
             continue
         rel = float((g_f[k] - g_t[k]).norm() / (g_t[k].norm() + 1e-30))
         assert rel <= 1e-5, (k, rel)
+    # deterministic mode (ordered reduction of the weight gradients' row splits): the gradients are equal bit for bit as well
+    m.deterministic_gradients = True
+    out_fd, loss_fd, g_fd = _step(m, x, target, torch_path=False)
+    monkeypatch.setenv("WN_NO_FUSED_LAYER", "1")
+    out_td, loss_td, g_td = _step(m, x, target, torch_path=False)
+    monkeypatch.delenv("WN_NO_FUSED_LAYER")
+    assert torch.equal(out_fd, out_td) and loss_fd == loss_td
+    for k in g_fd:
+        assert (g_fd[k] is None) == (g_td[k] is None), k
+        if g_fd[k] is not None:
+            assert torch.equal(g_fd[k].view(torch.int32), g_td[k].view(torch.int32)), k
 
 
 def test_training_abi_error_codes():
