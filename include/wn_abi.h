@@ -228,7 +228,25 @@ int wn_export_queue(wn_handle* h, int32_t layer, int32_t stream, float* host_dat
  * torch path for those, which reproduces what the reference does there. */
 int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t output_length, float* logits, void* hip_stream);
 
-/* Operand precision of wn_forward, wn_train_forward and the products of wn_train_backward (activation gradients AND weight
+/* Teacher-forced scoring -- what WavenetTrainer.validate() computes per batch (wavenet_training.py:89-112: output = model(x);
+ * F.cross_entropy(output, target); torch.max(output, 1)[1]; torch.eq / torch.sum) and what a caller asks who wants the log-likelihood of
+ * audio -- without the logits ever reaching memory.  `indices` (int32 [N][L]), the geometry, the shape limits and the WN_E_* codes are
+ * wn_forward's; `targets` is int64 [N*output_length] (torch's dtype; row = n*output_length + t).  All pointers are DEVICE pointers:
+ *   row_nll  [N*output_length] fp32 | NULL: logsumexp(logits) - logits[target] in nats (the row's negative log-likelihood)
+ *   row_pred [N*output_length] int32 | NULL: the class of the largest logit, the FIRST index on ties (torch.max)
+ *   sums     [3] fp64, required: sum of row_nll, number of rows with row_pred == target, number of rows counted
+ * A target outside [0, classes) gives a NaN row_nll (as wn_train_loss), its row_pred is still written, and the row is left out of all three
+ * sums.  The sums are added in a fixed order in fp64: two calls on the same inputs return the same bits.  mean loss = sums[0] / sums[2],
+ * accuracy = sums[1] / sums[2].  The dilated-conv stack is wn_forward's; the head (end_conv_1, end_conv_2) and the row statistics run as ONE
+ * kernel that keeps the head's hidden activations and the logits on the compute unit (csrc/wn_score.h; 256 classes, end channels a multiple
+ * of 64, fp32 operands), else -- other shapes, and bf16 operands, where it measured faster -- as wn_forward's two head products into the
+ * handle's workspace and a row kernel over them.  WN_NO_FUSED_SCORE=1 / =0 with WN_TESTING=1 pins the second / the first form (A/B runs;
+ * wn_info.dev_overrides says so).  Honours wn_set_forward_precision.  Asynchronous on hip_stream.  (Added without a new WN_ABI_VERSION: no existing call or struct changed; a caller
+ * that must run against an older library of version 5 looks the symbol up.) */
+int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64_t N, int64_t L, int64_t output_length,
+             float* row_nll, int32_t* row_pred, double* sums, void* hip_stream);
+
+/* Operand precision of wn_forward, wn_score, wn_train_forward and the products of wn_train_backward (activation gradients AND weight
  * gradients; the one-hot product of start_conv stays fp32):
  * 0 = fp32 matrix-core GEMMs (default: equals the reference's fp32 graph to rounding), 1 = bf16 operands with fp32
  * accumulation (residual stream, skip sum and all accumulators stay fp32; the training step keeps the activations that only

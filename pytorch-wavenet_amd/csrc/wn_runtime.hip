@@ -16,6 +16,7 @@
 #include "wn_kernel_v3.h"
 #include "wn_stacked_table.h"
 #include "wn_forward.h"
+#include "wn_score.h"
 #include "wn_gate.h"
 #include "wn_optim.h"
 
@@ -415,6 +416,7 @@ struct wn_handle {
     std::vector<int32_t> dil;
     float* d_tws; size_t tws_floats;  // training workspace (saved activations + backward temporaries)
     float* d_xent = nullptr; size_t xent_rows = 0;  // wn_train_loss: per-row losses
+    double* d_score_part = nullptr; size_t score_parts = 0;  // wn_score: one {sum nll, hits, rows} triple per workgroup
     WnTrainLay train; bool train_valid;
     // admission of persistent jobs (wn_gate.h)
     // wn_train_backward: the weight-gradient products run on a second stream next to the activation-gradient chain (wn_train.inl)
@@ -467,6 +469,7 @@ extern "C" void wn_destroy(wn_handle* h) {
     rt_free(h->d_wg_map); rt_free(h->d_ring_off); rt_free(h->d_gran); rt_free(h->d_status); rt_free(h->d_prof); rt_free(h->d_ws);
     rt_free(h->d_tws);
     rt_free(h->d_xent);
+    rt_free(h->d_score_part);
     rt_free(h->det_ws[0].buf); rt_free(h->det_ws[1].buf);
     delete h;
 }
@@ -766,6 +769,7 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
                            need, n_wg, cap, per_cu);
         }
     }
+    (void)wn_dev_env("WN_NO_FUSED_SCORE");   // (wn_score reads it per call; a handle created under it says so from the start)
     h->dev_overrides = g_dev_env_used;
     *out = h;
     return WN_OK;
@@ -1272,19 +1276,49 @@ static int wn_forward_geometry(const wn_handle* h, long long L, long long out_le
 }
 
 // WaveNetModel.forward() for one-hot inputs (class indices), see wn_forward.h.  Asynchronous on hip_stream.
-extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, void* hip_stream) {
-    g_err[0] = 0;
-    if (!h || !indices || !logits) return wn_fail(WN_E_BADARG, "wn_forward: NULL argument");
-    if (!h->chains.empty()) return wn_forward(h->chains[0], indices, N, L, out_len, logits, hip_stream);  // every chain holds the weights
-    if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_forward: wn_load_weights has not been called");
-    if (N < 1 || out_len < 1) return wn_fail(WN_E_BADARG, "wn_forward: N and output_length must be >= 1");
+// What wn_score asks of the forward instead of logits: the head's two products and the row statistics in one kernel (wn_score.h), or -- shapes that kernel is
+// not written for, bf16 operands (see wn_fused_score_enabled), WN_NO_FUSED_SCORE=1 with WN_TESTING=1 -- the two head products into the workspace and wn_score_rows over them.
+struct WnScoreOut {
+    const int64_t* targets;
+    float* row_nll;
+    int32_t* row_pred;
+    double* sums;
+};
+// Default: the fused kernel with fp32 operands, the unfused path with bf16 operands -- measured at config 5's evaluation batch (profiles/r07_score.txt) the fused
+// bf16 kernel is 0.5-1.7 ms SLOWER than the unfused path (it re-reads the skip tile once per chunk of end channels, and with bf16 operands the head is bound by
+// those reads, not by the matrix cores); fp32 is level to 0.6 ms faster.  WN_NO_FUSED_SCORE=1 / =0 (with WN_TESTING=1) pins the unfused / the fused path.
+static bool wn_fused_score_enabled(wn_handle* h, bool bf16) {
+    const char* off = wn_dev_env("WN_NO_FUSED_SCORE");
+    if (off) h->dev_overrides = 1;   // (read per call, not at wn_create: the handle reports it from the first scoring call on)
+    if (off && (off[0] == '1' || off[0] == '0')) return off[0] == '0';
+    return !bf16;
+}
+
+static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, const WnScoreOut* score, void* hip_stream,
+                          const char* who) {
+    if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
+    if (N < 1 || out_len < 1) return wn_fail(WN_E_BADARG, "%s: N and output_length must be >= 1", who);
     const WnPlan& pl = h->plan;
     const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
-    if (!h->fw_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_forward: needs kernel_size 2 and channel counts that are multiples of 32");
-    if ((long long)N * L >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "wn_forward: N*L must stay below 2^31 rows");
+    if (!h->fw_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2 and channel counts that are multiples of 32", who);
+    if ((long long)N * L >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "%s: N*L must stay below 2^31 rows", who);
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
     WnFwdGeom geo;
-    { int rc = wn_forward_geometry(h, L, out_len, geo, "wn_forward"); if (rc) return rc; }
+    { int rc = wn_forward_geometry(h, L, out_len, geo, who); if (rc) return rc; }
+    const long long Mrows = (long long)N * out_len;
+    const bool score_fused = score && C == 256 && S % 32 == 0 && E % WN_SCORE_EC == 0 && wn_fused_score_enabled(h, h->fw_bf16 && h->fwb_ok);
+    size_t n_part = 0;
+    if (score) {   // one fp64 triple per workgroup of the kernel that scores
+        n_part = (size_t)(score_fused ? (Mrows + WN_SCORE_TM - 1) / WN_SCORE_TM : (Mrows + WN_SCORE_ROWS_PER_WG - 1) / WN_SCORE_ROWS_PER_WG);
+        if (h->score_parts < n_part) {
+            if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+            (void)hipDeviceSynchronize();
+            rt_free(h->d_score_part);
+            h->d_score_part = (double*)rt_malloc(n_part * 3 * sizeof(double));
+            h->score_parts = h->d_score_part ? n_part : 0;
+            if (!h->d_score_part) return wn_fail(WN_E_NOMEM, "%s: %lld partial sums", who, (long long)n_part);
+        }
+    }
     const std::vector<long long>& need = geo.rows;
     const size_t x_fl = (size_t)N * L * R, z_fl = (size_t)N * need[1 < NL ? 1 : NL] * D > (size_t)N * need[NL] * D ? (size_t)N * need[1 < NL ? 1 : NL] * D : (size_t)N * need[NL] * D;
     // The skip sum over layers is accumulated G layers at a time: the gate epilogue also drops z (last output_length rows)
@@ -1297,18 +1331,20 @@ extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64
     // rows (zg) is stored as bf16.  Same roundings as the two-launch form (every value is rounded to bf16 once, where it becomes an operand).
     const bool fuse = h->fw_bf16 && h->fwb_ok && R == 128 && D == 128 && wn_fused_layer_enabled();
     const size_t xh_fl = fuse ? ((x_fl + 1) / 2 + 63) / 64 * 64 : 0;
-    const size_t total = 2 * x_fl + z_fl + skip_fl + e_fl + zg_fl + 2 * xh_fl;
+    const size_t lg_fl = (score && !score_fused) ? (size_t)Mrows * C : 0;   // (unfused scoring: the logits live in the workspace)
+    const size_t total = 2 * x_fl + z_fl + skip_fl + e_fl + zg_fl + 2 * xh_fl + lg_fl;
     if (h->ws_floats < total) {
         if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
         rt_free(h->d_ws);
         h->d_ws = (float*)rt_malloc(total * 4);
         h->ws_floats = h->d_ws ? total : 0;
-        if (!h->d_ws) return wn_fail(WN_E_NOMEM, "wn_forward: workspace of %.1f MB", total * 4e-6);
+        if (!h->d_ws) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
     }
     float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl; float* skip = z + z_fl; float* ev = skip + skip_fl;
     float* zg = ev + e_fl;
     unsigned short* xha = fuse ? reinterpret_cast<unsigned short*>(zg + zg_fl) : nullptr;
     unsigned short* xhb = fuse ? reinterpret_cast<unsigned short*>(zg + zg_fl + xh_fl) : nullptr;
+    if (lg_fl) logits = zg + zg_fl + 2 * xh_fl;
     hipStream_t st = (hipStream_t)hip_stream;
     {
         const long long rows = N * L;
@@ -1377,7 +1413,16 @@ extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64
         float* t = xin; xin = xout; xout = t;
         unsigned short* th = xhin; xhin = xhout; xhout = th;
     }
-    {   // head: relu(skip) -> end_conv_1 (+b, relu) -> end_conv_2 (+b)     wavenet_model.py:167-169
+    if (score_fused) {   // head and row statistics in one kernel: neither ev nor the logits reach HBM
+        WnScoreArgs sa;
+        memset(&sa, 0, sizeof(sa));
+        sa.skip = skip; sa.M = Mrows; sa.S = S; sa.E = E;
+        sa.w1t = fw + h->fw_off_w1; sa.w2t = fw + h->fw_off_w2; sa.b1 = fw + h->fw_off_b1; sa.b2 = fw + h->fw_off_b2;
+        if (bf16) { sa.w1h = fwb + h->fwb_off_w1; sa.w2h = fwb + h->fwb_off_w2; }
+        sa.targets = reinterpret_cast<const long long*>(score->targets); sa.row_nll = score->row_nll; sa.row_pred = score->row_pred; sa.part = h->d_score_part;
+        if (bf16) hipLaunchKernelGGL(wn_score_head_bf16, dim3((unsigned)n_part), dim3(256), 0, st, sa);
+        else hipLaunchKernelGGL(wn_score_head, dim3((unsigned)n_part), dim3(256), 0, st, sa);
+    } else {   // head: relu(skip) -> end_conv_1 (+b, relu) -> end_conv_2 (+b)     wavenet_model.py:167-169
         WnGemmArgs a;
         memset(&a, 0, sizeof(a));
         a.a0 = a.a1 = WnRowMap{skip, out_len * S, S, 0};
@@ -1391,8 +1436,30 @@ extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64
         a.c = WnRowMap{logits, out_len * C, C, 0};
         a.M = N * out_len; a.rows_per_batch = (int)out_len;
         launch(WN_EPI_PLAIN, a, bf16 ? fwb + h->fwb_off_w2 : nullptr);
+        if (score)
+            hipLaunchKernelGGL(wn_score_rows, dim3((unsigned)n_part), dim3(256), 0, st, logits, C, reinterpret_cast<const long long*>(score->targets), Mrows,
+                               score->row_nll, score->row_pred, h->d_score_part);
     }
-    return rt_hip(hipGetLastError(), "wn_forward launches");
+    if (score) hipLaunchKernelGGL(wn_score_reduce, dim3(1), dim3(1024), 0, st, h->d_score_part, (long long)n_part, score->sums);
+    return rt_hip(hipGetLastError(), score ? "wn_score launches" : "wn_forward launches");
+}
+
+extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !indices || !logits) return wn_fail(WN_E_BADARG, "wn_forward: NULL argument");
+    if (!h->chains.empty()) return wn_forward(h->chains[0], indices, N, L, out_len, logits, hip_stream);  // every chain holds the weights
+    return wn_forward_run(h, indices, N, L, out_len, logits, nullptr, hip_stream, "wn_forward");
+}
+
+// Teacher-forced scoring (include/wn_abi.h): wn_forward's stack up to the finished skip rows, then the head and the row statistics (wn_score.h).
+extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64_t N, int64_t L, int64_t out_len, float* row_nll, int32_t* row_pred,
+                        double* sums, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !indices || !targets || !sums) return wn_fail(WN_E_BADARG, "wn_score: NULL argument");
+    if (wn_dev_env("WN_NO_FUSED_SCORE")) h->dev_overrides = 1;   // (the front handle of a job of several chains reports it too)
+    if (!h->chains.empty()) return wn_score(h->chains[0], indices, targets, N, L, out_len, row_nll, row_pred, sums, hip_stream);  // every chain holds the weights
+    const WnScoreOut so{targets, row_nll, row_pred, sums};
+    return wn_forward_run(h, indices, N, L, out_len, nullptr, &so, hip_stream, "wn_score");
 }
 
 // Batched (teacher-forced) priming: the n_prime = n_given - 1 priming evaluations of generate_fast (wavenet_model.py:259-269)

@@ -74,7 +74,9 @@ class wn_train_tensors(ctypes.Structure):
 
 
 EXPORTS = ["wn_abi_version", "wn_create", "wn_destroy", "wn_load_weights", "wn_reset", "wn_generate", "wn_wait",
-           "wn_get_info", "wn_export_queue", "wn_forward", "wn_set_forward_precision", "wn_prime", "wn_train_get_layout", "wn_train_export_params", "wn_train_forward", "wn_train_backward", "wn_train_loss", "wn_train_pack", "wn_train_unpack_grads", "wn_train_set_deterministic", "wn_adam_step", "wn_profile_next", "wn_profile_read", "wn_last_error"]
+           "wn_get_info", "wn_export_queue", "wn_forward", "wn_set_forward_precision", "wn_prime", "wn_train_get_layout", "wn_train_export_params", "wn_train_forward", "wn_train_backward", "wn_train_loss", "wn_train_pack", "wn_train_unpack_grads", "wn_train_set_deterministic", "wn_adam_step", "wn_profile_next", "wn_profile_read", "wn_last_error", "wn_score"]
+# Functions added to ABI version 5 after its first libraries: a library of that version may lack them (Library.has says; the caller of a missing one raises).
+OPTIONAL_EXPORTS = ("wn_score",)
 
 
 TRAIN_SECTIONS = ("fg", "bfg", "res", "bres", "skip", "bskip", "bskip_total", "w1", "b1", "w2", "b2", "start_t", "start_b")
@@ -95,8 +97,9 @@ class Library:
         import torch  # noqa: F401
         self.dll = ctypes.CDLL(path)
         d = self.dll
+        self.missing = tuple(n for n in OPTIONAL_EXPORTS if not hasattr(d, n))
         for name in EXPORTS:
-            if not hasattr(d, name):
+            if not hasattr(d, name) and name not in self.missing:
                 raise RuntimeError("%s does not export %s" % (path, name))
         d.wn_abi_version.restype = ctypes.c_int
         d.wn_last_error.restype = ctypes.c_char_p
@@ -125,11 +128,18 @@ class Library:
         d.wn_adam_step.argtypes = [ctypes.POINTER(wn_adam_args)]
         d.wn_profile_next.argtypes = [ctypes.c_void_p, ctypes.c_int32]
         d.wn_profile_read.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64]
+        if self.has("wn_score"):
+            d.wn_score.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
+                                   ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         for name in EXPORTS:
-            if name not in ("wn_destroy", "wn_last_error"):
+            if name not in ("wn_destroy", "wn_last_error") and name not in self.missing:
                 getattr(d, name).restype = ctypes.c_int
         if d.wn_abi_version() != ABI_VERSION:
             raise RuntimeError("%s: ABI version %d, expected %d" % (path, d.wn_abi_version(), ABI_VERSION))
+
+    def has(self, name):
+        """False for a function of OPTIONAL_EXPORTS that this library does not export."""
+        return name not in self.missing
 
     def last_error(self):
         return (self.dll.wn_last_error() or b"").decode("utf-8", "replace")

@@ -152,6 +152,28 @@ class Engine:
         self.lib.check(self.lib.dll.wn_forward(self._h, idx.data_ptr(), N, L, int(output_length), out.data_ptr(), self.mem.stream()))
         return out
 
+    def score(self, indices, targets, output_length, want_rows=False, want_pred=False):
+        """Teacher-forced scoring (C ABI wn_score): indices int (N, L), targets int (N*output_length,) or (N, output_length) -> dict with
+        'sums' (float64 (3,) device tensor: sum of the rows' negative log-likelihoods in nats, rows whose argmax equals the target, rows counted)
+        and, on request, 'row_nll' float32 / 'row_pred' int32 of shape (N, output_length).  A target outside [0, classes) gives a NaN row_nll and
+        leaves the row out of the sums.  Device tensors, asynchronous: nothing is synchronised here."""
+        if not self.lib.has("wn_score"):
+            raise RuntimeError("mi355_wavenet: %s does not export wn_score (a library built before teacher-forced scoring was added): "
+                               "rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
+        import torch
+        idx = torch.as_tensor(indices).to(self.mem.device, torch.int32).contiguous()
+        N, L = idx.shape
+        M = N * int(output_length)
+        tgt = torch.as_tensor(targets).to(self.mem.device, torch.int64).reshape(-1).contiguous()
+        if tgt.numel() != M:
+            raise ValueError("targets hold %d values, %d items x output_length %d need %d" % (tgt.numel(), N, output_length, M))
+        sums = torch.empty(3, dtype=torch.float64, device=self.mem.device)
+        rows = torch.empty(N, int(output_length), dtype=torch.float32, device=self.mem.device) if want_rows else None
+        pred = torch.empty(N, int(output_length), dtype=torch.int32, device=self.mem.device) if want_pred else None
+        self.lib.check(self.lib.dll.wn_score(self._h, idx.data_ptr(), tgt.data_ptr(), N, L, int(output_length), self.mem.ptr(rows), self.mem.ptr(pred),
+                                             sums.data_ptr(), self.mem.stream()))
+        return {"sums": sums, "row_nll": rows, "row_pred": pred}
+
     def profile_next(self, n_items):
         self.lib.check(self.lib.dll.wn_profile_next(self._h, int(n_items)))
 

@@ -20,6 +20,7 @@ What is different underneath:
     gradients w.r.t. the input, kernel_size != 2, a class count that is not a multiple of 32 under autograd (channel counts that are not
     multiples of 32 run natively, zero-padded: with and, since round 6, under autograd), and the input lengths for which the reference itself has no defined result (its error, or its shapes, are reproduced).
 """
+import collections
 import os
 import os.path
 import time
@@ -31,6 +32,9 @@ import numpy as np
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
+
+# What WaveNetModel.score_indices returns: device tensors (see there).
+ScoreResult = collections.namedtuple("ScoreResult", ["loss", "accuracy", "n", "row_nll", "pred", "sums"])
 
 
 class WaveNetModel(nn.Module):
@@ -326,6 +330,36 @@ class WaveNetModel(nn.Module):
         out = self._index_call(lambda: eng.forward_indices(idx, self.output_length))
         self._wn_forward_calls = getattr(self, "_wn_forward_calls", 0) + 1
         return out
+
+    def score_indices(self, indices, targets=None, check=True, want_rows=False, want_pred=False):
+        """Extension: teacher-forced scoring on class indices -- what WavenetTrainer.validate() computes per batch (wavenet_training.py:89-112) and
+        the log-likelihood of audio under the model -- on the engine (C ABI wn_score): the logits never reach memory.  ``indices`` (N, L) and
+        ``targets`` (N, output_length) or (N*output_length,): the class each output position should predict.  ``targets=None``: ``indices`` is the
+        dataset's own window of L + 1 samples per item (audio_data.py: item_indices); the input is its first L samples and the targets are its last
+        output_length, as WavenetDataset.__getitem__ cuts them.  Returns a ScoreResult of DEVICE tensors (nothing is synchronised until the caller
+        reads one): loss (mean negative log-likelihood in nats = F.cross_entropy), accuracy, n (rows counted), with want_rows / want_pred row_nll float32 /
+        pred int32 (N, output_length) (else None),
+        sums (float64 (3,): sum of row_nll, hits, n).  A target outside [0, classes) gives a NaN row_nll and is left out of loss, accuracy and n.
+        Same checks and errors as forward_indices; ``check=False`` skips the range check of the indices."""
+        idx = torch.as_tensor(indices)
+        if targets is None:
+            if idx.dim() != 2:
+                raise ValueError("indices must be (N, L) class indices")
+            if idx.size(1) < self.output_length + 1:
+                raise ValueError("windows of %d sample(s): targets=None needs at least output_length + 1 = %d" % (idx.size(1), self.output_length + 1))
+            targets = idx[:, -self.output_length:]
+            idx = idx[:, :-1]
+        idx = self._checked_indices(idx, check)
+        tgt = torch.as_tensor(targets)
+        if tgt.numel() != idx.size(0) * self.output_length:
+            raise ValueError("targets hold %d values, %d items x output_length %d need %d" % (
+                tgt.numel(), idx.size(0), self.output_length, idx.size(0) * self.output_length))
+        eng = self._forward_engine()
+        self._apply_precision(eng)
+        out = self._index_call(lambda: eng.score(idx, tgt, self.output_length, want_rows=want_rows, want_pred=want_pred))
+        self._wn_forward_calls = getattr(self, "_wn_forward_calls", 0) + 1
+        sums = out["sums"]
+        return ScoreResult(loss=sums[0] / sums[2], accuracy=sums[1] / sums[2], n=sums[2], row_nll=out["row_nll"], pred=out["row_pred"], sums=sums)
 
     @staticmethod
     def _index_call(fn):
