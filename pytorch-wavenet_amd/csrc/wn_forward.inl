@@ -1,0 +1,379 @@
+// wn_forward.inl -- host side of the batched forward (included by wn_runtime.hip; GPU build only): the launchers of the matrix products of
+// wn_forward.h, wn_forward / wn_score (WaveNetModel.forward() for one-hot inputs), wn_prime (batched priming of the generation queues).
+
+// One "NN" product C = A . B^T of wn_forward.h.  bn != NULL: bf16 operands (B given as [N][K] bf16 -- or as two [N][ldb] halves
+// bn / bn1 --, A rounded while staged), fp32 accumulation; else fp32 operands.  Products with N % 256 == 0 take the 128 x 256 tile.
+static void wn_launch_nn(hipStream_t st, int epi, const WnGemmArgs& a, const unsigned short* bn = nullptr, const unsigned short* bn1 = nullptr, int ldb = 0) {
+    const bool wide = bn && a.N % 256 == 0 && epi != WN_EPI_GATE_BWD;
+    const unsigned mt = (unsigned)((a.M + 127) / 128), nt = (unsigned)(wide ? a.N / 256 : (a.N + 127) / 128);
+    const dim3 grid(mt * nt);   // 1-D (M / 128 can exceed a grid's y limit): row tiles fastest, then column tiles
+    if (bn) {
+        WnGemmArgsBf16 b;
+        b.g = a; b.bn = bn; b.bn1 = bn1; b.ldb = ldb;
+        if (wide) {
+            if (epi == WN_EPI_GATE && a.a_bf16) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE, 8, true>), grid, dim3(512), 0, st, b);   // (bf16-stored A: the shadow of x)
+            else if (epi == WN_EPI_GATE) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE, 8>), grid, dim3(512), 0, st, b);
+            else if (a.a_bf16) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 8, true>), grid, dim3(512), 0, st, b);   // (bf16-stored A: the grouped skip product)
+            else hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 8>), grid, dim3(512), 0, st, b);
+        } else {
+            if (epi == WN_EPI_GATE) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE, 4>), grid, dim3(256), 0, st, b);   // (never with a bf16-stored A: wn_train_layout_ws)
+            else if (epi == WN_EPI_GATE_BWD) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE_BWD, 4>), grid, dim3(256), 0, st, b);
+            else if (a.a_bf16) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 4, true>), grid, dim3(256), 0, st, b);   // (bf16-stored A: the residual and dx products)
+            else hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 4>), grid, dim3(256), 0, st, b);
+        }
+        return;
+    }
+    if (epi == WN_EPI_GATE) hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_GATE>, grid, dim3(256), 0, st, a);
+    else if (epi == WN_EPI_GATE_BWD) hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_GATE_BWD>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a);
+}
+
+// One forward layer in one launch (wn_fwd_layer_bf16): `a` = the filter/gate product's arguments (bf16 operands, c_bf16 = 1; a.c.base may be
+// NULL: z is not stored), `r` = the residual product's (its bias, cin, c, c_h are used).  Returns false when the shape is not the fused
+// kernel's (the caller launches the two products).  WN_NO_FUSED_LAYER=1 (with WN_TESTING=1) switches it off for A/B runs.
+static bool wn_fused_layer_enabled() { return !wn_dev_flag("WN_NO_FUSED_LAYER"); }
+static bool wn_launch_layer(hipStream_t st, const WnGemmArgs& a, const unsigned short* bn_fg, const WnGemmArgs& r, const unsigned short* bn_res) {
+    if (!bn_fg || !bn_res || !a.a_bf16 || a.N != 256 || r.N != 128 || r.K != 128 || a.K % 32 != 0 || a.k_split % 32 != 0 || !a.c_bf16 || a.relu_a || r.relu_a || r.relu_c ||
+        r.mask || r.cin_skip_lo || r.M != a.M || r.rows_per_batch != a.rows_per_batch) return false;   // (x from its bf16 shadow, z kept as bf16, the same rows in both products)
+    if (!wn_fused_layer_enabled()) return false;
+    WnGemmArgsBf16 b;
+    b.g = a; b.bn = bn_fg; b.bn1 = nullptr; b.ldb = 0;
+    WnLayerArgs la;
+    la.bn = bn_res; la.bias = r.bias; la.cin = r.cin; la.c = r.c; la.c_h = r.c_h; la.N = r.N;
+    const dim3 grid(wn_layer_grid(a.M));
+    hipLaunchKernelGGL(wn_fwd_layer_bf16, grid, dim3(512), 0, st, b, la);
+    return true;
+}
+
+// The backward's fused pair (wn_bwd_layer_bf16): `a` = the dx product of layer l (bf16-stored A in two views, weight banks bn / bn1 with row
+// length ldb), `b` = the gate-derivative product of layer l - 1, whose A operand is `a`'s output.  Returns false when the shapes are not
+// the fused kernel's (the caller launches the two products).
+static bool wn_launch_bwd_layer(hipStream_t st, const WnGemmArgs& a, const unsigned short* bn, const unsigned short* bn1, int ldb,
+                                const WnGemmArgs& b, const unsigned short* bn_res) {
+    if (!bn || !bn_res || !a.a_bf16 || a.N != 128 || a.K % 32 != 0 || a.bias || a.relu_a || a.relu_c || a.mask || a.c_h || a.c_bf16 ||
+        b.N != 128 || b.K != 128 || !b.c_bf16 || !b.gate_packed || b.M != a.M || b.rows_per_batch != a.rows_per_batch) return false;
+    if (b.a0.base != a.c.base || b.a0.t0 != a.c.t0 || b.a0.batch_stride != a.c.batch_stride || b.a0.row_stride != a.c.row_stride) return false;   // (the same rows)
+    if (!wn_fused_layer_enabled()) return false;
+    if (wn_dev_flag("WN_NO_FUSED_BWD")) return false;   // (A/B: the forward's fused layer alone)
+    WnGemmArgsBf16 x, y;
+    x.g = a; x.bn = bn; x.bn1 = bn1; x.ldb = ldb;
+    y.g = b; y.bn = bn_res; y.bn1 = nullptr; y.ldb = 0;
+    hipLaunchKernelGGL(wn_bwd_layer_bf16, dim3(wn_layer_grid(a.M)), dim3(512), 0, st, x, y);
+    return true;
+}
+
+// ------------------------------------------------------------------------------------------------ product descriptions
+// Every field a helper does not name is zero / NULL (= that feature off); the caller sets the few that are special to its product.
+// `rows` rows of `cols` elements per batch entry, dense; t0 = the first row a product reads or writes
+static WnRowMap wn_rows(const float* base, long long rows, long long cols, long long t0 = 0) { return WnRowMap{base, rows * cols, cols, t0}; }
+// C = [a0 (k < k_split) | a1] . B^T (+ bias): M rows in batch entries of rows_per_batch -- the two-view form of the tap products
+static WnGemmArgs wn_nn2(const WnRowMap& a0, const WnRowMap& a1, int k_split, int K, const float* bt, int N, const float* bias, const WnRowMap& c, long long M,
+                         long long rows_per_batch) {
+    WnGemmArgs g = {};
+    g.a0 = a0; g.a1 = a1; g.k_split = k_split; g.K = K; g.bt = bt; g.N = N; g.bias = bias; g.c = c; g.M = M; g.rows_per_batch = (int)rows_per_batch;
+    return g;
+}
+// C = A . B^T (+ bias) (+ cin where cin.base != NULL)
+static WnGemmArgs wn_nn(const WnRowMap& a, int K, const float* bt, int N, const float* bias, const WnRowMap& c, long long M, long long rows_per_batch,
+                        const WnRowMap& cin = WnRowMap{nullptr, 0, 0, 0}) {
+    WnGemmArgs g = wn_nn2(a, a, K, K, bt, N, bias, c, M, rows_per_batch);
+    g.cin = cin;
+    return g;
+}
+// The weight-gradient form: C [Ka][ldc] (+)= A^T . B over M rows
+static WnGemmTnArgs wn_tn(const WnRowMap& a, int Ka, const WnRowMap& b, int Nb, float* c, int ldc, long long M, long long rows_per_batch) {
+    WnGemmTnArgs g = {};
+    g.a = a; g.Ka = Ka; g.b = b; g.Nb = Nb; g.c = c; g.ldc = ldc; g.M = M; g.rows_per_batch = (int)rows_per_batch;
+    return g;
+}
+
+// The pieces wn_forward, wn_prime and wn_train_forward share.  `fw` = the packed fp32 bank (layout o), n = batch entries, x = the layer's input at
+// the first of its `rows` output positions.
+// z = gate([x(t - d) | x(t)] . Wfg^T + b) of layer l
+static WnGemmArgs wn_layer_fg(const WnPlan& pl, const wn_train_layout& o, const float* fw, int l, const WnRowMap& x, long long d, const WnRowMap& z, long long n,
+                              long long rows) {
+    WnRowMap x0 = x;
+    x0.t0 -= d;
+    return wn_nn2(x0, x, pl.R, 2 * pl.R, fw + o.fg + (size_t)l * 2 * pl.R * 2 * pl.D, 2 * pl.D, pl.has_bias ? fw + o.bfg + (size_t)l * 2 * pl.D : nullptr, z, n * rows, rows);
+}
+// x' = z . Wres^T + bres + x(t) of layer l
+static WnGemmArgs wn_layer_res(const WnPlan& pl, const wn_train_layout& o, const float* fw, int l, const WnRowMap& z, const WnRowMap& x, const WnRowMap& xout,
+                               long long n, long long rows) {
+    return wn_nn(z, pl.D, fw + o.res + (size_t)l * pl.D * pl.R, pl.R, pl.has_bias ? fw + o.bres + (size_t)l * pl.R : nullptr, xout, n * rows, rows, x);
+}
+// skip (+)= ZG . [Wskip of the layers first .. first + cnt - 1]^T   (K = cnt * D; the first group also adds bskip_total, the sum of all layers' skip biases)
+static WnGemmArgs wn_skip_group(const WnPlan& pl, const wn_train_layout& o, const float* fw, int first, int cnt, const WnRowMap& zg, const float* bskip_total,
+                                float* skip, long long n, long long out_len) {
+    const WnRowMap sk = wn_rows(skip, out_len, pl.S);
+    return wn_nn(zg, cnt * pl.D, fw + o.skip + (size_t)first * pl.D * pl.S, pl.S, (pl.has_bias && first == 0) ? bskip_total : nullptr, sk, n * out_len, out_len,
+                 first > 0 ? sk : WnRowMap{nullptr, 0, 0, 0});
+}
+// head: relu(skip) -> end_conv_1 (+b, relu) -> end_conv_2 (+b)     wavenet_model.py:167-169
+struct WnHeadArgs { WnGemmArgs e, logits; };
+static WnHeadArgs wn_head(const WnPlan& pl, const wn_train_layout& o, const float* fw, const float* skip, float* ev, float* logits, long long n, long long out_len) {
+    WnHeadArgs hd;
+    hd.e = wn_nn(wn_rows(skip, out_len, pl.S), pl.S, fw + o.w1, pl.E, fw + o.b1, wn_rows(ev, out_len, pl.E), n * out_len, out_len);
+    hd.e.relu_a = 1; hd.e.relu_c = 1;
+    hd.logits = wn_nn(wn_rows(ev, out_len, pl.E), pl.E, fw + o.w2, pl.C, fw + o.b2, wn_rows(logits, out_len, pl.C), n * out_len, out_len);
+    return hd;
+}
+
+// Time geometry of WaveNetModel.forward() for clips of L samples (wavenet_modules.py:10-39 `dilate`, wavenet_model.py:125-196).
+// In absolute time every layer's sequence ends at L (a kernel-size-2 dilated conv drops its input's first d positions).  Where the
+// length of a layer's input is not a multiple of its dilation the reference left-pads it with ZERO ACTIVATIONS (wavenet_modules.py:24-27),
+// so layer l's input lives on [a[l], L) preceded by pad[l] = (-(L - a[l])) mod d zeros, and its output on [a[l+1], L) with
+// a[l+1] = a[l] - pad[l] + d.  With L >= receptive_field + output_length - 1 none of the returned positions can see a pad zero (the
+// regime of rounds 1-3); shorter clips can: the tap x(t - d) then reads as zero for t - d < a[l] (row windows of the GEMMs' A views).
+//   rows[l] = trailing positions of layer l's input that are computed = min(rows[l+1] + d, L - a[l]);   zlo[l] = leading output rows of
+//   layer l whose tap is a pad zero.
+// Returns WN_E_UNSUPPORTED where the reference itself has no defined result: a layer left with no output position, the skip
+// un-dilation quirk at a per-row length of 1, fewer than output_length final positions (its view fails).
+static int wn_forward_geometry(const wn_handle* h, long long L, long long out_len, WnFwdGeom& g, const char* who) {
+    const std::string why = wn_forward_geometry_host(h->dil.data(), h->plan.NL, L, out_len, g);   // (wn_plan.h: plain host arithmetic, tested with g++)
+    if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
+    return WN_OK;
+}
+
+// WaveNetModel.forward() for one-hot inputs (class indices), see wn_forward.h.  Asynchronous on hip_stream.
+// What wn_score asks of the forward instead of logits: the head's two products and the row statistics in one kernel (wn_score.h), or -- shapes that kernel is
+// not written for, bf16 operands (see wn_fused_score_enabled), WN_NO_FUSED_SCORE=1 with WN_TESTING=1 -- the two head products into the workspace and wn_score_rows over them.
+struct WnScoreOut {
+    const int64_t* targets;
+    float* row_nll;
+    int32_t* row_pred;
+    double* sums;
+};
+// Default: the fused kernel with fp32 operands, the unfused path with bf16 operands -- measured at config 5's evaluation batch (profiles/r07_score.txt) the fused
+// bf16 kernel is 0.5-1.7 ms SLOWER than the unfused path (it re-reads the skip tile once per chunk of end channels, and with bf16 operands the head is bound by
+// those reads, not by the matrix cores); fp32 is level to 0.6 ms faster.  WN_NO_FUSED_SCORE=1 / =0 (with WN_TESTING=1) pins the unfused / the fused path.
+static bool wn_fused_score_enabled(wn_handle* h, bool bf16) {
+    const char* off = wn_dev_env("WN_NO_FUSED_SCORE");
+    if (off) h->dev_overrides = 1;   // (read per call, not at wn_create: the handle reports it from the first scoring call on)
+    if (off && (off[0] == '1' || off[0] == '0')) return off[0] == '0';
+    return !bf16;
+}
+
+static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, const WnScoreOut* score, void* hip_stream,
+                          const char* who) {
+    if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
+    if (N < 1 || out_len < 1) return wn_fail(WN_E_BADARG, "%s: N and output_length must be >= 1", who);
+    const WnPlan& pl = h->plan;
+    const WnWeights& wt = h->w;
+    const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
+    if (!wt.fw_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2 and channel counts that are multiples of 32", who);
+    if ((long long)N * L >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "%s: N*L must stay below 2^31 rows", who);
+    { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
+    WnFwdGeom geo;
+    { int rc = wn_forward_geometry(h, L, out_len, geo, who); if (rc) return rc; }
+    const long long Mrows = (long long)N * out_len;
+    const bool score_fused = score && C == 256 && S % 32 == 0 && E % WN_SCORE_EC == 0 && wn_fused_score_enabled(h, h->fw_bf16 && h->w.fwb_ok);
+    size_t n_part = 0;
+    if (score) {   // one fp64 triple per workgroup of the kernel that scores
+        n_part = (size_t)(score_fused ? (Mrows + WN_SCORE_TM - 1) / WN_SCORE_TM : (Mrows + WN_SCORE_ROWS_PER_WG - 1) / WN_SCORE_ROWS_PER_WG);
+        if (h->score_parts < n_part) {
+            if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+            (void)hipDeviceSynchronize();
+            if (!rt_grow(h->d_score_part, h->score_parts, n_part, 3)) return wn_fail(WN_E_NOMEM, "%s: %lld partial sums", who, (long long)n_part);
+        }
+    }
+    const std::vector<long long>& need = geo.rows;
+    const size_t x_fl = (size_t)N * L * R, z_fl = (size_t)N * need[1 < NL ? 1 : NL] * D > (size_t)N * need[NL] * D ? (size_t)N * need[1 < NL ? 1 : NL] * D : (size_t)N * need[NL] * D;
+    // The skip sum over layers is accumulated G layers at a time: the gate epilogue also drops z (last output_length rows)
+    // into column block (l mod G) of ZG [N*out_len][G*D], and one GEMM with K = G*D adds the group to SKIP -- instead of a
+    // read-modify-write of the whole SKIP matrix per layer (1.4 GB per layer at config 5).
+    const int G = pl.layers < NL ? pl.layers : NL;
+    const size_t skip_fl = (size_t)N * out_len * S, e_fl = (size_t)N * out_len * E, zg_fl = (size_t)N * out_len * G * D;
+    // bf16 operands at the 128 / 128 shape: a layer is ONE launch (wn_fwd_layer_bf16: z goes from the gate epilogue to the residual product
+    // through LDS and is never stored), its matrix operand reads of x take a bf16 shadow written next to x (WnGemmArgs::c_h), z on the skip
+    // rows (zg) is stored as bf16.  Same roundings as the two-launch form (every value is rounded to bf16 once, where it becomes an operand).
+    const bool fuse = h->fw_bf16 && h->w.fwb_ok && R == 128 && D == 128 && wn_fused_layer_enabled();
+    const size_t xh_fl = fuse ? ((x_fl + 1) / 2 + 63) / 64 * 64 : 0;
+    const size_t lg_fl = (score && !score_fused) ? (size_t)Mrows * C : 0;   // (unfused scoring: the logits live in the workspace)
+    const size_t total = 2 * x_fl + z_fl + skip_fl + e_fl + zg_fl + 2 * xh_fl + lg_fl;
+    if (h->ws_floats < total) {
+        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+        if (!rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
+    }
+    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl; float* skip = z + z_fl; float* ev = skip + skip_fl;
+    float* zg = ev + e_fl;
+    unsigned short* xha = fuse ? reinterpret_cast<unsigned short*>(zg + zg_fl) : nullptr;
+    unsigned short* xhb = fuse ? reinterpret_cast<unsigned short*>(zg + zg_fl + xh_fl) : nullptr;
+    if (lg_fl) logits = zg + zg_fl + 2 * xh_fl;
+    hipStream_t st = (hipStream_t)hip_stream;
+    {
+        const long long rows = N * L;
+        const long long work = rows * (R / 4);
+        hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, indices, h->w.d_start_t,
+                           pl.has_bias ? h->w.d_start_b : nullptr, xa, rows, R, xha);
+    }
+    const bool bf16 = h->fw_bf16 && wt.fwb_ok;
+    const unsigned short* fwb = wt.d_fwb;
+    auto launch = [&](int epi, const WnGemmArgs& a, size_t bank) { wn_launch_nn(st, epi, a, bf16 ? fwb + bank : nullptr); };   // bank: the product's B in the bf16 bank
+    const float* fw = wt.d_fw;
+    const wn_train_layout& o = wt.fw;
+    const WnBf16Layout& ob = wt.fwb;
+    float* xin = xa; float* xout = xb;
+    unsigned short* xhin = xha; unsigned short* xhout = xhb;
+    for (int l = 0; l < NL; ++l) {
+        const long long d = h->dil[l], rows = need[l + 1], t0 = L - rows;
+        const int gi = l % G;
+        // z = gate([x(t-d) | x(t)] . Wfg^T)
+        const float* xop = fuse ? reinterpret_cast<const float*>(xhin) : xin;   // (fuse: the bf16 shadow, the row maps count bf16 elements)
+        WnGemmArgs a = wn_layer_fg(pl, o, fw, l, wn_rows(xop, L, R, t0), d, wn_rows(z, rows, D), N, rows);
+        a.a_skip_lo[0] = (int)geo.zlo[l];   // (short clips: the reference's left zero padding stands in for x(t - d) there)
+        a.a_bf16 = fuse ? 1 : 0;
+        a.c_bf16 = fuse ? 1 : 0;   // (fuse: z and zg hold bf16)
+        a.c2 = wn_rows(fuse ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(zg) + (size_t)gi * D) : zg + (size_t)gi * D, out_len, (long long)G * D);
+        a.c2_first_row = (int)(rows - out_len);
+        WnGemmArgs ar = {};  // x' = z . Wres^T + x(t)   (the last layer's residual output is never consumed, also upstream)
+        if (l < NL - 1) {
+            ar = wn_layer_res(pl, o, fw, l, wn_rows(z, rows, D), wn_rows(xin, L, R, t0), wn_rows(xout, L, R, t0), N, rows);
+            ar.a_bf16 = fuse ? 1 : 0;
+            ar.c_h = fuse ? xhout : nullptr;
+        }
+        bool fused = false;
+        if (fuse && l < NL - 1) {
+            WnGemmArgs af = a;
+            af.c.base = nullptr;   // z itself is not stored: nothing reads it again
+            fused = wn_launch_layer(st, af, fwb + ob.fg + (size_t)l * 2 * D * 2 * R, ar, fwb + ob.res + (size_t)l * R * D);
+        }
+        if (!fused) {
+            launch(WN_EPI_GATE, a, ob.fg + (size_t)l * 2 * D * 2 * R);
+            if (l < NL - 1) launch(WN_EPI_PLAIN, ar, ob.res + (size_t)l * R * D);
+        }
+        if (gi == G - 1 || l == NL - 1) {  // skip (+)= ZG . [Wskip of the group's layers]^T   (K = layers_in_group * D)
+            const int first = l - gi, cnt = gi + 1;
+            WnGemmArgs ak = wn_skip_group(pl, o, fw, first, cnt, wn_rows(zg, out_len, (long long)G * D), fw + o.bskip_total, skip, N, out_len);
+            ak.a_bf16 = fuse ? 1 : 0;
+            launch(WN_EPI_PLAIN, ak, ob.skip + (size_t)(first / G) * S * G * D);
+        }
+        float* t = xin; xin = xout; xout = t;
+        unsigned short* th = xhin; xhin = xhout; xhout = th;
+    }
+    if (score_fused) {   // head and row statistics in one kernel: neither ev nor the logits reach HBM
+        WnScoreArgs sa = {};
+        sa.skip = skip; sa.M = Mrows; sa.S = S; sa.E = E;
+        sa.w1t = fw + o.w1; sa.w2t = fw + o.w2; sa.b1 = fw + o.b1; sa.b2 = fw + o.b2;
+        if (bf16) { sa.w1h = fwb + ob.w1; sa.w2h = fwb + ob.w2; }
+        sa.targets = reinterpret_cast<const long long*>(score->targets); sa.row_nll = score->row_nll; sa.row_pred = score->row_pred; sa.part = h->d_score_part;
+        if (bf16) hipLaunchKernelGGL(wn_score_head_bf16, dim3((unsigned)n_part), dim3(256), 0, st, sa);
+        else hipLaunchKernelGGL(wn_score_head, dim3((unsigned)n_part), dim3(256), 0, st, sa);
+    } else {
+        const WnHeadArgs hd = wn_head(pl, o, fw, skip, ev, logits, N, out_len);
+        launch(WN_EPI_PLAIN, hd.e, ob.w1);
+        launch(WN_EPI_PLAIN, hd.logits, ob.w2);
+        if (score)
+            hipLaunchKernelGGL(wn_score_rows, dim3((unsigned)n_part), dim3(256), 0, st, logits, C, reinterpret_cast<const long long*>(score->targets), Mrows,
+                               score->row_nll, score->row_pred, h->d_score_part);
+    }
+    if (score) hipLaunchKernelGGL(wn_score_reduce, dim3(1), dim3(1024), 0, st, h->d_score_part, (long long)n_part, score->sums);
+    return rt_hip(hipGetLastError(), score ? "wn_score launches" : "wn_forward launches");
+}
+
+extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !indices || !logits) return wn_fail(WN_E_BADARG, "wn_forward: NULL argument");
+    if (!h->chains.empty()) return wn_forward(h->chains[0], indices, N, L, out_len, logits, hip_stream);  // every chain holds the weights
+    return wn_forward_run(h, indices, N, L, out_len, logits, nullptr, hip_stream, "wn_forward");
+}
+
+// Teacher-forced scoring (include/wn_abi.h): wn_forward's stack up to the finished skip rows, then the head and the row statistics (wn_score.h).
+extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64_t N, int64_t L, int64_t out_len, float* row_nll, int32_t* row_pred,
+                        double* sums, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !indices || !targets || !sums) return wn_fail(WN_E_BADARG, "wn_score: NULL argument");
+    if (wn_dev_env("WN_NO_FUSED_SCORE")) h->dev_overrides = 1;   // (the front handle of a job of several chains reports it too)
+    if (!h->chains.empty()) return wn_score(h->chains[0], indices, targets, N, L, out_len, row_nll, row_pred, sums, hip_stream);  // every chain holds the weights
+    const WnScoreOut so{targets, row_nll, row_pred, sums};
+    return wn_forward_run(h, indices, N, L, out_len, nullptr, &so, hip_stream, "wn_score");
+}
+
+// Batched (teacher-forced) priming: the n_prime = n_given - 1 priming evaluations of generate_fast (wavenet_model.py:259-269)
+// as GEMMs over all given positions at once instead of one chain pass per sample: the layer
+// inputs of the whole window are computed with the forward kernels (no skip / head work -- the reference discards those
+// outputs) and the newest d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
+// (queue time 0); activations before the stream start are zero at every layer, like DilatedQueue.reset().
+extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !first_samples) return wn_fail(WN_E_BADARG, "wn_prime: NULL argument");
+    if (!h->chains.empty()) {
+        if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
+        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+        for (size_t i = 0; i < h->chains.size(); ++i) {
+            int rc = wn_prime(h->chains[i], first_samples + (size_t)h->chain_first[i] * (size_t)row_stride, n_prime, row_stride, hip_stream);
+            if (rc) return rc;
+        }
+        h->t_base = h->chains[0]->t_base;
+        return WN_OK;
+    }
+    if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_prime: wn_load_weights has not been called");
+    if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
+    if (n_prime == 0) return WN_OK;
+    const WnPlan& pl = h->plan;
+    const int R = pl.R, D = pl.D, NL = pl.NL, ns = pl.n_streams;
+    if (!h->w.fw_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: needs kernel_size 2 and channel counts that are multiples of 32");
+    if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+    if (h->t_base != 0) return wn_fail(WN_E_STATE, "wn_prime: queues must be freshly reset (queue time is %lld)", h->t_base);
+    { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
+    const long long n = n_prime;
+    if ((long long)ns * n >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: too many rows");
+    // q[i] = trailing positions of layer i's input that are needed (its own queue: d+1, and what the layers above need)
+    std::vector<long long> q(NL + 1, 0);
+    for (int l = NL - 1; l >= 0; --l) {
+        const long long d = h->dil[l];
+        long long v = q[l + 1] > 0 ? q[l + 1] + d : 0;
+        if (v < d + 1) v = d + 1;
+        q[l] = v < n ? v : n;
+    }
+    long long max_d = 1;
+    for (int l = 0; l < NL; ++l) max_d = h->dil[l] > max_d ? h->dil[l] : max_d;
+    const long long Lp = max_d, Lt = Lp + n;  // every stream's activation rows are preceded by Lp rows of zeros (t < 0)
+    const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
+    const size_t total = 2 * x_fl + z_fl;
+    if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "wn_prime: workspace of %.1f MB", total * 4e-6);
+    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl;
+    hipStream_t st = (hipStream_t)hip_stream;
+    int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * x_fl * 4, st), "hipMemsetAsync(prime workspace)");
+    if (rc) return rc;
+    // x0 = start_conv column gather over all given positions; rows of stream s start at xa + s*Lt*R + Lp*R
+    for (int s = 0; s < ns; ++s) {
+        const long long work = n * (R / 4);
+        hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, first_samples + (size_t)s * row_stride,
+                           h->w.d_start_t, pl.has_bias ? h->w.d_start_b : nullptr, xa + ((size_t)s * Lt + Lp) * R, n, R);
+    }
+    const float* fw = h->w.d_fw;
+    float* xin = xa; float* xout = xb;
+    for (int l = 0; l < NL; ++l) {
+        const long long d = h->dil[l];
+        const int ML = (int)d + 1;
+        {   // queue of layer l <- newest min(d+1, n) columns of its input
+            const int count = (int)(ML < n ? ML : n);
+            const long long work = (long long)ns * count * (R / 4);
+            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, Lt * R,
+                               h->d_rings + h->ring_off[l], R, ML, ns, pl.P, n, count);
+        }
+        const long long rows = q[l + 1];
+        if (l == NL - 1 || rows <= 0) break;
+        const long long t0 = n - rows;
+        const WnRowMap zmap = wn_rows(z, rows, D), x = WnRowMap{xin + Lp * R, Lt * R, R, t0};   // (x: t - d may be negative: those rows are the zero prefix)
+        wn_launch_nn(st, WN_EPI_GATE, wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, ns, rows));
+        wn_launch_nn(st, WN_EPI_PLAIN, wn_layer_res(pl, h->w.fw, fw, l, zmap, x, WnRowMap{xout + Lp * R, Lt * R, R, t0}, ns, rows));
+        float* t = xin; xin = xout; xout = t;
+    }
+    rc = rt_hip(hipGetLastError(), "wn_prime launches");
+    if (rc) return rc;
+    h->t_base = n;
+    return WN_OK;
+}
+
+// Operand precision of wn_forward's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),
+// 1 = bf16 operands with fp32 accumulation (the residual stream and all sums stay fp32).  wn_prime always runs fp32.
+extern "C" int wn_set_forward_precision(wn_handle* h, int32_t bf16) {
+    g_err[0] = 0;
+    if (!h) return wn_fail(WN_E_BADARG, "wn_set_forward_precision: NULL handle");
+    if (!h->chains.empty()) return wn_set_forward_precision(h->chains[0], bf16);
+    if (bf16 && !h->have_weights) return wn_fail(WN_E_STATE, "wn_set_forward_precision: load the weights first");
+    if (bf16 && !h->w.fwb_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 needs R, D, S, E to be multiples of 64");
+    h->fw_bf16 = bf16 ? 1 : 0;
+    return WN_OK;
+}

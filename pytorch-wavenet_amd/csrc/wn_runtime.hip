@@ -12,6 +12,7 @@
 #include <vector>
 
 #include "../../include/wn_abi.h"
+#include "wn_banks.h"
 #include "wn_kernel.h"
 #include "wn_kernel_v3.h"
 #include "wn_stacked_table.h"
@@ -33,6 +34,7 @@ static const char* wn_dev_env(const char* name) {
     if (v) g_dev_env_used = 1;
     return v;
 }
+static bool wn_dev_flag(const char* name) { const char* v = wn_dev_env(name); return v && v[0] == '1'; }   // the on / off switches ("1" = on)
 
 static int wn_fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -40,67 +42,6 @@ static int wn_fail(int code, const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
     return code;
-}
-
-// One "NN" product C = A . B^T of wn_forward.h.  bn != NULL: bf16 operands (B given as [N][K] bf16 -- or as two [N][ldb] halves
-// bn / bn1 --, A rounded while staged), fp32 accumulation; else fp32 operands.  Products with N % 256 == 0 take the 128 x 256 tile.
-static void wn_launch_nn(hipStream_t st, int epi, const WnGemmArgs& a, const unsigned short* bn = nullptr, const unsigned short* bn1 = nullptr, int ldb = 0) {
-    const bool wide = bn && a.N % 256 == 0 && epi != WN_EPI_GATE_BWD;
-    const unsigned mt = (unsigned)((a.M + 127) / 128), nt = (unsigned)(wide ? a.N / 256 : (a.N + 127) / 128);
-    const dim3 grid(mt * nt);   // 1-D (M / 128 can exceed a grid's y limit): row tiles fastest, then column tiles
-    if (bn) {
-        WnGemmArgsBf16 b;
-        b.g = a; b.bn = bn; b.bn1 = bn1; b.ldb = ldb;
-        if (wide) {
-            if (epi == WN_EPI_GATE && a.a_bf16) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE, 8, true>), grid, dim3(512), 0, st, b);   // (bf16-stored A: the shadow of x)
-            else if (epi == WN_EPI_GATE) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE, 8>), grid, dim3(512), 0, st, b);
-            else if (a.a_bf16) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 8, true>), grid, dim3(512), 0, st, b);   // (bf16-stored A: the grouped skip product)
-            else hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 8>), grid, dim3(512), 0, st, b);
-        } else {
-            if (epi == WN_EPI_GATE) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE, 4>), grid, dim3(256), 0, st, b);   // (never with a bf16-stored A: wn_train_layout_ws)
-            else if (epi == WN_EPI_GATE_BWD) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_GATE_BWD, 4>), grid, dim3(256), 0, st, b);
-            else if (a.a_bf16) hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 4, true>), grid, dim3(256), 0, st, b);   // (bf16-stored A: the residual and dx products)
-            else hipLaunchKernelGGL((wn_fwd_gemm_bf16<WN_EPI_PLAIN, 4>), grid, dim3(256), 0, st, b);
-        }
-        return;
-    }
-    if (epi == WN_EPI_GATE) hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_GATE>, grid, dim3(256), 0, st, a);
-    else if (epi == WN_EPI_GATE_BWD) hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_GATE_BWD>, grid, dim3(256), 0, st, a);
-    else hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a);
-}
-
-// One forward layer in one launch (wn_fwd_layer_bf16): `a` = the filter/gate product's arguments (bf16 operands, c_bf16 = 1; a.c.base may be
-// NULL: z is not stored), `r` = the residual product's (its bias, cin, c, c_h are used).  Returns false when the shape is not the fused
-// kernel's (the caller launches the two products).  WN_NO_FUSED_LAYER=1 (with WN_TESTING=1) switches it off for A/B runs.
-static bool wn_fused_layer_enabled() { const char* off = wn_dev_env("WN_NO_FUSED_LAYER"); return !(off && off[0] == '1'); }
-static bool wn_launch_layer(hipStream_t st, const WnGemmArgs& a, const unsigned short* bn_fg, const WnGemmArgs& r, const unsigned short* bn_res) {
-    if (!bn_fg || !bn_res || !a.a_bf16 || a.N != 256 || r.N != 128 || r.K != 128 || a.K % 32 != 0 || a.k_split % 32 != 0 || !a.c_bf16 || a.relu_a || r.relu_a || r.relu_c ||
-        r.mask || r.cin_skip_lo || r.M != a.M || r.rows_per_batch != a.rows_per_batch) return false;   // (x from its bf16 shadow, z kept as bf16, the same rows in both products)
-    if (!wn_fused_layer_enabled()) return false;
-    WnGemmArgsBf16 b;
-    b.g = a; b.bn = bn_fg; b.bn1 = nullptr; b.ldb = 0;
-    WnLayerArgs la;
-    la.bn = bn_res; la.bias = r.bias; la.cin = r.cin; la.c = r.c; la.c_h = r.c_h; la.N = r.N;
-    const dim3 grid(wn_layer_grid(a.M));
-    hipLaunchKernelGGL(wn_fwd_layer_bf16, grid, dim3(512), 0, st, b, la);
-    return true;
-}
-
-// The backward's fused pair (wn_bwd_layer_bf16): `a` = the dx product of layer l (bf16-stored A in two views, weight banks bn / bn1 with row
-// length ldb), `b` = the gate-derivative product of layer l - 1, whose A operand is `a`'s output.  Returns false when the shapes are not
-// the fused kernel's (the caller launches the two products).
-static bool wn_launch_bwd_layer(hipStream_t st, const WnGemmArgs& a, const unsigned short* bn, const unsigned short* bn1, int ldb,
-                                const WnGemmArgs& b, const unsigned short* bn_res) {
-    if (!bn || !bn_res || !a.a_bf16 || a.N != 128 || a.K % 32 != 0 || a.bias || a.relu_a || a.relu_c || a.mask || a.c_h || a.c_bf16 ||
-        b.N != 128 || b.K != 128 || !b.c_bf16 || !b.gate_packed || b.M != a.M || b.rows_per_batch != a.rows_per_batch) return false;
-    if (b.a0.base != a.c.base || b.a0.t0 != a.c.t0 || b.a0.batch_stride != a.c.batch_stride || b.a0.row_stride != a.c.row_stride) return false;   // (the same rows)
-    if (!wn_fused_layer_enabled()) return false;
-    { const char* off = wn_dev_env("WN_NO_FUSED_BWD"); if (off && off[0] == '1') return false; }   // (A/B: the forward's fused layer alone)
-    WnGemmArgsBf16 x, y;
-    x.g = a; x.bn = bn; x.bn1 = bn1; x.ldb = ldb;
-    y.g = b; y.bn = bn_res; y.bn1 = nullptr; y.ldb = 0;
-    hipLaunchKernelGGL(wn_bwd_layer_bf16, dim3(wn_layer_grid(a.M)), dim3(512), 0, st, x, y);
-    return true;
 }
 
 // ------------------------------------------------------------------------------------------------ runtime shim
@@ -117,6 +58,12 @@ static void* rt_malloc(size_t n) {
     return p;
 }
 static void rt_free(void* p) { if (p) (void)hipFree(p); }
+template <class T> static bool rt_grow(T*& p, size_t& have, size_t need, size_t per = 1) {   // a buffer of `need` units that only ever grows (old contents dropped)
+    rt_free(p);
+    p = (T*)rt_malloc(need * per * sizeof(T));
+    have = p ? need : 0;
+    return p != nullptr;
+}
 static int rt_h2d(void* d, const void* h, size_t n) { return rt_hip(hipMemcpy(d, h, n, hipMemcpyHostToDevice), "hipMemcpy H2D"); }
 static int rt_d2h(void* h, const void* d, size_t n) { return rt_hip(hipMemcpy(h, d, n, hipMemcpyDeviceToHost), "hipMemcpy D2H"); }
 static int rt_memset_async(void* d, int v, size_t n, void* stream) {
@@ -177,7 +124,7 @@ template <class SH>
 static void wn_pack_v2(const WnPlan& pl, const WnHostWeights& w, std::vector<float>& out) {
     constexpr int R = SH::R, DC = SH::DC, S = SH::S, EC = SH::EC, T1 = SH::T1, K1 = SH::K1, T2 = SH::T2, K2 = SH::K2, RS = SH::RS,
                   T3 = SH::T3, K3 = SH::K3;
-    const int D = pl.D, E = pl.E, C = pl.C, P = pl.P, NL = pl.NL;
+    const int D = pl.D, E = pl.E, P = pl.P, NL = pl.NL;
     out.assign((size_t)NL * P * SH::NWL * 256 + (size_t)pl.PA * SH::NWH * 256, 0.f);
     for (int l = 0; l < NL; ++l)
         for (int c = 0; c < P; ++c) {
@@ -218,7 +165,6 @@ static void wn_pack_v2(const WnPlan& pl, const WnHostWeights& w, std::vector<flo
             img[(size_t)(j++) * 256 + tid] = h == 0 ? w.end2_b[tid] : 0.f;
         }
     }
-    (void)C;
 }
 
 template <int R, int DC, int S, int EC, int PM, int SK = 0>
@@ -308,8 +254,7 @@ static bool wn_v3_applicable(const wn_config* cfg, int n_cu, int* out_vi, int* o
     const char* force = wn_dev_env("WN_KERNEL");  // "generic" pins the LDS-resident kernel (A/B runs, tests)
     if (force && !strcmp(force, "generic")) return false;
     if (cfg->n_streams < WN_V3_MIN_STREAMS) return false;
-    WnPlan pl;
-    memset(&pl, 0, sizeof(pl));
+    WnPlan pl = {};
     pl.layers = cfg->layers; pl.blocks = cfg->blocks; pl.NL = cfg->layers * cfg->blocks;
     pl.R = cfg->residual_channels; pl.D = cfg->dilation_channels; pl.S = cfg->skip_channels; pl.E = cfg->end_channels;
     pl.C = cfg->classes; pl.k = cfg->kernel_size; pl.n_streams = cfg->n_streams;
@@ -363,23 +308,31 @@ struct WnTrainLay {
     size_t skip, ev, dzg, bskip_total, res_o, skip_o, w1_o, w2_o, fgb0, fgb1, dskip, de, dz, dfg, dfg2, dxa, dxb, colsum_tmp, idx, total;
     size_t dskip_h;                       // bf16 step: the bf16 shadow of dskip (a matrix operand twice per skip block: the dzg product and the skip weight gradient); offset in floats
     size_t bw, bt_fg, bt_res, bt_skip, bt_w1, bt_w2;  // bf16 operand banks (offsets in floats)
-    int G, nblk;  // layers per skip block, blocks
+    int NL, G, nblk;  // layers; layers per skip block, blocks
+    int cnt(int b) const { const int first = b * G; return NL - first < G ? NL - first : G; }   // layers of skip block b (its first: b * G)
     bool bf16;  // the saved forward ran with bf16 operands: so does its backward
 };
 struct WnDetWs { float* buf = nullptr; size_t floats = 0; };
+// What the rounds of a multi-round handle share (wn_load_weights): the chain's weight images, start_conv and the GEMM-ready banks of wn_banks.h
+struct WnWeights {
+    float *d_blobs = nullptr, *d_start_t = nullptr, *d_start_b = nullptr;
+    // batched forward (wn_forward) and training: the fp32 bank, and its bf16 copy [N][K] row-major
+    float* d_fw = nullptr; size_t fw_floats = 0; bool fw_ok = false; wn_train_layout fw = {};
+    unsigned short* d_fwb = nullptr; size_t fwb_elems = 0; bool fwb_ok = false; WnBf16Layout fwb;
+};
 struct wn_handle {
-    wn_config cfg;
-    WnPlan plan;
-    bool have_weights;
-    bool pending;
-    bool broken;   // rounds front: a launch failed after some rounds had started; the rounds' queue times diverged -> wn_reset
-    void* last_stream;
-    long long t_base;  // evaluations since the last reset
-    int n_cu, wall_khz;
-    int variant;   // 1 = generic LDS-resident kernel, 3 = wave-specialised register-resident kernel (2: the 256-thread kernels of rounds 1-2, removed)
-    int v2_index;  // row of wn_v2_table()
-    int lds_bytes;
-    int v3_mode;   // variant 3: streams per pipeline item (wn_v3_mode)
+    wn_config cfg = {};
+    WnPlan plan = {};
+    bool have_weights = false;
+    bool pending = false;
+    bool broken = false;   // rounds front: a launch failed after some rounds had started; the rounds' queue times diverged -> wn_reset
+    void* last_stream = nullptr;
+    long long t_base = 0;  // evaluations since the last reset
+    int n_cu = 0, wall_khz = 0;
+    int variant = 1;   // 1 = generic LDS-resident kernel, 3 = wave-specialised register-resident kernel (2: the 256-thread kernels of rounds 1-2, removed), 4 = stacked kernel
+    int v2_index = -1; // row of wn_v2_table() / wn_v4_table()
+    int lds_bytes = 0;
+    int v3_mode = 0;    // variant 3: streams per pipeline item (wn_v3_mode)
     int v3_slots = 0;   // variant 3: skip-lane slots re-used per in-flight item (wn_v3_slots_for; 0 = one slot per stream)
     int dev_overrides = 0;  // a development override was in effect when this handle was planned (wn_dev_env)
     // Zero padding: a channel shape the wave-specialised kernel is not compiled for runs as the next instantiated shape that holds it,
@@ -392,33 +345,28 @@ struct wn_handle {
     // every call to its member handles (`chains`, one complete engine per round).
     std::vector<wn_handle*> chains;
     std::vector<int> chain_first;  // first stream of round i (chain_first[n] = n_streams)
-    bool rounds;
+    bool rounds = false;
     bool shares_weights = false;   // member i > 0 of a rounds front: its weight images, start_conv^T and GEMM banks ARE member 0's (immutable during a
                                    // job, identical for every member -- the image layout depends on the channel shape, not on the stream count): not freed here
     // owned device allocations
-    float *d_blobs, *d_start_t, *d_start_b, *d_rings;
-    int32_t *d_dil, *d_wg_map;
-    int64_t* d_ring_off;
-    wn_u64* d_gran;
-    uint32_t* d_status;
-    size_t blob_floats, ring_floats, gran_count;
-    long long* d_prof;
-    // batched forward (wn_forward): GEMM-ready weight banks and a workspace that grows on demand
-    float* d_fw; size_t fw_floats; bool fw_ok;
-    size_t fw_off_fg, fw_off_bfg, fw_off_res, fw_off_bres, fw_off_skip, fw_off_bskip, fw_off_bskip_total, fw_off_w1, fw_off_b1, fw_off_w2, fw_off_b2;
-    size_t fw_off_start_t, fw_off_start_b;  // training only: wn_forward / wn_prime read d_start_t / d_start_b
-    float* d_ws; size_t ws_floats;
-    unsigned short* d_fwb; size_t fwb_elems; bool fwb_ok; int fw_bf16;  // bf16 copies of the forward banks, [N][K] row-major
-    size_t fwb_off_fg, fwb_off_res, fwb_off_skip, fwb_off_w1, fwb_off_w2;
-    int prof_items;      // stamps requested for the next job (0 = off)
-    int prof_recorded;   // stamps held in d_prof
+    WnWeights w;   // (owned unless shares_weights)
+    float* d_rings = nullptr;
+    int32_t *d_dil = nullptr, *d_wg_map = nullptr;
+    int64_t* d_ring_off = nullptr;
+    wn_u64* d_gran = nullptr;
+    uint32_t* d_status = nullptr;
+    size_t blob_floats = 0, ring_floats = 0, gran_count = 0;
+    long long* d_prof = nullptr;
+    float* d_ws = nullptr; size_t ws_floats = 0;   // batched forward (wn_forward): a workspace that grows on demand
+    int fw_bf16 = 0;                               //   and its operand precision (wn_set_forward_precision)
+    int prof_items = 0;      // stamps requested for the next job (0 = off)
+    int prof_recorded = 0;   // stamps held in d_prof
     std::vector<int64_t> ring_off;
     std::vector<int32_t> dil;
-    float* d_tws; size_t tws_floats;  // training workspace (saved activations + backward temporaries)
+    float* d_tws = nullptr; size_t tws_floats = 0;  // training workspace (saved activations + backward temporaries)
     float* d_xent = nullptr; size_t xent_rows = 0;  // wn_train_loss: per-row losses
     double* d_score_part = nullptr; size_t score_parts = 0;  // wn_score: one {sum nll, hits, rows} triple per workgroup
-    WnTrainLay train; bool train_valid;
-    // admission of persistent jobs (wn_gate.h)
+    WnTrainLay train = {}; bool train_valid = false;
     // wn_train_backward: the weight-gradient products run on a second stream next to the activation-gradient chain (wn_train.inl)
     hipStream_t side_stream = nullptr;
     std::vector<hipEvent_t> events;
@@ -427,6 +375,7 @@ struct wn_handle {
     bool deterministic = false;
     WnDetWs det_ws[2];
     char busid[32] = "";
+    // admission of persistent jobs (wn_gate.h)
     std::shared_ptr<WnGateTicket> gate;   // the booking of the job in flight (released by the host function behind the kernel, or in wn_wait)
     int gate_shared = -1, gate_waited_ms = 0;
     int gate_need = 0;   // resident workgroups on the fullest XCD (wn_create)
@@ -434,6 +383,25 @@ struct wn_handle {
     int wg_per_cu = 0;   // workgroups of the job's kernel one CU holds (hipOccupancyMaxActiveBlocksPerMultiprocessor at wn_create)
     long long last_n_eval = 0;   // evaluations the job in flight advances the queues by (rolled back when it never started: WN_E_BUSY)
 };
+static void wn_free_weights(wn_handle* h) {   // (members i > 0 of a rounds front never free: the allocations are member 0's)
+    if (!h->shares_weights) { rt_free(h->w.d_blobs); rt_free(h->w.d_start_t); rt_free(h->w.d_start_b); rt_free(h->w.d_fw); rt_free(h->w.d_fwb); }
+}
+
+// The chain kernel a handle runs: its function (for the attribute and occupancy queries of wn_create), its workgroup size, its launch
+struct WnChainKernel { const void* fn; int threads; };
+static WnChainKernel wn_chain_kernel(const wn_handle* h) {
+    if (h->variant == 4) return WnChainKernel{wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
+    if (h->variant == 3) return WnChainKernel{wn_v2_table()[h->v2_index].fn_v3[h->v3_slots ? 2 : (h->v3_mode & 1)], WN_THREADS_V3};
+    return WnChainKernel{(const void*)wn_generate_kernel, WN_THREADS};
+}
+static void wn_chain_launch(const wn_handle* h, hipStream_t st, const WnRun& r) {
+    if (h->variant == 4)
+        wn_v4_table()[h->v2_index].launch(h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
+    else if (h->variant == 3)
+        wn_v2_table()[h->v2_index].launch_v3(h->v3_slots ? 2 : (h->v3_mode & 1), h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
+    else
+        hipLaunchKernelGGL(wn_generate_kernel, dim3(h->plan.n_blocks), dim3(WN_THREADS), (size_t)h->lds_bytes, st, h->plan, r);
+}
 
 // CUs per XCD a job of this handle needs -- the workgroups that stay resident on the fullest XCD (blocks are dispatched round-robin over
 // the XCDs; the padding blocks of the layer-aligned placement exit at once and hold nothing) -- and what an XCD has
@@ -464,7 +432,7 @@ extern "C" void wn_destroy(wn_handle* h) {
     if (h->side_stream) { (void)hipStreamSynchronize(h->side_stream); (void)hipStreamDestroy(h->side_stream); }
     for (hipEvent_t e : h->events) (void)hipEventDestroy(e);
     wn_gate_release(h->gate);
-    if (!h->shares_weights) { rt_free(h->d_blobs); rt_free(h->d_start_t); rt_free(h->d_start_b); rt_free(h->d_fw); rt_free(h->d_fwb); }
+    wn_free_weights(h);
     rt_free(h->d_rings); rt_free(h->d_dil);
     rt_free(h->d_wg_map); rt_free(h->d_ring_off); rt_free(h->d_gran); rt_free(h->d_status); rt_free(h->d_prof); rt_free(h->d_ws);
     rt_free(h->d_tws);
@@ -560,8 +528,7 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     char busid[32] = "";
     if (hipDeviceGetPCIBusId(busid, (int)sizeof(busid), cfg->device_id) != hipSuccess || !busid[0]) snprintf(busid, sizeof(busid), "dev%d", cfg->device_id);
     {   // rounds of the wave-specialised chain (see wn_handle::rounds)
-        const char* ce = wn_dev_env("WN_CHAINS");
-        const bool off = ce && ce[0] == '1';
+        const bool off = wn_dev_flag("WN_CHAINS");
         wn_config probe = *cfg;
         probe.n_streams = WN_V3_ROUND_STREAMS;
         if (!off && cfg->n_streams > WN_V3_ROUND_STREAMS && !wn_v3_applicable(cfg, n_cu, nullptr, nullptr, nullptr) &&
@@ -590,16 +557,8 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
                 f->cfg = *cfg;
                 f->plan = c0->plan;
                 f->plan.n_streams = cfg->n_streams;
-                f->have_weights = false; f->pending = false; f->last_stream = nullptr; f->t_base = 0;
                 f->n_cu = n_cu; f->wall_khz = wall_khz; f->variant = c0->variant; f->v2_index = c0->v2_index; f->lds_bytes = c0->lds_bytes;
                 f->v3_mode = c0->v3_mode; f->v3_slots = c0->v3_slots;
-                f->d_blobs = f->d_start_t = f->d_start_b = f->d_rings = nullptr;
-                f->d_dil = f->d_wg_map = nullptr; f->d_ring_off = nullptr; f->d_gran = nullptr; f->d_status = nullptr;
-                f->d_prof = nullptr; f->prof_items = 0; f->prof_recorded = 0;
-                f->d_fw = nullptr; f->fw_floats = 0; f->fw_ok = false; f->d_ws = nullptr; f->ws_floats = 0;
-                f->d_fwb = nullptr; f->fwb_elems = 0; f->fwb_ok = false; f->fw_bf16 = 0;
-                f->d_tws = nullptr; f->tws_floats = 0; f->train_valid = false;
-                f->blob_floats = f->ring_floats = f->gran_count = 0;
                 f->dil = c0->dil;
                 f->chains = cs;
                 f->chain_first = firsts;
@@ -613,25 +572,15 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
         }
     }
     wn_handle* h = new wn_handle();
-    memset(&h->plan, 0, sizeof(h->plan));
     h->cfg = *cfg;
-    h->v3_mode = 0; h->rounds = false;
     { const char* de = getenv("WN_DETERMINISTIC"); h->deterministic = de && de[0] == '1'; }
-    h->have_weights = false; h->pending = false; h->last_stream = nullptr; h->t_base = 0;
     h->n_cu = n_cu; h->wall_khz = wall_khz;
     memcpy(h->busid, busid, sizeof(busid));
-    h->d_blobs = h->d_start_t = h->d_start_b = h->d_rings = nullptr;
-    h->d_dil = h->d_wg_map = nullptr; h->d_ring_off = nullptr; h->d_gran = nullptr; h->d_status = nullptr;
-    h->d_prof = nullptr; h->prof_items = 0; h->prof_recorded = 0;
-    h->d_fw = nullptr; h->fw_floats = 0; h->fw_ok = false; h->d_ws = nullptr; h->ws_floats = 0;
-    h->d_fwb = nullptr; h->fwb_elems = 0; h->fwb_ok = false; h->fw_bf16 = 0;
-    h->d_tws = nullptr; h->tws_floats = 0; h->train_valid = false;
     WnPlan& pl = h->plan;
     pl.layers = cfg->layers; pl.blocks = cfg->blocks; pl.NL = cfg->layers * cfg->blocks;
     pl.R = cfg->residual_channels; pl.D = cfg->dilation_channels; pl.S = cfg->skip_channels; pl.E = cfg->end_channels;
     pl.C = cfg->classes; pl.k = cfg->kernel_size; pl.has_bias = cfg->bias ? 1 : 0; pl.n_streams = cfg->n_streams;
     pl.HR = 1;
-    h->variant = 1; h->v2_index = -1;
     {
         int P2 = 0, PA2 = 0;
         int vi3 = -1, vi4 = -1;
@@ -690,8 +639,7 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     pl.allow_plain = 0;
     if ((h->variant == 3 || h->variant == 4) && n_cu % 8 == 0 &&
         wn_make_wg_map_layers(h->variant == 4 ? pl.n_lw : pl.NL, pl.P, pl.PA * pl.HR, pl.n_smp, 8, n_cu / 8, wg_map, &pl.n_blocks)) {
-        const char* np = wn_dev_env("WN_NO_LOCAL_STORES");
-        pl.allow_plain = (np && np[0] == '1') ? 0 : 1;
+        pl.allow_plain = wn_dev_flag("WN_NO_LOCAL_STORES") ? 0 : 1;
     } else {
         wn_make_wg_map(pl.n_wg, 8, wg_map);
     }
@@ -720,16 +668,16 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
         h->blob_floats = n_lw * (size_t)ve.nwl * 256 + (size_t)pl.PA * ve.nwh * 256;
         pl.head_blob_off = (int64_t)n_lw * ve.nwl * 256;
     }
-    h->d_blobs = (float*)rt_malloc(h->blob_floats * 4);
-    h->d_start_t = (float*)rt_malloc((size_t)pl.C * pl.R * 4);
-    h->d_start_b = (float*)rt_malloc((size_t)pl.R * 4);
+    h->w.d_blobs = (float*)rt_malloc(h->blob_floats * 4);
+    h->w.d_start_t = (float*)rt_malloc((size_t)pl.C * pl.R * 4);
+    h->w.d_start_b = (float*)rt_malloc((size_t)pl.R * 4);
     h->d_rings = (float*)rt_malloc(h->ring_floats * 4);
     h->d_dil = (int32_t*)rt_malloc((size_t)pl.NL * 4);
     h->d_ring_off = (int64_t*)rt_malloc((size_t)pl.NL * 8);
     h->d_wg_map = (int32_t*)rt_malloc((size_t)pl.n_blocks * 4);
     h->d_gran = (wn_u64*)rt_malloc(h->gran_count * 8);
     h->d_status = (uint32_t*)rt_malloc((size_t)(8 + pl.n_wg) * 4);
-    if (!h->d_blobs || !h->d_start_t || !h->d_start_b || !h->d_rings || !h->d_dil || !h->d_ring_off || !h->d_wg_map ||
+    if (!h->w.d_blobs || !h->w.d_start_t || !h->w.d_start_b || !h->d_rings || !h->d_dil || !h->d_ring_off || !h->d_wg_map ||
         !h->d_gran || !h->d_status) {
         const double q_mb = h->ring_floats * 4e-6, g_mb = h->gran_count * 8e-6, w_mb = h->blob_floats * 4e-6;
         wn_destroy(h);
@@ -743,21 +691,18 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)(8 + pl.n_wg) * 4, nullptr);
     rc = rc ? rc : rt_sync(nullptr);
     if (rc) { wn_destroy(h); return rc; }
-    pl.blobs = h->d_blobs; pl.start_t = h->d_start_t; pl.start_b = nullptr;
+    pl.blobs = h->w.d_blobs; pl.start_t = h->w.d_start_t; pl.start_b = nullptr;
     pl.dil = h->d_dil; pl.ring_off = h->d_ring_off; pl.wg_map = h->d_wg_map; pl.rings = h->d_rings;
     pl.gx = h->d_gran; pl.gs = h->d_gran + gx_n; pl.gl = h->d_gran + gx_n + gs_n; pl.gi = h->d_gran + gx_n + gs_n + gl_n;
     pl.g0 = pl.gi + pl.n_streams;
     pl.status = h->d_status;
     pl.xcc_tab = h->d_status + 8;
-    rc = rt_hip(hipFuncSetAttribute(h->variant == 4 ? wn_v4_table()[h->v2_index].fn : h->variant == 3 ? wn_v2_table()[h->v2_index].fn_v3[h->v3_slots ? 2 : (h->v3_mode & 1)] : (const void*)wn_generate_kernel,
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes),
-                "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    const WnChainKernel ck = wn_chain_kernel(h);
+    rc = rt_hip(hipFuncSetAttribute(ck.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     if (rc) { wn_destroy(h); return rc; }
     {   // residency is a requirement, not a hope: what the hardware can keep resident of THIS kernel with THIS much LDS, against what the plan needs per XCD
-        const void* fn = h->variant == 4 ? wn_v4_table()[h->v2_index].fn : h->variant == 3 ? wn_v2_table()[h->v2_index].fn_v3[h->v3_slots ? 2 : (h->v3_mode & 1)] : (const void*)wn_generate_kernel;
-        const int threads = h->variant == 4 ? WN_THREADS_V4 : h->variant == 3 ? WN_THREADS_V3 : WN_THREADS;
         int per_cu = 0;
-        rc = rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, fn, threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+        rc = rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ck.fn, ck.threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
         if (rc) { wn_destroy(h); return rc; }
         int need = 0, cap = 0;
         wn_gate_numbers(h, &need, &cap);
@@ -781,10 +726,6 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w);
 static int wn_load_weights_padded(wn_handle* h, const wn_weight_ptrs* w) {
     const WnPlan& pl = h->plan;
     const int R = h->user_R, D = h->user_D, S = h->user_S, E = h->user_E, R2 = pl.R, D2 = pl.D, S2 = pl.S, E2 = pl.E, C = pl.C, NL = pl.NL, k = pl.k;
-    if (!w->start_w || !w->filter_w || !w->gate_w || !w->res_w || !w->skip_w || !w->end1_w || !w->end1_b || !w->end2_w || !w->end2_b)
-        return wn_fail(WN_E_BADARG, "wn_load_weights: a mandatory weight pointer is NULL");
-    if (pl.has_bias && (!w->start_b || !w->filter_b || !w->gate_b || !w->res_b || !w->skip_b))
-        return wn_fail(WN_E_BADARG, "wn_load_weights: cfg.bias=1 but a stack bias pointer is NULL");
     // dst[n][a][b] (extents A2, B2, inner run of `in` floats) <- src[n][a][b] (extents A, B)
     auto pad3 = [](const float* src, int n, int A, int B, int A2, int B2, int in) {
         std::vector<float> dst((size_t)n * A2 * B2 * in, 0.f);
@@ -811,13 +752,18 @@ static int wn_load_weights_padded(wn_handle* h, const wn_weight_ptrs* w) {
 }
 
 extern "C" int wn_load_weights(wn_handle* h, const wn_weight_ptrs* w) {
-    if (h && w && h->padded) { g_err[0] = 0; return wn_load_weights_padded(h, w); }
-    return wn_load_weights_impl(h, w);
+    g_err[0] = 0;
+    if (!h || !w) return wn_fail(WN_E_BADARG, "wn_load_weights: NULL argument");
+    if (!w->start_w || !w->filter_w || !w->gate_w || !w->res_w || !w->skip_w || !w->end1_w || !w->end1_b || !w->end2_w || !w->end2_b)
+        return wn_fail(WN_E_BADARG, "wn_load_weights: a mandatory weight pointer is NULL");
+    if (h->plan.has_bias && (!w->start_b || !w->filter_b || !w->gate_b || !w->res_b || !w->skip_b))
+        return wn_fail(WN_E_BADARG, "wn_load_weights: cfg.bias=1 but a stack bias pointer is NULL");
+    return h->padded ? wn_load_weights_padded(h, w) : wn_load_weights_impl(h, w);
 }
 
-// weights in the handle's own (possibly padded) channel shape
+// weights in the handle's own (possibly padded) channel shape; the pointers have been checked
 static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
-    if (h && !h->chains.empty()) {
+    if (!h->chains.empty()) {
         // Rounds: ONE copy of the weights.  Member 0 packs and uploads; the others point at its images and banks (round 3 uploaded the
         // weight images, start_conv^T and both GEMM banks into every member: 4 x 120 MB at cfg3 x 512 streams).
         wn_handle* c0 = h->chains[0];
@@ -828,29 +774,16 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
                 return wn_fail(WN_E_STATE, "wn_load_weights: the rounds of this handle were planned with different geometries");
             { int rc = rt_hip(hipSetDevice(c->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
             if (c->pending) { int rc = wn_wait(c); if (rc) return rc; }
-            if (!c->shares_weights) { rt_free(c->d_blobs); rt_free(c->d_start_t); rt_free(c->d_start_b); rt_free(c->d_fw); rt_free(c->d_fwb); }
+            wn_free_weights(c);
             c->shares_weights = true;
-            c->d_blobs = c0->d_blobs; c->d_start_t = c0->d_start_t; c->d_start_b = c0->d_start_b;
+            c->w = c0->w;
             c->plan.blobs = c0->plan.blobs; c->plan.start_t = c0->plan.start_t; c->plan.start_b = c0->plan.start_b;
-            c->d_fw = c0->d_fw; c->fw_floats = c0->fw_floats; c->fw_ok = c0->fw_ok;
-            c->fw_off_fg = c0->fw_off_fg; c->fw_off_bfg = c0->fw_off_bfg; c->fw_off_res = c0->fw_off_res; c->fw_off_bres = c0->fw_off_bres;
-            c->fw_off_skip = c0->fw_off_skip; c->fw_off_bskip = c0->fw_off_bskip; c->fw_off_bskip_total = c0->fw_off_bskip_total;
-            c->fw_off_w1 = c0->fw_off_w1; c->fw_off_b1 = c0->fw_off_b1; c->fw_off_w2 = c0->fw_off_w2; c->fw_off_b2 = c0->fw_off_b2;
-            c->fw_off_start_t = c0->fw_off_start_t; c->fw_off_start_b = c0->fw_off_start_b;
-            c->d_fwb = c0->d_fwb; c->fwb_elems = c0->fwb_elems; c->fwb_ok = c0->fwb_ok;
-            c->fwb_off_fg = c0->fwb_off_fg; c->fwb_off_res = c0->fwb_off_res; c->fwb_off_skip = c0->fwb_off_skip; c->fwb_off_w1 = c0->fwb_off_w1; c->fwb_off_w2 = c0->fwb_off_w2;
             c->have_weights = true;
         }
         h->have_weights = true;
         return WN_OK;
     }
-    g_err[0] = 0;
-    if (!h || !w) return wn_fail(WN_E_BADARG, "wn_load_weights: NULL argument");
-    if (!w->start_w || !w->filter_w || !w->gate_w || !w->res_w || !w->skip_w || !w->end1_w || !w->end1_b || !w->end2_w || !w->end2_b)
-        return wn_fail(WN_E_BADARG, "wn_load_weights: a mandatory weight pointer is NULL");
     const WnPlan& pl = h->plan;
-    if (pl.has_bias && (!w->start_b || !w->filter_b || !w->gate_b || !w->res_b || !w->skip_b))
-        return wn_fail(WN_E_BADARG, "wn_load_weights: cfg.bias=1 but a stack bias pointer is NULL");
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
     if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
     WnHostWeights hw = {w->start_w, w->start_b, w->filter_w, w->filter_b, w->gate_w, w->gate_b, w->res_w,
@@ -862,108 +795,38 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
         wn_pack_blobs(pl, hw, blobs);
     if (blobs.size() != h->blob_floats) return wn_fail(WN_E_STATE, "wn_load_weights: internal blob size mismatch");
     std::vector<float> st((size_t)pl.C * pl.R);
-    for (int r = 0; r < pl.R; ++r)
-        for (int c = 0; c < pl.C; ++c) st[(size_t)c * pl.R + r] = w->start_w[(size_t)r * pl.C + c];
-    int rc = rt_h2d(h->d_blobs, blobs.data(), blobs.size() * 4);
-    rc = rc ? rc : rt_h2d(h->d_start_t, st.data(), st.size() * 4);
+    wn_transpose_start(w->start_w, pl.R, pl.C, st.data());
+    WnWeights& wt = h->w;
+    int rc = rt_h2d(wt.d_blobs, blobs.data(), blobs.size() * 4);
+    rc = rc ? rc : rt_h2d(wt.d_start_t, st.data(), st.size() * 4);
     if (pl.has_bias) {
-        rc = rc ? rc : rt_h2d(h->d_start_b, w->start_b, (size_t)pl.R * 4);
-        h->plan.start_b = h->d_start_b;
+        rc = rc ? rc : rt_h2d(wt.d_start_b, w->start_b, (size_t)pl.R * 4);
+        h->plan.start_b = wt.d_start_b;
     } else {
         h->plan.start_b = nullptr;
     }
     if (rc) return rc;
-    {   // GEMM-ready banks for wn_forward: B^T [K][N] row-major per layer (see wn_forward.h)
-        const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
-        h->fw_ok = pl.k == 2 && R % 32 == 0 && D % 32 == 0 && S % 32 == 0 && E % 32 == 0 && C % 32 == 0;
-        if (h->fw_ok) {
-            size_t o = 0;
-            h->fw_off_fg = o; o += (size_t)NL * 2 * R * 2 * D;
-            h->fw_off_bfg = o; o += (size_t)NL * 2 * D;
-            h->fw_off_res = o; o += (size_t)NL * D * R;
-            h->fw_off_bres = o; o += (size_t)NL * R;
-            h->fw_off_skip = o; o += (size_t)NL * D * S;
-            h->fw_off_bskip = o; o += (size_t)NL * S;
-            h->fw_off_bskip_total = o; o += (size_t)S;
-            h->fw_off_w1 = o; o += (size_t)S * E;
-            h->fw_off_b1 = o; o += (size_t)E;
-            h->fw_off_w2 = o; o += (size_t)E * C;
-            h->fw_off_b2 = o; o += (size_t)C;
-            h->fw_off_start_t = o; o += (size_t)C * R;
-            h->fw_off_start_b = o; o += (size_t)R;
-            std::vector<float> fw(o, 0.f);
-            for (int l = 0; l < NL; ++l) {
-                float* fg = fw.data() + h->fw_off_fg + (size_t)l * 2 * R * 2 * D;
-                for (int ch = 0; ch < D; ++ch) {
-                    const int nf = 64 * (ch / 32) + (ch % 32), ng = nf + 32;  // column order [F(32) | G(32)] per 32-channel group
-                    for (int tap = 0; tap < 2; ++tap)
-                        for (int r = 0; r < R; ++r) {
-                            fg[(size_t)(tap * R + r) * 2 * D + nf] = w->filter_w[(((size_t)l * D + ch) * R + r) * 2 + tap];
-                            fg[(size_t)(tap * R + r) * 2 * D + ng] = w->gate_w[(((size_t)l * D + ch) * R + r) * 2 + tap];
-                        }
-                    if (pl.has_bias) {
-                        fw[h->fw_off_bfg + (size_t)l * 2 * D + nf] = w->filter_b[(size_t)l * D + ch];
-                        fw[h->fw_off_bfg + (size_t)l * 2 * D + ng] = w->gate_b[(size_t)l * D + ch];
-                    }
-                }
-                for (int dch = 0; dch < D; ++dch) {
-                    for (int r = 0; r < R; ++r) fw[h->fw_off_res + ((size_t)l * D + dch) * R + r] = w->res_w[((size_t)l * R + r) * D + dch];
-                    for (int sc = 0; sc < S; ++sc) fw[h->fw_off_skip + ((size_t)l * D + dch) * S + sc] = w->skip_w[((size_t)l * S + sc) * D + dch];
-                }
-                if (pl.has_bias) {
-                    for (int r = 0; r < R; ++r) fw[h->fw_off_bres + (size_t)l * R + r] = w->res_b[(size_t)l * R + r];
-                    for (int sc = 0; sc < S; ++sc) {
-                        fw[h->fw_off_bskip + (size_t)l * S + sc] = w->skip_b[(size_t)l * S + sc];
-                        fw[h->fw_off_bskip_total + sc] += w->skip_b[(size_t)l * S + sc];  // the grouped skip GEMM adds all biases once
-                    }
-                }
-            }
-            for (int sc = 0; sc < S; ++sc)
-                for (int e = 0; e < E; ++e) fw[h->fw_off_w1 + (size_t)sc * E + e] = w->end1_w[(size_t)e * S + sc];
-            for (int e = 0; e < E; ++e) fw[h->fw_off_b1 + e] = w->end1_b[e];
-            for (int e = 0; e < E; ++e)
-                for (int c = 0; c < C; ++c) fw[h->fw_off_w2 + (size_t)e * C + c] = w->end2_w[(size_t)c * E + e];
-            for (int c = 0; c < C; ++c) fw[h->fw_off_b2 + c] = w->end2_b[c];
-            memcpy(fw.data() + h->fw_off_start_t, st.data(), st.size() * 4);
-            if (pl.has_bias) memcpy(fw.data() + h->fw_off_start_b, w->start_b, (size_t)R * 4);
-            if (h->fw_floats != o) { rt_free(h->d_fw); h->d_fw = (float*)rt_malloc(o * 4); h->fw_floats = o; }
-            if (!h->d_fw) return wn_fail(WN_E_NOMEM, "wn_load_weights: forward weight banks (%.1f MB)", o * 4e-6);
-            rc = rt_h2d(h->d_fw, fw.data(), o * 4);
+    // GEMM-ready banks for wn_forward and the training step (wn_banks.h)
+    wt.fw_ok = wn_bank_ok(pl);
+    if (wt.fw_ok) {
+        wt.fw = wn_bank_layout(pl);
+        const std::vector<float> fw = wn_pack_bank(wt.fw, pl, w);
+        const size_t o = fw.size();
+        if (wt.fw_floats != o) { rt_free(wt.d_fw); wt.d_fw = (float*)rt_malloc(o * 4); wt.fw_floats = o; }
+        if (!wt.d_fw) return wn_fail(WN_E_NOMEM, "wn_load_weights: forward weight banks (%.1f MB)", o * 4e-6);
+        rc = rt_h2d(wt.d_fw, fw.data(), o * 4);
+        if (rc) return rc;
+        // bf16 copies for wn_set_forward_precision(1)
+        const WnBf16Layout fwb = wn_bank_layout_bf16(pl);
+        wt.fwb_ok = fwb.ok;
+        if (fwb.ok) {
+            wt.fwb = fwb;
+            const std::vector<unsigned short> wb = wn_pack_bank_bf16(fwb, wt.fw, pl, fw, w);
+            const size_t ob = wb.size();
+            if (wt.fwb_elems != ob) { rt_free(wt.d_fwb); wt.d_fwb = (unsigned short*)rt_malloc(ob * 2); wt.fwb_elems = ob; }
+            if (!wt.d_fwb) return wn_fail(WN_E_NOMEM, "wn_load_weights: bf16 forward banks");
+            rc = rt_h2d(wt.d_fwb, wb.data(), ob * 2);
             if (rc) return rc;
-            // bf16 copies for wn_set_forward_precision(1): B as [N][K] row-major (K contiguous), K a multiple of 64
-            const int G = pl.layers < NL ? pl.layers : NL;
-            h->fwb_ok = R % 64 == 0 && D % 64 == 0 && S % 64 == 0 && E % 64 == 0 && NL % G == 0;
-            if (h->fwb_ok) {
-                auto bf = [](float x) -> unsigned short {
-                    unsigned u; memcpy(&u, &x, 4);
-                    u += 0x7fffu + ((u >> 16) & 1u);
-                    return (unsigned short)(u >> 16);
-                };
-                size_t ob = 0;
-                h->fwb_off_fg = ob; ob += (size_t)NL * 2 * D * 2 * R;
-                h->fwb_off_res = ob; ob += (size_t)NL * R * D;
-                h->fwb_off_skip = ob; ob += (size_t)NL * D * S;
-                h->fwb_off_w1 = ob; ob += (size_t)E * S;
-                h->fwb_off_w2 = ob; ob += (size_t)C * E;
-                std::vector<unsigned short> wb(ob, 0);
-                for (int l = 0; l < NL; ++l) {
-                    for (int n = 0; n < 2 * D; ++n)  // packed column n of layer l = row n here; k = tap*R + ch
-                        for (int k = 0; k < 2 * R; ++k)
-                            wb[h->fwb_off_fg + ((size_t)l * 2 * D + n) * 2 * R + k] = bf(fw[h->fw_off_fg + (size_t)l * 2 * R * 2 * D + (size_t)k * 2 * D + n]);
-                    for (int r = 0; r < R; ++r)
-                        for (int dch = 0; dch < D; ++dch) wb[h->fwb_off_res + ((size_t)l * R + r) * D + dch] = bf(w->res_w[((size_t)l * R + r) * D + dch]);
-                    const int blk = l / G, li = l % G;  // skip banks are grouped per block: [block][S][G*D]
-                    for (int sc = 0; sc < S; ++sc)
-                        for (int dch = 0; dch < D; ++dch)
-                            wb[h->fwb_off_skip + ((size_t)blk * S + sc) * G * D + (size_t)li * D + dch] = bf(w->skip_w[((size_t)l * S + sc) * D + dch]);
-                }
-                for (size_t i = 0; i < (size_t)E * S; ++i) wb[h->fwb_off_w1 + i] = bf(w->end1_w[i]);
-                for (size_t i = 0; i < (size_t)C * E; ++i) wb[h->fwb_off_w2 + i] = bf(w->end2_w[i]);
-                if (h->fwb_elems != ob) { rt_free(h->d_fwb); h->d_fwb = (unsigned short*)rt_malloc(ob * 2); h->fwb_elems = ob; }
-                if (!h->d_fwb) return wn_fail(WN_E_NOMEM, "wn_load_weights: bf16 forward banks");
-                rc = rt_h2d(h->d_fwb, wb.data(), ob * 2);
-                if (rc) return rc;
-            }
         }
     }
     h->have_weights = true;
@@ -1075,10 +938,9 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
         h->prof_items = 0;
     }
     {   // admission: a persistent job only runs once ALL its workgroups are resident (wn_gate.h)
-        const char* off = wn_dev_env("WN_NO_DEVICE_GATE");
         wn_gate_release(h->gate);
         h->gate.reset();
-        if (!(off && off[0] == '1')) {
+        if (!wn_dev_flag("WN_NO_DEVICE_GATE")) {
             int need = 0, cap = 0;
             wn_gate_numbers(h, &need, &cap);
             const char* te = getenv("WN_GATE_TIMEOUT_MS");
@@ -1095,13 +957,7 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     int rc = rt_memset_async(h->d_gran, 0, h->gran_count * 8, a->hip_stream);
     rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)(8 + h->plan.n_wg) * 4, a->hip_stream);
     if (rc) { wn_gate_release(h->gate); h->gate.reset(); return rc; }
-    if (h->variant == 4)
-        wn_v4_table()[h->v2_index].launch(h->plan.n_blocks, (size_t)h->lds_bytes, (hipStream_t)a->hip_stream, h->plan, r);
-    else if (h->variant == 3)
-        wn_v2_table()[h->v2_index].launch_v3(h->v3_slots ? 2 : (h->v3_mode & 1), h->plan.n_blocks, (size_t)h->lds_bytes, (hipStream_t)a->hip_stream, h->plan, r);
-    else
-        hipLaunchKernelGGL(wn_generate_kernel, dim3(h->plan.n_blocks), dim3(WN_THREADS), (size_t)h->lds_bytes,
-                           (hipStream_t)a->hip_stream, h->plan, r);
+    wn_chain_launch(h, (hipStream_t)a->hip_stream, r);
     rc = rt_hip(hipGetLastError(), "launch wn_generate_kernel");
     if (rc) { wn_gate_release(h->gate); h->gate.reset(); return rc; }
     if (h->gate) {   // the booking goes back the moment the kernel is done (a caller that never waits must not keep the device closed)
@@ -1202,10 +1058,9 @@ extern "C" int wn_get_info(wn_handle* h, wn_info* out) {
     out->n_samplers = pl.n_smp;
     out->dev_overrides = h->dev_overrides;
     out->layers_per_workgroup = h->variant == 4 ? pl.LPW : 1;
-    if (h->variant == 4) out->n_workgroups = pl.n_wg;
     out->gate_shared = h->gate_shared; out->gate_waited_ms = h->gate_waited_ms;
     { int need = 0, cap = 0; wn_gate_numbers(h, &need, &cap); out->gate_need_per_xcd = need; }
-    out->forward_native = (h->have_weights && h->fw_ok) ? 1 : 0;
+    out->forward_native = (h->have_weights && h->w.fw_ok) ? 1 : 0;
     out->workgroups_per_cu = h->wg_per_cu; out->resident_timeout_ms = h->resident_ms; out->skip_lane_slots = h->variant == 3 ? h->v3_slots : 0;
     return WN_OK;
 }
@@ -1259,376 +1114,6 @@ extern "C" int wn_profile_read(wn_handle* h, int64_t* host_out, int64_t capacity
     return rt_d2h(host_out, h->d_prof, (size_t)n * 8);
 }
 
-// Time geometry of WaveNetModel.forward() for clips of L samples (wavenet_modules.py:10-39 `dilate`, wavenet_model.py:125-196).
-// In absolute time every layer's sequence ends at L (a kernel-size-2 dilated conv drops its input's first d positions).  Where the
-// length of a layer's input is not a multiple of its dilation the reference left-pads it with ZERO ACTIVATIONS (wavenet_modules.py:24-27),
-// so layer l's input lives on [a[l], L) preceded by pad[l] = (-(L - a[l])) mod d zeros, and its output on [a[l+1], L) with
-// a[l+1] = a[l] - pad[l] + d.  With L >= receptive_field + output_length - 1 none of the returned positions can see a pad zero (the
-// regime of rounds 1-3); shorter clips can: the tap x(t - d) then reads as zero for t - d < a[l] (row windows of the GEMMs' A views).
-//   rows[l] = trailing positions of layer l's input that are computed = min(rows[l+1] + d, L - a[l]);   zlo[l] = leading output rows of
-//   layer l whose tap is a pad zero.
-// Returns WN_E_UNSUPPORTED where the reference itself has no defined result: a layer left with no output position, the skip
-// un-dilation quirk at a per-row length of 1, fewer than output_length final positions (its view fails).
-static int wn_forward_geometry(const wn_handle* h, long long L, long long out_len, WnFwdGeom& g, const char* who) {
-    const std::string why = wn_forward_geometry_host(h->dil.data(), h->plan.NL, L, out_len, g);   // (wn_plan.h: plain host arithmetic, tested with g++)
-    if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
-    return WN_OK;
-}
-
-// WaveNetModel.forward() for one-hot inputs (class indices), see wn_forward.h.  Asynchronous on hip_stream.
-// What wn_score asks of the forward instead of logits: the head's two products and the row statistics in one kernel (wn_score.h), or -- shapes that kernel is
-// not written for, bf16 operands (see wn_fused_score_enabled), WN_NO_FUSED_SCORE=1 with WN_TESTING=1 -- the two head products into the workspace and wn_score_rows over them.
-struct WnScoreOut {
-    const int64_t* targets;
-    float* row_nll;
-    int32_t* row_pred;
-    double* sums;
-};
-// Default: the fused kernel with fp32 operands, the unfused path with bf16 operands -- measured at config 5's evaluation batch (profiles/r07_score.txt) the fused
-// bf16 kernel is 0.5-1.7 ms SLOWER than the unfused path (it re-reads the skip tile once per chunk of end channels, and with bf16 operands the head is bound by
-// those reads, not by the matrix cores); fp32 is level to 0.6 ms faster.  WN_NO_FUSED_SCORE=1 / =0 (with WN_TESTING=1) pins the unfused / the fused path.
-static bool wn_fused_score_enabled(wn_handle* h, bool bf16) {
-    const char* off = wn_dev_env("WN_NO_FUSED_SCORE");
-    if (off) h->dev_overrides = 1;   // (read per call, not at wn_create: the handle reports it from the first scoring call on)
-    if (off && (off[0] == '1' || off[0] == '0')) return off[0] == '0';
-    return !bf16;
-}
-
-static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, const WnScoreOut* score, void* hip_stream,
-                          const char* who) {
-    if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
-    if (N < 1 || out_len < 1) return wn_fail(WN_E_BADARG, "%s: N and output_length must be >= 1", who);
-    const WnPlan& pl = h->plan;
-    const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
-    if (!h->fw_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2 and channel counts that are multiples of 32", who);
-    if ((long long)N * L >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "%s: N*L must stay below 2^31 rows", who);
-    { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
-    WnFwdGeom geo;
-    { int rc = wn_forward_geometry(h, L, out_len, geo, who); if (rc) return rc; }
-    const long long Mrows = (long long)N * out_len;
-    const bool score_fused = score && C == 256 && S % 32 == 0 && E % WN_SCORE_EC == 0 && wn_fused_score_enabled(h, h->fw_bf16 && h->fwb_ok);
-    size_t n_part = 0;
-    if (score) {   // one fp64 triple per workgroup of the kernel that scores
-        n_part = (size_t)(score_fused ? (Mrows + WN_SCORE_TM - 1) / WN_SCORE_TM : (Mrows + WN_SCORE_ROWS_PER_WG - 1) / WN_SCORE_ROWS_PER_WG);
-        if (h->score_parts < n_part) {
-            if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
-            (void)hipDeviceSynchronize();
-            rt_free(h->d_score_part);
-            h->d_score_part = (double*)rt_malloc(n_part * 3 * sizeof(double));
-            h->score_parts = h->d_score_part ? n_part : 0;
-            if (!h->d_score_part) return wn_fail(WN_E_NOMEM, "%s: %lld partial sums", who, (long long)n_part);
-        }
-    }
-    const std::vector<long long>& need = geo.rows;
-    const size_t x_fl = (size_t)N * L * R, z_fl = (size_t)N * need[1 < NL ? 1 : NL] * D > (size_t)N * need[NL] * D ? (size_t)N * need[1 < NL ? 1 : NL] * D : (size_t)N * need[NL] * D;
-    // The skip sum over layers is accumulated G layers at a time: the gate epilogue also drops z (last output_length rows)
-    // into column block (l mod G) of ZG [N*out_len][G*D], and one GEMM with K = G*D adds the group to SKIP -- instead of a
-    // read-modify-write of the whole SKIP matrix per layer (1.4 GB per layer at config 5).
-    const int G = pl.layers < NL ? pl.layers : NL;
-    const size_t skip_fl = (size_t)N * out_len * S, e_fl = (size_t)N * out_len * E, zg_fl = (size_t)N * out_len * G * D;
-    // bf16 operands at the 128 / 128 shape: a layer is ONE launch (wn_fwd_layer_bf16: z goes from the gate epilogue to the residual product
-    // through LDS and is never stored), its matrix operand reads of x take a bf16 shadow written next to x (WnGemmArgs::c_h), z on the skip
-    // rows (zg) is stored as bf16.  Same roundings as the two-launch form (every value is rounded to bf16 once, where it becomes an operand).
-    const bool fuse = h->fw_bf16 && h->fwb_ok && R == 128 && D == 128 && wn_fused_layer_enabled();
-    const size_t xh_fl = fuse ? ((x_fl + 1) / 2 + 63) / 64 * 64 : 0;
-    const size_t lg_fl = (score && !score_fused) ? (size_t)Mrows * C : 0;   // (unfused scoring: the logits live in the workspace)
-    const size_t total = 2 * x_fl + z_fl + skip_fl + e_fl + zg_fl + 2 * xh_fl + lg_fl;
-    if (h->ws_floats < total) {
-        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
-        rt_free(h->d_ws);
-        h->d_ws = (float*)rt_malloc(total * 4);
-        h->ws_floats = h->d_ws ? total : 0;
-        if (!h->d_ws) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
-    }
-    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl; float* skip = z + z_fl; float* ev = skip + skip_fl;
-    float* zg = ev + e_fl;
-    unsigned short* xha = fuse ? reinterpret_cast<unsigned short*>(zg + zg_fl) : nullptr;
-    unsigned short* xhb = fuse ? reinterpret_cast<unsigned short*>(zg + zg_fl + xh_fl) : nullptr;
-    if (lg_fl) logits = zg + zg_fl + 2 * xh_fl;
-    hipStream_t st = (hipStream_t)hip_stream;
-    {
-        const long long rows = N * L;
-        const long long work = rows * (R / 4);
-        hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, indices, h->d_start_t,
-                           pl.has_bias ? h->d_start_b : nullptr, xa, rows, R, xha);
-    }
-    const bool bf16 = h->fw_bf16 && h->fwb_ok;
-    auto launch = [&](int epi, const WnGemmArgs& a, const unsigned short* bn) { wn_launch_nn(st, epi, a, bf16 ? bn : nullptr); };
-    const unsigned short* fwb = h->d_fwb;
-    const float* fw = h->d_fw;
-    float* xin = xa; float* xout = xb;
-    unsigned short* xhin = xha; unsigned short* xhout = xhb;
-    for (int l = 0; l < NL; ++l) {
-        const long long d = h->dil[l], rows = need[l + 1], t0 = L - rows;
-        const int gi = l % G;
-        WnGemmArgs a;
-        memset(&a, 0, sizeof(a));
-        // z = gate([x(t-d) | x(t)] . Wfg^T)
-        const float* xop = fuse ? reinterpret_cast<const float*>(xhin) : xin;   // (fuse: the bf16 shadow, the row maps count bf16 elements)
-        a.a0 = WnRowMap{xop, (long long)L * R, R, t0 - d};
-        a.a_skip_lo[0] = (int)geo.zlo[l];   // (short clips: the reference's left zero padding stands in for x(t - d) there)
-        a.a1 = WnRowMap{xop, (long long)L * R, R, t0};
-        a.a_bf16 = fuse ? 1 : 0;
-        a.k_split = R; a.K = 2 * R; a.bt = fw + h->fw_off_fg + (size_t)l * 2 * R * 2 * D; a.N = 2 * D;
-        a.bias = pl.has_bias ? fw + h->fw_off_bfg + (size_t)l * 2 * D : nullptr;
-        a.c = WnRowMap{z, rows * D, D, 0};
-        a.c_bf16 = fuse ? 1 : 0;   // (fuse: z and zg hold bf16)
-        a.c2 = WnRowMap{fuse ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(zg) + (size_t)gi * D) : zg + (size_t)gi * D, out_len * (long long)G * D, (long long)G * D, 0};
-        a.c2_first_row = (int)(rows - out_len);
-        a.M = N * rows; a.rows_per_batch = (int)rows;
-        WnGemmArgs ar;  // x' = z . Wres^T + x(t)   (the last layer's residual output is never consumed, also upstream)
-        memset(&ar, 0, sizeof(ar));
-        if (l < NL - 1) {
-            ar.a0 = ar.a1 = WnRowMap{z, rows * D, D, 0};
-            ar.a_bf16 = fuse ? 1 : 0;
-            ar.k_split = D; ar.K = D; ar.bt = fw + h->fw_off_res + (size_t)l * D * R; ar.N = R;
-            ar.bias = pl.has_bias ? fw + h->fw_off_bres + (size_t)l * R : nullptr;
-            ar.cin = WnRowMap{xin, (long long)L * R, R, t0};
-            ar.c = WnRowMap{xout, (long long)L * R, R, t0};
-            ar.c_h = fuse ? xhout : nullptr;
-            ar.M = N * rows; ar.rows_per_batch = (int)rows;
-        }
-        bool fused = false;
-        if (fuse && l < NL - 1) {
-            WnGemmArgs af = a;
-            af.c.base = nullptr;   // z itself is not stored: nothing reads it again
-            fused = wn_launch_layer(st, af, fwb + h->fwb_off_fg + (size_t)l * 2 * D * 2 * R, ar, fwb + h->fwb_off_res + (size_t)l * R * D);
-        }
-        if (!fused) {
-            launch(WN_EPI_GATE, a, bf16 ? fwb + h->fwb_off_fg + (size_t)l * 2 * D * 2 * R : nullptr);
-            if (l < NL - 1) launch(WN_EPI_PLAIN, ar, bf16 ? fwb + h->fwb_off_res + (size_t)l * R * D : nullptr);
-        }
-        if (gi == G - 1 || l == NL - 1) {  // skip (+)= ZG . [Wskip of the group's layers]^T   (K = layers_in_group * D)
-            const int first = l - gi, cnt = gi + 1;
-            memset(&a, 0, sizeof(a));
-            a.a0 = a.a1 = WnRowMap{zg, out_len * (long long)G * D, (long long)G * D, 0};
-            a.a_bf16 = fuse ? 1 : 0;
-            a.k_split = cnt * D; a.K = cnt * D; a.bt = fw + h->fw_off_skip + (size_t)first * D * S; a.N = S;
-            a.bias = (pl.has_bias && first == 0) ? fw + h->fw_off_bskip_total : nullptr;
-            if (first > 0) a.cin = WnRowMap{skip, out_len * S, S, 0};
-            a.c = WnRowMap{skip, out_len * S, S, 0};
-            a.M = N * out_len; a.rows_per_batch = (int)out_len;
-            launch(WN_EPI_PLAIN, a, bf16 ? fwb + h->fwb_off_skip + (size_t)(first / G) * S * G * D : nullptr);
-        }
-        float* t = xin; xin = xout; xout = t;
-        unsigned short* th = xhin; xhin = xhout; xhout = th;
-    }
-    if (score_fused) {   // head and row statistics in one kernel: neither ev nor the logits reach HBM
-        WnScoreArgs sa;
-        memset(&sa, 0, sizeof(sa));
-        sa.skip = skip; sa.M = Mrows; sa.S = S; sa.E = E;
-        sa.w1t = fw + h->fw_off_w1; sa.w2t = fw + h->fw_off_w2; sa.b1 = fw + h->fw_off_b1; sa.b2 = fw + h->fw_off_b2;
-        if (bf16) { sa.w1h = fwb + h->fwb_off_w1; sa.w2h = fwb + h->fwb_off_w2; }
-        sa.targets = reinterpret_cast<const long long*>(score->targets); sa.row_nll = score->row_nll; sa.row_pred = score->row_pred; sa.part = h->d_score_part;
-        if (bf16) hipLaunchKernelGGL(wn_score_head_bf16, dim3((unsigned)n_part), dim3(256), 0, st, sa);
-        else hipLaunchKernelGGL(wn_score_head, dim3((unsigned)n_part), dim3(256), 0, st, sa);
-    } else {   // head: relu(skip) -> end_conv_1 (+b, relu) -> end_conv_2 (+b)     wavenet_model.py:167-169
-        WnGemmArgs a;
-        memset(&a, 0, sizeof(a));
-        a.a0 = a.a1 = WnRowMap{skip, out_len * S, S, 0};
-        a.k_split = S; a.K = S; a.bt = fw + h->fw_off_w1; a.N = E; a.bias = fw + h->fw_off_b1;
-        a.c = WnRowMap{ev, out_len * E, E, 0};
-        a.M = N * out_len; a.rows_per_batch = (int)out_len; a.relu_a = 1; a.relu_c = 1;
-        launch(WN_EPI_PLAIN, a, bf16 ? fwb + h->fwb_off_w1 : nullptr);
-        memset(&a, 0, sizeof(a));
-        a.a0 = a.a1 = WnRowMap{ev, out_len * E, E, 0};
-        a.k_split = E; a.K = E; a.bt = fw + h->fw_off_w2; a.N = C; a.bias = fw + h->fw_off_b2;
-        a.c = WnRowMap{logits, out_len * C, C, 0};
-        a.M = N * out_len; a.rows_per_batch = (int)out_len;
-        launch(WN_EPI_PLAIN, a, bf16 ? fwb + h->fwb_off_w2 : nullptr);
-        if (score)
-            hipLaunchKernelGGL(wn_score_rows, dim3((unsigned)n_part), dim3(256), 0, st, logits, C, reinterpret_cast<const long long*>(score->targets), Mrows,
-                               score->row_nll, score->row_pred, h->d_score_part);
-    }
-    if (score) hipLaunchKernelGGL(wn_score_reduce, dim3(1), dim3(1024), 0, st, h->d_score_part, (long long)n_part, score->sums);
-    return rt_hip(hipGetLastError(), score ? "wn_score launches" : "wn_forward launches");
-}
-
-extern "C" int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, void* hip_stream) {
-    g_err[0] = 0;
-    if (!h || !indices || !logits) return wn_fail(WN_E_BADARG, "wn_forward: NULL argument");
-    if (!h->chains.empty()) return wn_forward(h->chains[0], indices, N, L, out_len, logits, hip_stream);  // every chain holds the weights
-    return wn_forward_run(h, indices, N, L, out_len, logits, nullptr, hip_stream, "wn_forward");
-}
-
-// Teacher-forced scoring (include/wn_abi.h): wn_forward's stack up to the finished skip rows, then the head and the row statistics (wn_score.h).
-extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64_t N, int64_t L, int64_t out_len, float* row_nll, int32_t* row_pred,
-                        double* sums, void* hip_stream) {
-    g_err[0] = 0;
-    if (!h || !indices || !targets || !sums) return wn_fail(WN_E_BADARG, "wn_score: NULL argument");
-    if (wn_dev_env("WN_NO_FUSED_SCORE")) h->dev_overrides = 1;   // (the front handle of a job of several chains reports it too)
-    if (!h->chains.empty()) return wn_score(h->chains[0], indices, targets, N, L, out_len, row_nll, row_pred, sums, hip_stream);  // every chain holds the weights
-    const WnScoreOut so{targets, row_nll, row_pred, sums};
-    return wn_forward_run(h, indices, N, L, out_len, nullptr, &so, hip_stream, "wn_score");
-}
-
-// Batched (teacher-forced) priming: the n_prime = n_given - 1 priming evaluations of generate_fast (wavenet_model.py:259-269)
-// as GEMMs over all given positions at once instead of one chain pass per sample: the layer
-// inputs of the whole window are computed with the forward kernels (no skip / head work -- the reference discards those
-// outputs) and the newest d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
-// (queue time 0); activations before the stream start are zero at every layer, like DilatedQueue.reset().
-extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream) {
-    g_err[0] = 0;
-    if (!h || !first_samples) return wn_fail(WN_E_BADARG, "wn_prime: NULL argument");
-    if (!h->chains.empty()) {
-        if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
-        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
-        for (size_t i = 0; i < h->chains.size(); ++i) {
-            int rc = wn_prime(h->chains[i], first_samples + (size_t)h->chain_first[i] * (size_t)row_stride, n_prime, row_stride, hip_stream);
-            if (rc) return rc;
-        }
-        h->t_base = h->chains[0]->t_base;
-        return WN_OK;
-    }
-    if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_prime: wn_load_weights has not been called");
-    if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
-    if (n_prime == 0) return WN_OK;
-    const WnPlan& pl = h->plan;
-    const int R = pl.R, D = pl.D, NL = pl.NL, ns = pl.n_streams;
-    if (!h->fw_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: needs kernel_size 2 and channel counts that are multiples of 32");
-    if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
-    if (h->t_base != 0) return wn_fail(WN_E_STATE, "wn_prime: queues must be freshly reset (queue time is %lld)", h->t_base);
-    if (row_stride != n_prime && ns > 1) { /* strided rows are fine: handled by the gather below */ }
-    { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
-    const long long n = n_prime;
-    if ((long long)ns * n >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: too many rows");
-    // q[i] = trailing positions of layer i's input that are needed (its own queue: d+1, and what the layers above need)
-    std::vector<long long> q(NL + 1, 0);
-    for (int l = NL - 1; l >= 0; --l) {
-        const long long d = h->dil[l];
-        long long v = q[l + 1] > 0 ? q[l + 1] + d : 0;
-        if (v < d + 1) v = d + 1;
-        q[l] = v < n ? v : n;
-    }
-    long long max_d = 1;
-    for (int l = 0; l < NL; ++l) max_d = h->dil[l] > max_d ? h->dil[l] : max_d;
-    const long long Lp = max_d, Lt = Lp + n;  // every stream's activation rows are preceded by Lp rows of zeros (t < 0)
-    const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
-    const size_t total = 2 * x_fl + z_fl;
-    if (h->ws_floats < total) {
-        rt_free(h->d_ws);
-        h->d_ws = (float*)rt_malloc(total * 4);
-        h->ws_floats = h->d_ws ? total : 0;
-        if (!h->d_ws) return wn_fail(WN_E_NOMEM, "wn_prime: workspace of %.1f MB", total * 4e-6);
-    }
-    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl;
-    hipStream_t st = (hipStream_t)hip_stream;
-    int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * x_fl * 4, st), "hipMemsetAsync(prime workspace)");
-    if (rc) return rc;
-    // x0 = start_conv column gather over all given positions; rows of stream s start at xa + s*Lt*R + Lp*R
-    for (int s = 0; s < ns; ++s) {
-        const long long work = n * (R / 4);
-        hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, first_samples + (size_t)s * row_stride,
-                           h->d_start_t, pl.has_bias ? h->d_start_b : nullptr, xa + ((size_t)s * Lt + Lp) * R, n, R);
-    }
-    auto launch = [&](int epi, const WnGemmArgs& a) { wn_launch_nn(st, epi, a); };
-    const float* fw = h->d_fw;
-    float* xin = xa; float* xout = xb;
-    for (int l = 0; l < NL; ++l) {
-        const long long d = h->dil[l];
-        const int ML = (int)d + 1;
-        {   // queue of layer l <- newest min(d+1, n) columns of its input
-            const int count = (int)(ML < n ? ML : n);
-            const long long work = (long long)ns * count * (R / 4);
-            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, Lt * R,
-                               h->d_rings + h->ring_off[l], R, ML, ns, pl.P, n, count);
-        }
-        const long long rows = q[l + 1];
-        if (l == NL - 1 || rows <= 0) break;
-        const long long t0 = n - rows;
-        WnGemmArgs a;
-        memset(&a, 0, sizeof(a));
-        a.a0 = WnRowMap{xin + Lp * R, Lt * R, R, t0 - d};  // t - d may be negative: those rows are the zero prefix
-        a.a1 = WnRowMap{xin + Lp * R, Lt * R, R, t0};
-        a.k_split = R; a.K = 2 * R; a.bt = fw + h->fw_off_fg + (size_t)l * 2 * R * 2 * D; a.N = 2 * D;
-        a.bias = pl.has_bias ? fw + h->fw_off_bfg + (size_t)l * 2 * D : nullptr;
-        a.c = WnRowMap{z, rows * D, D, 0};
-        a.M = ns * rows; a.rows_per_batch = (int)rows;
-        launch(WN_EPI_GATE, a);
-        memset(&a, 0, sizeof(a));
-        a.a0 = a.a1 = WnRowMap{z, rows * D, D, 0};
-        a.k_split = D; a.K = D; a.bt = fw + h->fw_off_res + (size_t)l * D * R; a.N = R;
-        a.bias = pl.has_bias ? fw + h->fw_off_bres + (size_t)l * R : nullptr;
-        a.cin = WnRowMap{xin + Lp * R, Lt * R, R, t0};
-        a.c = WnRowMap{xout + Lp * R, Lt * R, R, t0};
-        a.M = ns * rows; a.rows_per_batch = (int)rows;
-        launch(WN_EPI_PLAIN, a);
-        float* t = xin; xin = xout; xout = t;
-    }
-    rc = rt_hip(hipGetLastError(), "wn_prime launches");
-    if (rc) return rc;
-    h->t_base = n;
-    return WN_OK;
-}
-
-// Operand precision of wn_forward's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),
-// 1 = bf16 operands with fp32 accumulation (the residual stream and all sums stay fp32).  wn_prime always runs fp32.
-extern "C" int wn_set_forward_precision(wn_handle* h, int32_t bf16) {
-    g_err[0] = 0;
-    if (!h) return wn_fail(WN_E_BADARG, "wn_set_forward_precision: NULL handle");
-    if (!h->chains.empty()) return wn_set_forward_precision(h->chains[0], bf16);
-    if (bf16 && !h->have_weights) return wn_fail(WN_E_STATE, "wn_set_forward_precision: load the weights first");
-    if (bf16 && !h->fwb_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 needs R, D, S, E to be multiples of 64");
-    h->fw_bf16 = bf16 ? 1 : 0;
-    return WN_OK;
-}
-
+#include "wn_forward.inl"
 #include "wn_train.inl"
-
-extern "C" int wn_adam_step(const wn_adam_args* a) {
-    g_err[0] = 0;
-    if (!a || a->n_tensors < 0 || (a->n_tensors > 0 && (!a->sizes || !a->params || !a->grads || !a->exp_avg || !a->exp_avg_sq)) || !a->scratch)
-        return wn_fail(WN_E_BADARG, "wn_adam_step: NULL argument");
-    if (a->step < 1 || !(a->beta1 >= 0. && a->beta1 < 1.) || !(a->beta2 >= 0. && a->beta2 < 1.) || !(a->eps >= 0.))
-        return wn_fail(WN_E_BADARG, "wn_adam_step: step must be >= 1, betas in [0, 1), eps >= 0");
-    if (a->flags & ~(int64_t)(WN_ADAM_NORM_ONLY | WN_ADAM_NORM_KEEP | WN_ADAM_NORM_GIVEN)) return wn_fail(WN_E_BADARG, "wn_adam_step: unknown flags");
-    if ((a->flags & WN_ADAM_NORM_ONLY) && (a->flags & WN_ADAM_NORM_GIVEN)) return wn_fail(WN_E_BADARG, "wn_adam_step: NORM_ONLY and NORM_GIVEN exclude each other");
-    // (no handle: the caller's current device is left as it was -- torch's current device is process state the parameters' device must not change)
-    struct DeviceGuard {
-        int prev = -1;
-        ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-    } guard;
-    { int cur = -1; if (hipGetDevice(&cur) == hipSuccess && cur != a->device_id) guard.prev = cur; else (void)hipGetLastError(); }
-    { int rc = rt_hip(hipSetDevice(a->device_id), "hipSetDevice"); if (rc) return rc; }
-    hipStream_t st = (hipStream_t)a->hip_stream;
-    const bool norm_only = (a->flags & WN_ADAM_NORM_ONLY) != 0;
-    const bool clip = a->max_grad_norm > 0. || norm_only;
-    double* acc = static_cast<double*>(a->scratch);
-    WnAdamScalars k;   // every fp32 scalar is the double torch forms in Python, rounded once (torch/optim/adam.py: _multi_tensor_adam)
-    const double bc1 = 1.0 - pow(a->beta1, (double)a->step), bc2 = 1.0 - pow(a->beta2, (double)a->step);
-    k.neg_step = (float)(-(a->lr / bc1)); k.sqrt_bc2 = (float)sqrt(bc2);
-    k.one_minus_b1 = (float)(1.0 - a->beta1); k.b2 = (float)a->beta2; k.one_minus_b2 = (float)(1.0 - a->beta2); k.eps = (float)a->eps;
-    k.weight_decay = (float)a->weight_decay; k.max_norm = (clip && !norm_only) ? (float)a->max_grad_norm : 0.f;
-    k.lerp_hi = k.one_minus_b1 >= 0.5f ? 1 : 0;
-    // batches of up to WN_OPT_TENSORS tensors (skipping the ones without a gradient: torch's optimisers do)
-    std::vector<WnOptBatch> batches;
-    WnOptBatch b;
-    memset(&b, 0, sizeof(b));
-    auto flush = [&]() { if (b.n > 0) { batches.push_back(b); memset(&b, 0, sizeof(b)); } };
-    for (int i = 0; i < a->n_tensors; ++i) {
-        if (!a->grads[i] || a->sizes[i] <= 0) continue;
-        if (!a->params[i] || !a->exp_avg[i] || !a->exp_avg_sq[i]) return wn_fail(WN_E_BADARG, "wn_adam_step: tensor %d has a gradient but no parameter / state pointer", i);
-        const long long chunks = (a->sizes[i] + WN_OPT_CHUNK - 1) / WN_OPT_CHUNK;
-        if (b.n == WN_OPT_TENSORS || (long long)b.chunk0[b.n] + chunks > 0x3fffffffll) flush();
-        b.p[b.n] = static_cast<float*>(a->params[i]); b.g[b.n] = static_cast<float*>(a->grads[i]);
-        b.m[b.n] = static_cast<float*>(a->exp_avg[i]); b.v[b.n] = static_cast<float*>(a->exp_avg_sq[i]);
-        b.size[b.n] = a->sizes[i];
-        b.chunk0[b.n + 1] = b.chunk0[b.n] + (int)chunks;
-        b.n++;
-    }
-    flush();
-    // The norm of a clipped step is the norm of ALL gradients that are clipped together (clip_grad_norm_(model.parameters())): a caller with several
-    // parameter groups first adds every group's sum of squares into `scratch` (NORM_ONLY; NORM_KEEP from the second group on), then steps each group on
-    // the total (NORM_GIVEN).  One group: one call, no flags.
-    if (clip && !(a->flags & WN_ADAM_NORM_GIVEN)) {
-        if (!(a->flags & WN_ADAM_NORM_KEEP)) {
-            int rc = rt_hip(hipMemsetAsync(acc, 0, sizeof(double), st), "hipMemsetAsync(norm)");
-            if (rc) return rc;
-        }
-        for (const WnOptBatch& bb : batches) hipLaunchKernelGGL(wn_opt_sumsq, dim3((unsigned)bb.chunk0[bb.n]), dim3(256), 0, st, bb, acc);
-    }
-    if (norm_only) return rt_hip(hipGetLastError(), "wn_adam_step launches");
-    for (const WnOptBatch& bb : batches)
-        hipLaunchKernelGGL(wn_opt_adam, dim3((unsigned)bb.chunk0[bb.n]), dim3(256), 0, st, bb, k, clip ? acc : nullptr, clip ? a->total_norm : nullptr);
-    return rt_hip(hipGetLastError(), "wn_adam_step launches");
-}
+#include "wn_optim.inl"
