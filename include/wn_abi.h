@@ -161,8 +161,8 @@ typedef struct wn_info {
                                  (no usable table: said once on stderr), -1 = no job yet */
     int32_t gate_waited_ms;   /* how long the last job waited for jobs booked in front of it */
     int32_t gate_need_per_xcd; /* CUs per XCD a job of this handle books: the workgroups it keeps resident on its fullest XCD (of n_compute_units / 8) */
-    int32_t forward_native;   /* after wn_load_weights: 1 = wn_forward / wn_prime serve this handle's (padded) shape, 0 = they answer WN_E_UNSUPPORTED
-                                 for every call (kernel_size != 2, channel counts that are not multiples of 32 after padding); the facade keys its
+    int32_t forward_native;   /* after wn_load_weights: 1 = wn_forward / wn_score / wn_prime serve this handle's (padded) shape, 0 = they answer WN_E_UNSUPPORTED
+                                 for every call (kernel_size above 4, channel counts that are not multiples of 32 after padding); the facade keys its
                                  "do not ask again" on THIS, not on the text of an error */
     int32_t workgroups_per_cu; /* workgroups of the job's kernel ONE compute unit holds with the job's LDS (hipOccupancyMaxActiveBlocksPerMultiprocessor,
                                   checked against the plan at wn_create) */
@@ -224,8 +224,10 @@ int wn_export_queue(wn_handle* h, int32_t layer, int32_t stream, float* host_dat
  * (round 4; the same holds for wn_train_forward / wn_train_backward: pad zeros carry no gradient).  WN_E_UNSUPPORTED for clip
  * lengths at which the reference itself has no defined result -- a layer left without an output position, the skip path's
  * un-dilation quirk at a per-row length of 1 (Appendix A item 17), fewer than output_length final positions; the message names
- * the layer --, for kernel_size != 2 and for channel counts that are not multiples of 32 (after zero padding): callers use the
- * torch path for those, which reproduces what the reference does there. */
+ * the layer --, for kernel_size above 4 and for channel counts that are not multiples of 32 (after zero padding): callers use the
+ * torch path for those, which reproduces what the reference does there.  kernel_size 3 and 4 (fp32 operands; the filter/gate product of a
+ * layer reads its k taps as k row-shifted views of the activation matrix, csrc/wn_forward.h: wn_fwd_gemm_taps) are served from
+ * L >= receptive_field + output_length - 1 on: shorter clips -- the zero-padding regime above -- are WN_E_UNSUPPORTED for them. */
 int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t output_length, float* logits, void* hip_stream);
 
 /* Teacher-forced scoring -- what WavenetTrainer.validate() computes per batch (wavenet_training.py:89-112: output = model(x);
@@ -254,7 +256,7 @@ int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64
  * since round 5 the skip convs' share of dz (one product per block of layers, added to the residual conv's share by the gate
  * derivative) as well: one more rounding point, carried by the step's oracle, oracle/bf16_step.py;
  * logits differ from the fp32 path at the 1e-2 level of their scale, gradients by a few per cent in norm -- mostly sign
- * flips of ReLU masks).  WN_E_UNSUPPORTED unless R, D, S and E are multiples of 64. */
+ * flips of ReLU masks).  WN_E_UNSUPPORTED unless R, D, S and E are multiples of 64 and kernel_size is 2 (kernel_size 3 and 4 run fp32). */
 int wn_set_forward_precision(wn_handle* h, int32_t bf16);
 
 /* The priming loop of generate_fast (wavenet_model.py:259-269) for ALL given samples at once: `first_samples` is a DEVICE
@@ -262,7 +264,8 @@ int wn_set_forward_precision(wn_handle* h, int32_t bf16);
  * forced with the forward GEMM kernels (no skip / head work: the reference discards those outputs) and the queues are left
  * exactly as n_prime single evaluations would leave them.  Needs freshly reset queues (wn_reset); follow with
  * wn_generate(n_given = 1, first_samples = the last given sample).  WN_E_UNSUPPORTED under the same shape limits as
- * wn_forward: callers then prime through wn_generate.  Asynchronous on hip_stream. */
+ * wn_forward (kernel_size 2, 3 and 4; any n_prime: before the stream start every layer's activations are zero, like a reset queue's):
+ * callers then prime through wn_generate.  Asynchronous on hip_stream. */
 int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream);
 
 /* ---- training step (WavenetTrainer.train, wavenet_training.py:58-107: output = model(x); loss = cross_entropy; loss.backward()) ----
@@ -270,7 +273,8 @@ int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_
  * fp32 DEVICE array in the packed layout described by wn_train_layout (each reference parameter appears exactly once, so
  * any element-wise optimiser can step on the flat array directly), plus a same-shaped gradient array.  The loss (and its
  * gradient w.r.t. the logits) stays with the caller -- the reference computes it with F.cross_entropy (wavenet_training.py:83).
- * Offsets are in floats.  Packed layouts (NL layers, R/D/S/E/C channel counts, k = 2 taps):
+ * Offsets are in floats.  Packed layouts (NL layers, R/D/S/E/C channel counts, k = 2 taps; the inference bank of a kernel_size 3 or 4 handle has
+ * fg [NL][kR][2D], tap 0 = x[t-(k-1)d] the oldest, and is not reachable through wn_train_*, which stay kernel_size 2):
  *   fg    [NL][2R][2D]  row = tap*R + r (tap 0 = x[t-d], tap 1 = x[t]); column = 64*(ch/32) + 32*gate + ch%32, gate 0 = filter
  *                       (filter_convs.l.weight[ch][r][tap], gate_convs.l.weight[ch][r][tap])       bfg [NL][2D] same columns
  *   res   [NL][D][R]    residual_convs.l.weight[r][d][0] transposed                                 bres [NL][R]

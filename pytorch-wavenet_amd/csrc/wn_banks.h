@@ -14,14 +14,18 @@
 #include "../../include/wn_abi.h"
 #include "wn_plan.h"
 
-// the batched forward and the training step need kernel_size 2 and channel counts that are multiples of 32
+// the training step (and the bf16 forward) needs kernel_size 2 and channel counts that are multiples of 32
 static inline bool wn_bank_ok(const WnPlan& s) { return s.k == 2 && s.R % 32 == 0 && s.D % 32 == 0 && s.S % 32 == 0 && s.E % 32 == 0 && s.C % 32 == 0; }
+// inference (wn_forward / wn_score / wn_prime, fp32 operands) also takes kernel_size 3 and 4: only the filter/gate product reads the taps (wn_fwd_gemm_taps)
+static inline bool wn_bank_fwd_ok(const WnPlan& s) {
+    return s.k >= 2 && s.k <= 4 && s.R % 32 == 0 && s.D % 32 == 0 && s.S % 32 == 0 && s.E % 32 == 0 && s.C % 32 == 0;
+}
 
 static inline wn_train_layout wn_bank_layout(const WnPlan& s) {   // offsets in floats
-    const int64_t NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C;
+    const int64_t NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C, k = s.k;
     wn_train_layout t;
     int64_t o = 0;
-    t.fg = o; o += NL * 2 * R * 2 * D;
+    t.fg = o; o += NL * k * R * 2 * D;   // (k taps: Wfg^T of a layer is [k*R][2D], tap j -- j = 0 the oldest -- in rows j*R .. (j+1)*R - 1)
     t.bfg = o; o += NL * 2 * D;
     t.res = o; o += NL * D * R;
     t.bres = o; o += NL * R;
@@ -67,16 +71,16 @@ static inline void wn_transpose_start(const float* start_w, int R, int C, float*
 // B^T [K][N] row-major per layer (see wn_forward.h).  Bias sections stay zero for a model without stack biases.
 static inline std::vector<float> wn_pack_bank(const wn_train_layout& o, const WnPlan& s, const wn_weight_ptrs* w) {
     const bool has_bias = s.has_bias != 0;
-    const int NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C;
+    const int NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C, k = s.k;
     std::vector<float> fw((size_t)o.total, 0.f);
     for (int l = 0; l < NL; ++l) {
-        float* fg = fw.data() + o.fg + (size_t)l * 2 * R * 2 * D;
+        float* fg = fw.data() + o.fg + (size_t)l * k * R * 2 * D;
         for (int ch = 0; ch < D; ++ch) {
             const int nf = 64 * (ch / 32) + (ch % 32), ng = nf + 32;  // column order [F(32) | G(32)] per 32-channel group
-            for (int tap = 0; tap < 2; ++tap)
+            for (int tap = 0; tap < k; ++tap)
                 for (int r = 0; r < R; ++r) {
-                    fg[(size_t)(tap * R + r) * 2 * D + nf] = w->filter_w[(((size_t)l * D + ch) * R + r) * 2 + tap];
-                    fg[(size_t)(tap * R + r) * 2 * D + ng] = w->gate_w[(((size_t)l * D + ch) * R + r) * 2 + tap];
+                    fg[(size_t)(tap * R + r) * 2 * D + nf] = w->filter_w[(((size_t)l * D + ch) * R + r) * k + tap];
+                    fg[(size_t)(tap * R + r) * 2 * D + ng] = w->gate_w[(((size_t)l * D + ch) * R + r) * k + tap];
                 }
             if (has_bias) {
                 fw[o.bfg + (size_t)l * 2 * D + nf] = w->filter_b[(size_t)l * D + ch];

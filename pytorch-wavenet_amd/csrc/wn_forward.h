@@ -457,6 +457,108 @@ __global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm(WnGemmArgs g) {
     wn_gemm_epilogue<EPI>(g, acc, m0 + 32 * wv, n0, lane, smem_f + wv * WN_EPI_TILE_FLOATS);   // (the loop's last barrier: nobody reads the operand buffers any more)
 }
 
+// ---- The filter/gate product of a layer with kernel_size TAPS = 3 or 4 (inference: wn_forward / wn_score / wn_prime, fp32 operands):
+//     z = gate([x(t - (TAPS-1) d) | ... | x(t - d) | x(t)] . Wfg^T + b),   K = TAPS * R,
+// wn_fwd_gemm<WN_EPI_GATE>'s tile, K loop and epilogue with an A operand of TAPS row-shifted views of ONE activation matrix (no
+// dilate() copies): g.a1 is the view of x(t), view j (j = 0 the oldest tap, columns j*R .. of Wfg) lies (TAPS-1-j) * tap_rows rows
+// before it, g.k_split = R is the K extent of a view (a K chunk never straddles two views: R % 32 == 0), g.K = TAPS * R.  The chunks
+// are streamed through the same double-buffered LDS image as the two-view product's: its size does not depend on TAPS.
+// A view's row is formed from (batch entry, row in the entry) like every other row here, so a tap stays inside its batch entry: the
+// host guarantees t0 - (TAPS-1) * tap_rows >= t_min, the first row of an entry that exists (0 in the forward; minus the zero prefix
+// in wn_prime), and a row before t_min reads as zero instead of being loaded.
+struct WnTapsArgs {
+    WnGemmArgs g;          // a0, bt1, a_skip_*, a_bf16, relu_a: unused
+    long long tap_rows;    // d: rows between two neighbouring taps
+    long long t_min;       // first row (in the units of g.a1.t0) of a batch entry that may be read
+};
+template <int TAPS>
+__global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm_taps(WnTapsArgs ta) {
+    static_assert(TAPS == 3 || TAPS == 4, "kernel_size 3 and 4 (2 is wn_fwd_gemm's two-view form)");
+    const WnGemmArgs& g = ta.g;
+    constexpr int TM = 128, TN = 128, KC = WN_GEMM_KC, AP = TM + 1;
+    constexpr int NQ = KC / 8;
+    constexpr int BT = 256 / KC;
+    __shared__ __attribute__((aligned(16))) float smem_f[2 * KC * AP + 2 * KC * TN + (2 * KC * AP) % 4];
+    static_assert(2 * KC * AP + 2 * KC * TN >= 4 * WN_EPI_TILE_FLOATS, "the operand buffers hold the four waves' staging tiles");
+    float (*a_t)[KC * AP] = reinterpret_cast<float (*)[KC * AP]>(smem_f);                                        // [2][k][row]
+    float (*b_s)[KC * TN] = reinterpret_cast<float (*)[KC * TN]>(smem_f + ((2 * KC * AP + 3) & ~3));               // [2][k][col]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const unsigned mtiles = (unsigned)((g.M + TM - 1) / TM), tm_i = blockIdx.x % mtiles, tn_i = blockIdx.x / mtiles;  // row tiles fastest
+    const long long m0 = (long long)tm_i * TM;
+    const int n0 = (int)tn_i * TN;
+    wn_f16v acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+
+    // loader roles as in wn_fwd_gemm: A chunk = 128 rows x KC floats, two threads per row; B chunk = KC x 128
+    const int arow = tid >> 1, ahalf = tid & 1;
+    const long long am = m0 + arow;
+    const bool arow_ok = am < g.M;
+    const unsigned aq = arow_ok ? (unsigned)am / (unsigned)g.rows_per_batch : 0u, arem = arow_ok ? (unsigned)am - aq * (unsigned)g.rows_per_batch : 0u;
+    const float* a1p = wn_row_at(g.a1, aq, arem) + ahalf * (KC / 2);   // the row of x(t)
+    const long long tap_fl = ta.tap_rows * g.a1.row_stride;              // floats between two neighbouring taps
+    const long long t_row = g.a1.t0 + (long long)arem;                    // the row's time inside its batch entry
+    unsigned okmask = 0;                                                 // bit j: view j of this row exists
+#pragma unroll
+    for (int j = 0; j < TAPS; ++j) okmask |= (arow_ok && t_row - (TAPS - 1 - j) * ta.tap_rows >= ta.t_min) ? (1u << j) : 0u;
+    const int brow = tid / BT, bcol = (tid % BT) * (KC / 2);
+    const float* bp = g.bt + (size_t)brow * g.N + n0 + bcol;
+    const bool okb = n0 + bcol < g.N;   // (one predicate for the thread's NQ loads: see wn_fwd_gemm)
+
+    float4 va[NQ], vb[NQ];
+    int f_tap = 0, f_off = 0;   // the view and the column inside it of the next chunk to fetch
+    auto fetch = [&]() {
+        const bool ok = (okmask >> f_tap) & 1u;
+        const float* src = a1p - (long long)(TAPS - 1 - f_tap) * tap_fl + f_off;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) va[q] = ok ? *reinterpret_cast<const float4*>(src + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) vb[q] = okb ? *reinterpret_cast<const float4*>(bp + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bp += (size_t)KC * g.N;
+        f_off += KC;
+        if (f_off == g.k_split) { f_off = 0; ++f_tap; }
+    };
+    auto stash = [&](int buf) {  // registers -> LDS (A transposed to [k][row])
+        float* at = a_t[buf];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float4 x = va[q];
+            const int k = ahalf * (KC / 2) + q * 4;
+            at[(k + 0) * AP + arow] = x.x; at[(k + 1) * AP + arow] = x.y; at[(k + 2) * AP + arow] = x.z; at[(k + 3) * AP + arow] = x.w;
+        }
+        float* bs = b_s[buf] + brow * TN + bcol;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) *reinterpret_cast<float4*>(bs + q * 4) = vb[q];
+    };
+
+    const int nchunks = TAPS * (g.k_split / KC);
+    fetch();
+    stash(0);
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; ++kc) {
+        const int buf = kc & 1;
+        if (kc + 1 < nchunks) fetch();  // lands while this chunk is multiplied
+        const float* at = a_t[buf] + 32 * wv + (lane & 31);
+        const float* bs = b_s[buf] + (lane & 31);
+        const int kh = lane >> 5;
+#pragma unroll
+        for (int ks = 0; ks < KC / 2; ++ks) {
+            const float a = at[(2 * ks + kh) * AP];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float b = bs[(2 * ks + kh) * TN + 32 * j];
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
+            }
+        }
+        if (kc + 1 < nchunks) stash(buf ^ 1);
+        __syncthreads();
+    }
+
+    wn_gemm_epilogue<WN_EPI_GATE>(g, acc, m0 + 32 * wv, n0, lane, smem_f + wv * WN_EPI_TILE_FLOATS);   // (the loop's last barrier: nobody reads the operand buffers any more)
+}
+
 
 // ------------------------------------------------------------------------------------------------ bf16 operands
 // Same GEMM with bf16 MFMA operands and fp32 accumulation (v_mfma_f32_32x32x16_bf16, 16x the fp32 matrix rate): the fp32

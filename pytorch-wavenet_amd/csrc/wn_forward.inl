@@ -28,6 +28,13 @@ static void wn_launch_nn(hipStream_t st, int epi, const WnGemmArgs& a, const uns
     else hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a);
 }
 
+// The filter/gate product of a layer with kernel_size 3 or 4 (wn_fwd_gemm_taps: fp32 operands, the 128 x 128 tile)
+static void wn_launch_taps(hipStream_t st, int taps, const WnTapsArgs& a) {
+    const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)((a.g.N + 127) / 128));
+    if (taps == 3) hipLaunchKernelGGL(wn_fwd_gemm_taps<3>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(wn_fwd_gemm_taps<4>, grid, dim3(256), 0, st, a);
+}
+
 // One forward layer in one launch (wn_fwd_layer_bf16): `a` = the filter/gate product's arguments (bf16 operands, c_bf16 = 1; a.c.base may be
 // NULL: z is not stored), `r` = the residual product's (its bias, cin, c, c_h are used).  Returns false when the shape is not the fused
 // kernel's (the caller launches the two products).  WN_NO_FUSED_LAYER=1 (with WN_TESTING=1) switches it off for A/B runs.
@@ -89,12 +96,21 @@ static WnGemmTnArgs wn_tn(const WnRowMap& a, int Ka, const WnRowMap& b, int Nb, 
 
 // The pieces wn_forward, wn_prime and wn_train_forward share.  `fw` = the packed fp32 bank (layout o), n = batch entries, x = the layer's input at
 // the first of its `rows` output positions.
-// z = gate([x(t - d) | x(t)] . Wfg^T + b) of layer l
+// z = gate([x(t - d) | x(t)] . Wfg^T + b) of layer l   (kernel_size 2)
 static WnGemmArgs wn_layer_fg(const WnPlan& pl, const wn_train_layout& o, const float* fw, int l, const WnRowMap& x, long long d, const WnRowMap& z, long long n,
                               long long rows) {
     WnRowMap x0 = x;
     x0.t0 -= d;
     return wn_nn2(x0, x, pl.R, 2 * pl.R, fw + o.fg + (size_t)l * 2 * pl.R * 2 * pl.D, 2 * pl.D, pl.has_bias ? fw + o.bfg + (size_t)l * 2 * pl.D : nullptr, z, n * rows, rows);
+}
+// z = gate([x(t - (k-1) d) | ... | x(t)] . Wfg^T + b) of layer l, kernel_size k = 3 or 4: the views are formed in the kernel from the view of x(t);
+// t_min = the first row of a batch entry of x that exists (in the units of x.t0)
+static WnTapsArgs wn_layer_fg_taps(const WnPlan& pl, const wn_train_layout& o, const float* fw, int l, const WnRowMap& x, long long d, const WnRowMap& z, long long n,
+                                   long long rows, long long t_min) {
+    WnTapsArgs a;
+    a.g = wn_nn2(x, x, pl.R, pl.k * pl.R, fw + o.fg + (size_t)l * pl.k * pl.R * 2 * pl.D, 2 * pl.D, pl.has_bias ? fw + o.bfg + (size_t)l * 2 * pl.D : nullptr, z, n * rows, rows);
+    a.tap_rows = d; a.t_min = t_min;
+    return a;
 }
 // x' = z . Wres^T + bres + x(t) of layer l
 static WnGemmArgs wn_layer_res(const WnPlan& pl, const wn_train_layout& o, const float* fw, int l, const WnRowMap& z, const WnRowMap& x, const WnRowMap& xout,
@@ -119,7 +135,8 @@ static WnHeadArgs wn_head(const WnPlan& pl, const wn_train_layout& o, const floa
 }
 
 // Time geometry of WaveNetModel.forward() for clips of L samples (wavenet_modules.py:10-39 `dilate`, wavenet_model.py:125-196).
-// In absolute time every layer's sequence ends at L (a kernel-size-2 dilated conv drops its input's first d positions).  Where the
+// In absolute time every layer's sequence ends at L (a kernel-size-2 dilated conv drops its input's first d positions; kernel_size k: (k - 1) d,
+// served from L >= receptive_field + output_length - 1 on only -- wn_plan.h).  Where the
 // length of a layer's input is not a multiple of its dilation the reference left-pads it with ZERO ACTIVATIONS (wavenet_modules.py:24-27),
 // so layer l's input lives on [a[l], L) preceded by pad[l] = (-(L - a[l])) mod d zeros, and its output on [a[l+1], L) with
 // a[l+1] = a[l] - pad[l] + d.  With L >= receptive_field + output_length - 1 none of the returned positions can see a pad zero (the
@@ -129,7 +146,7 @@ static WnHeadArgs wn_head(const WnPlan& pl, const wn_train_layout& o, const floa
 // Returns WN_E_UNSUPPORTED where the reference itself has no defined result: a layer left with no output position, the skip
 // un-dilation quirk at a per-row length of 1, fewer than output_length final positions (its view fails).
 static int wn_forward_geometry(const wn_handle* h, long long L, long long out_len, WnFwdGeom& g, const char* who) {
-    const std::string why = wn_forward_geometry_host(h->dil.data(), h->plan.NL, L, out_len, g);   // (wn_plan.h: plain host arithmetic, tested with g++)
+    const std::string why = wn_forward_geometry_host(h->dil.data(), h->plan.NL, L, out_len, g, h->plan.k);   // (wn_plan.h: plain host arithmetic, tested with g++)
     if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
     return WN_OK;
 }
@@ -160,7 +177,7 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
     const WnPlan& pl = h->plan;
     const WnWeights& wt = h->w;
     const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
-    if (!wt.fw_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2 and channel counts that are multiples of 32", who);
+    if (!wt.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
     if ((long long)N * L >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "%s: N*L must stay below 2^31 rows", who);
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
     WnFwdGeom geo;
@@ -177,6 +194,10 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
         }
     }
     const std::vector<long long>& need = geo.rows;
+    const int taps = pl.k;   // 2: the two-view product of wn_fwd_gemm; 3, 4: wn_fwd_gemm_taps (fp32 operands: fwb_ok is false for them)
+    if (taps != 2)
+        for (int l = 0; l < NL; ++l)
+            if (geo.zlo[l] != 0 || L - need[l + 1] - (long long)(taps - 1) * h->dil[l] < 0) return wn_fail(WN_E_UNSUPPORTED, "%s: kernel_size %d does not serve zero-padded taps", who, taps);
     const size_t x_fl = (size_t)N * L * R, z_fl = (size_t)N * need[1 < NL ? 1 : NL] * D > (size_t)N * need[NL] * D ? (size_t)N * need[1 < NL ? 1 : NL] * D : (size_t)N * need[NL] * D;
     // The skip sum over layers is accumulated G layers at a time: the gate epilogue also drops z (last output_length rows)
     // into column block (l mod G) of ZG [N*out_len][G*D], and one GEMM with K = G*D adds the group to SKIP -- instead of a
@@ -237,7 +258,12 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
             af.c.base = nullptr;   // z itself is not stored: nothing reads it again
             fused = wn_launch_layer(st, af, fwb + ob.fg + (size_t)l * 2 * D * 2 * R, ar, fwb + ob.res + (size_t)l * R * D);
         }
-        if (!fused) {
+        if (taps != 2) {   // (a's epilogue fields -- c, c2: z and its copy on the skip rows -- carried over)
+            WnTapsArgs at = wn_layer_fg_taps(pl, o, fw, l, wn_rows(xin, L, R, t0), d, wn_rows(z, rows, D), N, rows, 0);
+            at.g.c2 = a.c2; at.g.c2_first_row = a.c2_first_row;
+            wn_launch_taps(st, taps, at);
+            if (l < NL - 1) launch(WN_EPI_PLAIN, ar, 0);
+        } else if (!fused) {
             launch(WN_EPI_GATE, a, ob.fg + (size_t)l * 2 * D * 2 * R);
             if (l < NL - 1) launch(WN_EPI_PLAIN, ar, ob.res + (size_t)l * R * D);
         }
@@ -291,7 +317,7 @@ extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* tar
 // Batched (teacher-forced) priming: the n_prime = n_given - 1 priming evaluations of generate_fast (wavenet_model.py:259-269)
 // as GEMMs over all given positions at once instead of one chain pass per sample: the layer
 // inputs of the whole window are computed with the forward kernels (no skip / head work -- the reference discards those
-// outputs) and the newest d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
+// outputs) and the newest (k-1)*d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
 // (queue time 0); activations before the stream start are zero at every layer, like DilatedQueue.reset().
 extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream) {
     g_err[0] = 0;
@@ -311,23 +337,24 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
     if (n_prime == 0) return WN_OK;
     const WnPlan& pl = h->plan;
     const int R = pl.R, D = pl.D, NL = pl.NL, ns = pl.n_streams;
-    if (!h->w.fw_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: needs kernel_size 2 and channel counts that are multiples of 32");
+    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32");
+    const long long k1 = pl.k - 1;   // a layer's queue holds k1 * d + 1 columns, its conv reaches k1 * d positions back
     if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
     if (h->t_base != 0) return wn_fail(WN_E_STATE, "wn_prime: queues must be freshly reset (queue time is %lld)", h->t_base);
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
     const long long n = n_prime;
     if ((long long)ns * n >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: too many rows");
-    // q[i] = trailing positions of layer i's input that are needed (its own queue: d+1, and what the layers above need)
+    // q[i] = trailing positions of layer i's input that are needed (its own queue: k1*d+1, and what the layers above need)
     std::vector<long long> q(NL + 1, 0);
     for (int l = NL - 1; l >= 0; --l) {
         const long long d = h->dil[l];
-        long long v = q[l + 1] > 0 ? q[l + 1] + d : 0;
-        if (v < d + 1) v = d + 1;
+        long long v = q[l + 1] > 0 ? q[l + 1] + k1 * d : 0;
+        if (v < k1 * d + 1) v = k1 * d + 1;
         q[l] = v < n ? v : n;
     }
     long long max_d = 1;
     for (int l = 0; l < NL; ++l) max_d = h->dil[l] > max_d ? h->dil[l] : max_d;
-    const long long Lp = max_d, Lt = Lp + n;  // every stream's activation rows are preceded by Lp rows of zeros (t < 0)
+    const long long Lp = k1 * max_d, Lt = Lp + n;  // every stream's activation rows are preceded by Lp rows of zeros (t < 0): the oldest tap's reach
     const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
     const size_t total = 2 * x_fl + z_fl;
     if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "wn_prime: workspace of %.1f MB", total * 4e-6);
@@ -345,8 +372,8 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
     float* xin = xa; float* xout = xb;
     for (int l = 0; l < NL; ++l) {
         const long long d = h->dil[l];
-        const int ML = (int)d + 1;
-        {   // queue of layer l <- newest min(d+1, n) columns of its input
+        const int ML = (int)(k1 * d) + 1;
+        {   // queue of layer l <- newest min(k1*d+1, n) columns of its input
             const int count = (int)(ML < n ? ML : n);
             const long long work = (long long)ns * count * (R / 4);
             hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, Lt * R,
@@ -356,7 +383,8 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
         if (l == NL - 1 || rows <= 0) break;
         const long long t0 = n - rows;
         const WnRowMap zmap = wn_rows(z, rows, D), x = WnRowMap{xin + Lp * R, Lt * R, R, t0};   // (x: t - d may be negative: those rows are the zero prefix)
-        wn_launch_nn(st, WN_EPI_GATE, wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, ns, rows));
+        if (pl.k == 2) wn_launch_nn(st, WN_EPI_GATE, wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, ns, rows));
+        else wn_launch_taps(st, pl.k, wn_layer_fg_taps(pl, h->w.fw, fw, l, x, d, zmap, ns, rows, -Lp));
         wn_launch_nn(st, WN_EPI_PLAIN, wn_layer_res(pl, h->w.fw, fw, l, zmap, x, WnRowMap{xout + Lp * R, Lt * R, R, t0}, ns, rows));
         float* t = xin; xin = xout; xout = t;
     }
@@ -373,6 +401,7 @@ extern "C" int wn_set_forward_precision(wn_handle* h, int32_t bf16) {
     if (!h) return wn_fail(WN_E_BADARG, "wn_set_forward_precision: NULL handle");
     if (!h->chains.empty()) return wn_set_forward_precision(h->chains[0], bf16);
     if (bf16 && !h->have_weights) return wn_fail(WN_E_STATE, "wn_set_forward_precision: load the weights first");
+    if (bf16 && h->plan.k != 2) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 operands need kernel_size 2 (kernel_size %d runs fp32)", h->plan.k);
     if (bf16 && !h->w.fwb_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 needs R, D, S, E to be multiples of 64");
     h->fw_bf16 = bf16 ? 1 : 0;
     return WN_OK;

@@ -450,26 +450,37 @@ static inline int wn_v4_stream_limit(int n_stack) { const int n = (n_stack + 2) 
 // ---- time geometry of WaveNetModel.forward() (wn_forward / wn_train_*; comment: wn_runtime.hip above wn_forward_geometry)
 struct WnFwdGeom { std::vector<long long> a, rows, zlo; };
 // dil[l] = dilation of layer l.  Returns "" and fills g, or the reason why the reference has no defined result for clips of L samples.
-static inline std::string wn_forward_geometry_host(const int32_t* dil, int NL, long long L, long long out_len, WnFwdGeom& g) {
+// kernel_size k: a layer's conv drops its input's first (k - 1) d positions; zlo counts the output rows whose OLDEST tap is a pad zero.
+// k = 3, 4 are served from L >= receptive_field + output_length - 1 only (no returned position sees a pad zero: zlo is 0 everywhere);
+// shorter clips -- the reference's zero-padding regime, which the k = 2 kernels cover with row windows -- are refused for them.
+static inline std::string wn_forward_geometry_host(const int32_t* dil, int NL, long long L, long long out_len, WnFwdGeom& g, int kernel_size = 2) {
+    const long long k1 = kernel_size - 1;
     g.a.assign(NL + 1, 0); g.rows.assign(NL + 1, 0); g.zlo.assign(NL, 0);
+    if (kernel_size != 2) {
+        long long rf = 1;
+        for (int l = 0; l < NL; ++l) rf += k1 * dil[l];
+        if (L < rf + out_len - 1)
+            return "L=" + std::to_string(L) + " is below receptive_field + output_length - 1 = " + std::to_string(rf + out_len - 1) + ": with kernel_size " +
+                   std::to_string(kernel_size) + " the matrix-core forward does not serve the reference's zero-padding regime";
+    }
     for (int l = 0; l < NL; ++l) {
         const long long d = dil[l], len = L - g.a[l];
         if (len < 1) return "L=" + std::to_string(L) + " leaves layer " + std::to_string(l) + " without input (the reference's conv fails there)";
         const long long pad = (d - len % d) % d, steps = (len + pad) / d;   // per-row length of the dilated layout
-        if (steps < 2) return "L=" + std::to_string(L) + " leaves layer " + std::to_string(l) + " (dilation " + std::to_string(d) + ") no output position";
-        if (steps == 2 && d > 1)
+        if (steps < k1 + 1) return "L=" + std::to_string(L) + " leaves layer " + std::to_string(l) + " (dilation " + std::to_string(d) + ") no output position";
+        if (steps == k1 + 1 && d > 1)
             return "L=" + std::to_string(L) + " gives layer " + std::to_string(l) + " (dilation " + std::to_string(d) + ") a per-row output length of 1: the reference "
                    "skips the skip path's un-dilation there (wavenet_model.py:155) and its shapes no longer match";
-        g.a[l + 1] = g.a[l] - pad + d;
+        g.a[l + 1] = g.a[l] - pad + k1 * d;
     }
     if (L - g.a[NL] < out_len)
         return "L=" + std::to_string(L) + " yields " + std::to_string(L - g.a[NL]) + " output positions, output_length is " + std::to_string(out_len) +
                " (the reference's view(n * l, c) fails)";
     g.rows[NL] = out_len;
     for (int l = NL - 1; l >= 0; --l) {
-        const long long want = g.rows[l + 1] + dil[l], have = L - g.a[l];
+        const long long want = g.rows[l + 1] + k1 * dil[l], have = L - g.a[l];
         g.rows[l] = want < have ? want : have;
-        const long long z = g.a[l] + dil[l] - (L - g.rows[l + 1]);
+        const long long z = g.a[l] + k1 * dil[l] - (L - g.rows[l + 1]);
         g.zlo[l] = z > 0 ? z : 0;
     }
     return std::string();

@@ -317,7 +317,8 @@ struct WnDetWs { float* buf = nullptr; size_t floats = 0; };
 struct WnWeights {
     float *d_blobs = nullptr, *d_start_t = nullptr, *d_start_b = nullptr;
     // batched forward (wn_forward) and training: the fp32 bank, and its bf16 copy [N][K] row-major
-    float* d_fw = nullptr; size_t fw_floats = 0; bool fw_ok = false; wn_train_layout fw = {};
+    float* d_fw = nullptr; size_t fw_floats = 0; bool fw_ok = false; wn_train_layout fw = {};   // fw_ok: the training step's shapes (kernel_size 2)
+    bool fwd_ok = false;   // inference (wn_forward / wn_score / wn_prime): also kernel_size 3 and 4 (wn_banks.h: wn_bank_fwd_ok)
     unsigned short* d_fwb = nullptr; size_t fwb_elems = 0; bool fwb_ok = false; WnBf16Layout fwb;
 };
 struct wn_handle {
@@ -808,7 +809,9 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
     if (rc) return rc;
     // GEMM-ready banks for wn_forward and the training step (wn_banks.h)
     wt.fw_ok = wn_bank_ok(pl);
-    if (wt.fw_ok) {
+    wt.fwd_ok = wn_bank_fwd_ok(pl);
+    wt.fwb_ok = false;
+    if (wt.fwd_ok) {
         wt.fw = wn_bank_layout(pl);
         const std::vector<float> fw = wn_pack_bank(wt.fw, pl, w);
         const size_t o = fw.size();
@@ -818,8 +821,8 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
         if (rc) return rc;
         // bf16 copies for wn_set_forward_precision(1)
         const WnBf16Layout fwb = wn_bank_layout_bf16(pl);
-        wt.fwb_ok = fwb.ok;
-        if (fwb.ok) {
+        wt.fwb_ok = wt.fw_ok && fwb.ok;   // (bf16 operands: kernel_size 2 only)
+        if (wt.fwb_ok) {
             wt.fwb = fwb;
             const std::vector<unsigned short> wb = wn_pack_bank_bf16(fwb, wt.fw, pl, fw, w);
             const size_t ob = wb.size();
@@ -1060,7 +1063,7 @@ extern "C" int wn_get_info(wn_handle* h, wn_info* out) {
     out->layers_per_workgroup = h->variant == 4 ? pl.LPW : 1;
     out->gate_shared = h->gate_shared; out->gate_waited_ms = h->gate_waited_ms;
     { int need = 0, cap = 0; wn_gate_numbers(h, &need, &cap); out->gate_need_per_xcd = need; }
-    out->forward_native = (h->have_weights && h->w.fw_ok) ? 1 : 0;
+    out->forward_native = (h->have_weights && h->w.fwd_ok) ? 1 : 0;
     out->workgroups_per_cu = h->wg_per_cu; out->resident_timeout_ms = h->resident_ms; out->skip_lane_slots = h->variant == 3 ? h->v3_slots : 0;
     return WN_OK;
 }

@@ -145,6 +145,12 @@ class WaveNetModel(nn.Module):
         return self.kernel_size == 2 and not any(c % 32 for c in (self.residual_channels, self.dilation_channels, self.skip_channels,
                                                                   self.end_channels, self.classes))
 
+    def _native_indices_supported(self):
+        """Shapes the index-based inference extensions cover (forward_indices / score_indices: wn_forward / wn_score): kernel_size 2, 3 or 4,
+        channel counts multiples of 32.  forward() on a one-hot tensor and training stay on torch ops for kernel_size != 2."""
+        return self.kernel_size in (2, 3, 4) and not any(c % 32 for c in (self.residual_channels, self.dilation_channels, self.skip_channels,
+                                                                            self.end_channels, self.classes))
+
     def _native_trainable(self):
         """Shapes the native training step covers: kernel_size 2 and a class count that is a multiple of 32 -- channel counts that are not multiples
         of 32 are zero-padded up to multiples of 64 for it (round 6: mi355_wavenet/training.py StackRunner.pad_tensors; same logits, same gradients)."""
@@ -251,6 +257,8 @@ class WaveNetModel(nn.Module):
         c = eng.cfg   # (the ENGINE's channel shape: the training engine of a model with odd channel counts is zero-padded to multiples of 64)
         if want and any(c[k] % 64 for k in ("residual_channels", "dilation_channels", "skip_channels", "end_channels")):
             want = False
+        if c.get("kernel_size", 2) != 2:
+            want = False   # (kernel_size 3 and 4: the matrix-core inference path is fp32 only)
         eng.set_forward_precision(want)
 
     def _native_train_forward(self, idx):
@@ -310,10 +318,13 @@ class WaveNetModel(nn.Module):
             raise ValueError("indices must be (N, L) class indices")
         if training and self._native_trainable():
             pass   # (the training engine pads odd channel counts itself)
-        elif not self._native_supported():
-            raise ValueError("the index-based forward needs kernel_size 2 and channel counts that are multiples of 32 "
-                             "(residual %d, dilation %d, skip %d, end %d, classes %d)" % (
-                                 self.residual_channels, self.dilation_channels, self.skip_channels, self.end_channels, self.classes))
+        elif training and self.kernel_size != 2:
+            raise ValueError("the index-based training forward needs kernel_size 2 (kernel_size %d: inference only, forward_indices / "
+                             "score_indices)" % self.kernel_size)
+        elif not self._native_indices_supported():
+            raise ValueError("the index-based forward needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32 "
+                             "(kernel_size %d, residual %d, dilation %d, skip %d, end %d, classes %d)" % (
+                                 self.kernel_size, self.residual_channels, self.dilation_channels, self.skip_channels, self.end_channels, self.classes))
         if idx.size(1) < 2:
             raise ValueError("items of %d sample(s): forward() needs at least two" % idx.size(1))
         if check and idx.numel() and (int(idx.min()) < 0 or int(idx.max()) >= self.classes):
