@@ -1,5 +1,5 @@
 """TEST INFRASTRUCTURE: ctypes binding of tests/kernels/libwn_kernel_harness.so (tests/kernels/build_harness.py), the product's training-time
-kernels launched one at a time through their own launchers.  The argument structs are filled in C (wn_kernel_harness.hip): this side
+and inference kernels launched one at a time through their own launchers.  The argument structs are filled in C (wn_kernel_harness.hip): this side
 passes scalars, device pointers and row maps as (pointer, batch_stride, row_stride, t0).  The product package never loads it."""
 import ctypes
 import os
@@ -20,6 +20,15 @@ _SIGS = {
     "kh_tn_reduce": [_P, _P, _I, _I, _I, _P, _I, _I],
     "kh_gate_bwd": [_P, _I, _P, _P, _P, _P, _LL, _I, _P, _I, _I, _I],
     "kh_xent": [_P, _P, _P, _LL, _P, _P, _P],
+    "kh_taps": [_P, _I] + _MAP + [_LL, _LL, _I, _P, _I, _P] + _MAP + [_LL, _I] + _MAP + [_I, _P, _P, _I],
+    "kh_score_head": [_P, _I, _P, _LL, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "kh_score_rows": [_P, _P, _I, _P, _LL, _P, _P, _P],
+    "kh_score_reduce": [_P, _P, _LL, _P],
+    "kh_fill_ring": [_P, _P, _LL, _P, _I, _I, _I, _I, _LL, _I],
+    "kh_fwd_start": [_P, _P, _P, _P, _P, _LL, _I, _P],
+    "kh_cvt_bf16": [_P, _P, _P, _LL],
+    "kh_cvt_bf16_transposed": [_P, _P, _LL, _P, _I, _I, _I],
+    "kh_transpose_batched": [_P, _P, _LL, _P, _I, _I, _I],
     "kh_tn_grid": [_LL, _I, _I, _I, _I, ctypes.POINTER(_LL)],
 }
 
@@ -32,7 +41,7 @@ class Harness:
             fn.argtypes = args
             fn.restype = None if name == "kh_tn_grid" else _I
         self.dll.kh_release.restype = None
-        assert self.dll.kh_version() == 1
+        assert self.dll.kh_version() == 2, "stale kernel harness (tests/kernels/build_harness.py --force)"
 
     def call(self, name, *args):
         rc = getattr(self.dll, name)(*args)

@@ -1,4 +1,5 @@
-// wn_kernel_harness.hip -- TEST INFRASTRUCTURE ONLY: the training-time matrix-core kernels launched one at a time (tests/test_gpu_kernels.py).
+// wn_kernel_harness.hip -- TEST INFRASTRUCTURE ONLY: the product's kernels launched one at a time: the training-time matrix-core kernels
+// (tests/test_gpu_kernels.py) and the inference kernels -- tap product, score head, ring fill, the small layout kernels (tests/test_gpu_infer_kernels.py).
 //
 // The product's runtime unit is included as it is, so its own static launchers (wn_launch_nn, wn_launch_tn, wn_launch_colsum, wn_launch_layer,
 // wn_launch_bwd_layer) and kernels, with their dispatch conditions, are the code under test: nothing is copied.  The entry points take plain
@@ -18,7 +19,7 @@ struct KhDet {
 
 extern "C" {
 
-int kh_version() { return 1; }
+int kh_version() { return 2; }
 
 // One NN product through wn_launch_nn.  bn != NULL: the bf16 forms (B as bf16 [N][ldb]); else fp32 with B^T = bt [K][N] (bt1: rows k >= k_split).
 int kh_nn(void* stream, int epi, KH_MAP(a0), KH_MAP(a1), int k_split, int K, const float* bt, const float* bt1, int N, const float* bias,
@@ -122,6 +123,86 @@ int kh_xent(void* stream, const float* logits, const long long* targets, long lo
     (void)hipGetLastError();
     hipLaunchKernelGGL(wn_xent_rows, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, (hipStream_t)stream, logits, targets, M, (float)(1.0 / (double)M), row_loss, dlogits);
     hipLaunchKernelGGL(wn_xent_reduce, dim3(1), dim3(1024), 0, (hipStream_t)stream, row_loss, M, 1.0 / (double)M, loss);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- inference kernels (tests/test_gpu_infer_kernels.py)
+// The filter/gate product of kernel_size `taps` = 3 or 4 through wn_launch_taps, its arguments filled as wn_layer_fg_taps fills them (a0 = a1 = the view
+// of x(t), k_split = R, K = taps * R), with the epilogue fields wn_forward_run adds (c2) and the saved gates.
+int kh_taps(void* stream, int taps, KH_MAP(x), long long tap_rows, long long t_min, int R, const float* bt, int N, const float* bias, KH_MAP(z), long long M,
+            int rows_per_batch, KH_MAP(c2), int c2_first_row, float* gate_t, float* gate_g, int gate_packed) {
+    WnTapsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g.a0 = KH_ROWMAP(x); a.g.a1 = KH_ROWMAP(x); a.g.k_split = R; a.g.K = taps * R; a.g.bt = bt; a.g.N = N; a.g.bias = bias;
+    a.g.c = KH_ROWMAP(z); a.g.M = M; a.g.rows_per_batch = rows_per_batch;
+    a.g.c2 = KH_ROWMAP(c2); a.g.c2_first_row = c2_first_row; a.g.gate_t = gate_t; a.g.gate_g = gate_g; a.g.gate_packed = gate_packed;
+    a.tap_rows = tap_rows; a.t_min = t_min;
+    if (taps != 3 && taps != 4) return -1;
+    (void)hipGetLastError();
+    wn_launch_taps((hipStream_t)stream, taps, a);
+    return (int)hipGetLastError();
+}
+
+// wn_score_head / wn_score_head_bf16 with the grid of wn_forward_run: one workgroup of 256 per WN_SCORE_TM rows, one fp64 triple of `part` each
+int kh_score_head(void* stream, int bf16, const float* skip, long long M, int S, int E, const float* w1t, const float* w2t, const unsigned short* w1h,
+                  const unsigned short* w2h, const float* b1, const float* b2, const long long* targets, float* row_nll, int* row_pred, double* part) {
+    WnScoreArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.skip = skip; sa.M = M; sa.S = S; sa.E = E; sa.w1t = w1t; sa.w2t = w2t; sa.w1h = w1h; sa.w2h = w2h; sa.b1 = b1; sa.b2 = b2;
+    sa.targets = targets; sa.row_nll = row_nll; sa.row_pred = row_pred; sa.part = part;
+    const unsigned n_part = (unsigned)((M + WN_SCORE_TM - 1) / WN_SCORE_TM);
+    (void)hipGetLastError();
+    if (bf16) hipLaunchKernelGGL(wn_score_head_bf16, dim3(n_part), dim3(256), 0, (hipStream_t)stream, sa);
+    else hipLaunchKernelGGL(wn_score_head, dim3(n_part), dim3(256), 0, (hipStream_t)stream, sa);
+    return (int)hipGetLastError();
+}
+
+int kh_score_rows(void* stream, const float* logits, int C, const long long* targets, long long M, float* row_nll, int* row_pred, double* part) {
+    const unsigned n_part = (unsigned)((M + WN_SCORE_ROWS_PER_WG - 1) / WN_SCORE_ROWS_PER_WG);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_score_rows, dim3(n_part), dim3(256), 0, (hipStream_t)stream, logits, C, targets, M, row_nll, row_pred, part);
+    return (int)hipGetLastError();
+}
+
+int kh_score_reduce(void* stream, const double* part, long long n, double* sums) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_score_reduce, dim3(1), dim3(1024), 0, (hipStream_t)stream, part, n, sums);
+    return (int)hipGetLastError();
+}
+
+// wn_fill_ring with the grid of wn_prime: one thread per float4 of the `count` newest rows of every stream
+int kh_fill_ring(void* stream, const float* x, long long x_batch_stride, float* ring, int R, int ML, int n_streams, int P, long long n_time, int count) {
+    const long long work = (long long)n_streams * count * (R / 4);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, x_batch_stride, ring, R, ML, n_streams, P, n_time, count);
+    return (int)hipGetLastError();
+}
+
+// wn_fwd_start as wn_forward_run / wn_train_forward launch it (xh: the bf16 shadow, may be NULL)
+int kh_fwd_start(void* stream, const int32_t* idx, const float* start_t, const float* start_b, float* x, long long rows, int R, unsigned short* xh) {
+    const long long work = rows * (R / 4);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, start_t, start_b, x, rows, R, xh);
+    return (int)hipGetLastError();
+}
+
+int kh_cvt_bf16(void* stream, const float* in, unsigned short* out, long long n) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_cvt_bf16, dim3((unsigned)((n / 2 + 256) / 256)), dim3(256), 0, (hipStream_t)stream, in, out, n);
+    return (int)hipGetLastError();
+}
+
+int kh_cvt_bf16_transposed(void* stream, const float* in, long long in_batch_stride, unsigned short* out, int rows, int cols, int batches) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_cvt_bf16_transposed, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32), (unsigned)batches), dim3(256), 0, (hipStream_t)stream,
+                       in, in_batch_stride, out, rows, cols);
+    return (int)hipGetLastError();
+}
+
+int kh_transpose_batched(void* stream, const float* in, long long in_batch_stride, float* out, int rows, int cols, int batches) {
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_transpose_batched, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32), (unsigned)batches), dim3(256), 0, (hipStream_t)stream,
+                       in, in_batch_stride, out, rows, cols);
     return (int)hipGetLastError();
 }
 

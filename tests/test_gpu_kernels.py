@@ -37,6 +37,7 @@ Branch table: each hipLaunchKernelGGL line of the launchers -> the cases (test i
                    wn_bwd_gemm_tn (+ wn_tn_reduce)          test_tn[f32-*], test_tn[idx-*], test_tn[relu-*], test_tn_window_2gb[f32]
   wn_launch_colsum wn_bwd_colsum<true> / <false>, wn_tn_reduce   test_colsum (N % 4 != 0: the atomics path in both modes)
   direct           wn_tn_reduce                             test_tn_reduce;  wn_bwd_gate<*>: test_gate_bwd;  wn_xent_rows/_reduce: test_xent
+(The inference kernels -- wn_launch_taps, the score kernels, ring fill, the small layout kernels: tests/test_gpu_infer_kernels.py, with a table of its own.)
 """
 import os
 import time
@@ -54,6 +55,7 @@ PLAIN, GATE, GATE_BWD = 0, 1, 2
 SENT32 = np.uint32(0x7FC0DEAD)    # sentinel of fp32 outputs (a NaN no kernel produces)
 SENT16 = np.uint16(0x7FDE)        # ... of bf16 outputs
 WORST = {}
+WALL = {}    # module -> its own wall time in seconds (modules that share the harness and its closing line)
 _T0 = time.time()
 
 
@@ -61,8 +63,13 @@ def _worst(family, err):
     WORST[family] = max(WORST.get(family, 0.0), float(err))
 
 
+_KH = []   # the loaded harness: tests/test_gpu_infer_kernels.py imports this fixture, and both modules share one harness and one closing line
+
+
 @pytest.fixture(scope="session")
 def kh(request):
+    if _KH:
+        return _KH[0]
     t0 = time.time()
     h = kernel_lib.build_and_load()
     build_s = time.time() - t0
@@ -70,10 +77,11 @@ def kh(request):
     def report():
         capman = request.config.pluginmanager.getplugin("capturemanager")
         with capman.global_and_fixture_disabled():
-            print("\ntest_gpu_kernels: %.1f s wall (harness build / load %.1f s); worst errors of the bounded families: %s"
-                  % (time.time() - _T0, build_s, ", ".join("%s %.3g" % kv for kv in sorted(WORST.items()))))
+            print("\ntest_gpu_kernels%s: %.1f s wall (harness build / load %.1f s); worst errors of the bounded families: %s"
+                  % ("".join(" (+ %s: %.1f s wall of its own)" % kv for kv in sorted(WALL.items())), time.time() - _T0, build_s, ", ".join("%s %.3g" % kv for kv in sorted(WORST.items()))))
         h.close()
     request.addfinalizer(report)
+    _KH.append(h)
     return h
 
 
