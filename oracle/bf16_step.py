@@ -16,7 +16,7 @@ rounding points and nothing else:
   * tanh(F) and sigmoid(G) are saved for the backward as bf16: the gate derivative dF = dz * G * (1 - T^2), dG = dz * T * G * (1 - G) is
     evaluated on the rounded pair, and [dF | dG] is stored as bf16 (the bias gradient of the filter / gate convs sums the stored values);
   * the skip convs' share of dz -- dzg = rb(dskip) . rb(Wskip), one product per block of layers in the kernels -- is STORED as bf16 (round 5,
-    WN_DZG_BF16 in csrc/wn_forward.h); the gate derivative adds it to the residual conv's share (fp32, never stored) in fp32;
+    wn_gemm_epilogue / wn_bwd_gate in csrc/wn_forward.h); the gate derivative adds it to the residual conv's share (fp32, never stored) in fp32;
   * the residual stream x, the skip sum, the pre-activations, biases, the loss and every bias gradient stay fp32; start_conv's gradient
     is an exact gather-sum (one-hot rows);
   * full-length clips only (L >= receptive_field + output_length - 1: no returned position sees the reference's pad zeros).

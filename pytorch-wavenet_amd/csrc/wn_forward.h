@@ -117,24 +117,14 @@ static __device__ __forceinline__ uint4 wn_pack_bf16x8(float4 a, float4 b) {
 // [row][zld bf16] of what the strip emits -- z (WN_EPI_GATE with c_bf16; g.c.base may then be NULL: z not stored) or the plain output
 // (WN_EPI_PLAIN) -- the A operand of the fused kernels' second product.
 // CB16: WN_EPI_PLAIN honours g.c_bf16 (the stand-alone bf16 products; the fused kernels' plain epilogues always write fp32 and compile without the branch).
-#ifndef WN_ABL_TN_PLAIN_STORE
-#define WN_ABL_TN_PLAIN_STORE 0   // timing ablation of wn_bwd_gemm_tn_bf16 (tools/build_variant.py; results wrong): plain stores instead of the fp32 atomics
-#endif
-#ifndef WN_DZG_BF16
-#define WN_DZG_BF16 1   // bf16 step: the skip path's share of dz -- dzg = dskip . Wskip of a block of layers, written by one product, read once by every layer's
-                        // gate derivative -- is STORED as bf16 like every other product output that only feeds the next stage ([dF|dG], z, the gate pair): 8.9 GB
-                        // of fp32 written and 8.9 GB read per config-5 step become 4.45 + 4.45.  One more rounding point of the bf16 step (oracle/bf16_step.py
-                        // carries it); 0 keeps fp32 (A/B builds: host and kernels read the same switch).
-#endif
+// bf16 step: the skip path's share of dz -- dzg = dskip . Wskip of a block of layers, written by one product, read once by every layer's gate derivative --
+// is STORED as bf16 like every other product output that only feeds the next stage ([dF|dG], z, the gate pair): 8.9 GB of fp32 written and 8.9 GB read per
+// config-5 step become 4.45 + 4.45 (-1.4 ms: profiles/r05_training_step_byte_cuts.txt).  One more rounding point of the bf16 step (oracle/bf16_step.py carries it).
 static __device__ __forceinline__ float wn_gate_clamp(float x) { return x > 100.f ? 100.f : (x < -100.f ? -100.f : x); }
 template <int EPI, int NTILES = 4, bool CB16 = false>
 static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, const wn_f16v (&acc)[NTILES], long long mw, int nw, int lane, float* stage,
                                                         unsigned short* zl = nullptr, int zld = 0) {
     const int col = lane & 31;
-#ifdef WN_EPI_TIMING_SKIP   // timing experiment (results wrong): one store per lane instead of the strip's epilogue
-    if (acc[0][0] + acc[1][1] + acc[2][2] + acc[3][3] == 12345.678f) const_cast<float*>(g.c.base)[lane] = 1.f;
-    return;
-#endif
     // row-wise lane roles: 4 columns per lane, 8 rows per pass (fp32 rows);  8 columns per lane, 16 rows per pass (bf16-stored rows)
     const int r4 = lane >> 3, c4 = 4 * (lane & 7);
     const int r8 = lane >> 2, c8 = 8 * (lane & 3);
@@ -253,17 +243,12 @@ static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, con
                     { const float4 a = *reinterpret_cast<const float4*>(sp), b = *reinterpret_cast<const float4*>(sp + 4);
                       dz[0] = a.x; dz[1] = a.y; dz[2] = a.z; dz[3] = a.w; dz[4] = b.x; dz[5] = b.y; dz[6] = b.z; dz[7] = b.w; }
                     if (g.c2.base && (int)rem >= g.c2_first_row) {
-#if WN_DZG_BF16   // (dzg is stored as bf16: c2's row map counts bf16 elements; one 16-byte load)
+                        // (dzg is stored as bf16: c2's row map counts bf16 elements; one 16-byte load)
                         const unsigned short* zrow = reinterpret_cast<const unsigned short*>(g.c2.base) + (long long)q * g.c2.batch_stride +
                                                      (g.c2.t0 + (long long)rem - g.c2_first_row) * g.c2.row_stride + ch0 + c8;
                         const uint4 a = *reinterpret_cast<const uint4*>(zrow);
                         dz[0] += __uint_as_float(a.x << 16); dz[1] += __uint_as_float(a.x & 0xffff0000u); dz[2] += __uint_as_float(a.y << 16); dz[3] += __uint_as_float(a.y & 0xffff0000u);
                         dz[4] += __uint_as_float(a.z << 16); dz[5] += __uint_as_float(a.z & 0xffff0000u); dz[6] += __uint_as_float(a.w << 16); dz[7] += __uint_as_float(a.w & 0xffff0000u);
-#else
-                        const float* zrow = g.c2.base + (long long)q * g.c2.batch_stride + (g.c2.t0 + (long long)rem - g.c2_first_row) * g.c2.row_stride + ch0 + c8;
-                        const float4 a = *reinterpret_cast<const float4*>(zrow), b = *reinterpret_cast<const float4*>(zrow + 4);
-                        dz[0] += a.x; dz[1] += a.y; dz[2] += a.z; dz[3] += a.w; dz[4] += b.x; dz[5] += b.y; dz[6] += b.z; dz[7] += b.w;
-#endif
                     }
                     if (g.gate_packed) {
                         const unsigned* gp = reinterpret_cast<const unsigned*>(g.gate_t) + m * g.N + ch0 + c8;
@@ -365,14 +350,10 @@ static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, con
 // C[M][N] (+)= A[M][K] . B^T[K][N]; 128 x 128 tile per workgroup, 4 waves, wave w owns rows 32w..32w+31 and all 128
 // columns (4 accumulator tiles of 32x32).  WN_EPI_GATE: the 128 columns are [F(32) | G(32) | F(32) | G(32)] and the tile
 // emits 64 columns of tanh(F+bf) * sigmoid(G+bg).
-#ifndef WN_GEMM_KC
 #define WN_GEMM_KC 16   // K chunk of the fp32 GEMMs.  Measured on the config-5 forward: 32 (65.8 KB LDS, 2 workgroups per CU)
                         // 89.4 ms; 16 (32.9 KB) with 3 per CU 78.4 ms, with 4 per CU (119 VGPRs) 71.2 ms; 8: 70.9 ms
-#endif
+#define WN_GEMM_MINB 4  // (workgroups per CU: the 71.2 ms of the line above)
 template <int EPI>
-#ifndef WN_GEMM_MINB
-#define WN_GEMM_MINB 4
-#endif
 __global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm(WnGemmArgs g) {
     constexpr int TM = 128, TN = 128, KC = WN_GEMM_KC, AP = TM + 1;  // AP: padded row length of the transposed A chunk
     constexpr int NQ = KC / 8;          // float4 per thread per operand and chunk
@@ -574,16 +555,9 @@ struct WnGemmArgsBf16 {
     int ldb;                   // 0 -> K
 };
 
-#ifndef WN_NN_COL_ADJ
-#define WN_NN_COL_ADJ 1   // column tiles of a row tile next to each other in dispatch order: grouped skip product 1176 -> 1097 us, dzg 1215 -> 1171 us
-#endif
-#ifndef WN_GEMM_BF16_KC
 #define WN_GEMM_BF16_KC 32    // config-5 forward (round 2): 64 (73.7 KB LDS, 2 workgroups per CU) 52.7 ms; 32 (41 KB, 3 per CU, 152 VGPRs) 40.8 ms
-#endif
-#ifndef WN_GEMM_BF16_MINB
 #define WN_GEMM_BF16_MINB 4   // 4-wave form: 4 workgroups per CU (exactly the CU's 160 KB of LDS, 128 VGPRs): 3 -> 4 took the residual / dx products from 346 to 314 us
                               // (the forms that convert an fp32-stored A on its way to LDS keep 3: at 128 VGPRs they spilled 2-3 registers -- round 6)
-#endif
 
 // WAVES = 4: 128 x 128 tile (wave w: rows 32w.., all 128 columns).  WAVES = 8: 128 x 256 tile (wave w: rows 32 (w & 3).., column half
 // w >> 2) for products with N >= 256 -- these GEMMs are streams over A (K is 128-512, M is 350 k-500 k rows), and a 128-column
@@ -604,12 +578,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? (A16 ? WN_GEMM_BF16_MINB :
     unsigned short (*a_s)[TM * LD] = reinterpret_cast<unsigned short (*)[TM * LD]>(smem_h);
     unsigned short (*b_s)[TN * LD] = reinterpret_cast<unsigned short (*)[TN * LD]>(smem_h + 2 * TM * LD);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv & 3, wc = wv >> 2;
-#if WN_NN_COL_ADJ   // the column tiles of a row tile next to each other in dispatch order (different XCDs, same moment: the second read of the
-                    // row tile's A is served by the memory-side cache; the XCD-local variant of this -- ids 8 apart -- measured slower)
+    // the column tiles of a row tile next to each other in dispatch order (different XCDs, same moment: the second read of the row tile's A is served by the
+    // memory-side cache; the XCD-local variant of this -- ids 8 apart -- measured slower): against row tiles fastest the grouped skip product 1176 -> 1097 us,
+    // dzg 1215 -> 1171 us (profiles/archive/r03_train_step_experiments.txt)
     const unsigned ntiles = (unsigned)((g.N + TN - 1) / TN), tm_i = blockIdx.x / ntiles, tn_i = blockIdx.x % ntiles;
-#else
-    const unsigned mtiles = (unsigned)((g.M + TM - 1) / TM), tm_i = blockIdx.x % mtiles, tn_i = blockIdx.x / mtiles;  // row tiles fastest
-#endif
     const long long m0 = (long long)tm_i * TM;
     const int n0 = (int)tn_i * TN;
     wn_f16v acc[4];
@@ -725,25 +697,14 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? (A16 ? WN_GEMM_BF16_MINB :
 // (or of itself and its neighbour for d < 128).  With one contiguous range of tiles per XCD, in dispatch order, both reads meet in one L2 a few microseconds apart
 // instead of going out to the fabric twice.  grid = 8 * ceil(tiles / 8) workgroups; the ones past the end return.  (The mapping of workgroups to XCDs is not a
 // contract: a different one costs the locality, nothing else.)
-#ifndef WN_LAYER_XCD_RANGES
-#define WN_LAYER_XCD_RANGES 1
-#endif
 static __device__ __forceinline__ long long wn_layer_tile(long long M) {
-#if WN_LAYER_XCD_RANGES
     const unsigned tiles = (unsigned)((M + 127) / 128), per = (tiles + 7) / 8;
     const unsigned t = (blockIdx.x & 7u) * per + (blockIdx.x >> 3);
     return (blockIdx.x >> 3) < per && t < tiles ? (long long)t : -1;
-#else
-    return (long long)blockIdx.x < (M + 127) / 128 ? (long long)blockIdx.x : -1;
-#endif
 }
 static inline unsigned wn_layer_grid(long long M) {
     const unsigned tiles = (unsigned)((M + 127) / 128);
-#if WN_LAYER_XCD_RANGES
     return 8u * ((tiles + 7) / 8);
-#else
-    return tiles;
-#endif
 }
 
 struct WnLayerArgs {
@@ -1205,9 +1166,7 @@ __global__ __launch_bounds__(256) void wn_tn_reduce(const float* part, int n_spl
 // thread reads a 4-column x 8-row patch (eight coalesced float4 loads), transposes it in registers and writes four 16-byte
 // [column][row 0..7] vectors.  Used by wn_train_backward when the step runs with bf16 operands (wn_set_forward_precision);
 // the one-hot product of start_conv stays on the fp32 kernel.
-#ifndef WN_TN_BF16_MINB
 #define WN_TN_BF16_MINB 3
-#endif
 // WAVES = 4: 128 x 128 tile of C.  WAVES = 8: 128 (Ka) x 256 (Nb) tile for Nb >= 256 (wave w: ka strip 32 (w & 3).., nb half w >> 2), so
 // that A -- the layer input x in the filter/gate weight gradient, 262 MB -- is streamed once instead of once per 128 columns of B.
 // B16: B is stored as bf16 rows.  Its chunk is copied to LDS as it is -- row-major [KC rows][TB columns], 16-byte pieces, no conversion,
@@ -1222,11 +1181,8 @@ typedef short wn_s8 __attribute__((ext_vector_type(8)));
 // residual weight gradient) where B16 is a clear gain (211 -> 160 us in the filter/gate one), so where the choice exists the bf16-stored
 // operand goes in as B (operands swapped, c_trans) -- but only for few row splits: a transposed tile of atomics touches 32x the cache
 // lines (residual weight gradient, ~1000 splits: 598 us).
-#ifndef WN_TN_DEEP
-#define WN_TN_DEEP 0   // 1: two chunks in flight per workgroup where both operands are stored as bf16 (see the K loop) -- built in round 6, at the 128-register cap of the 256-column form it spills, at 256 registers (one workgroup per CU) it is level: off -- profiles/r06_tn_loads.txt
-#endif
 template <int WAVES, bool A16, bool B16>
-__global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 && !(B16 && WN_TN_DEEP)) ? 4 : 2)) void wn_bwd_gemm_tn_bf16(WnGemmTnArgs g) {
+__global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : (A16 ? 4 : 2)) void wn_bwd_gemm_tn_bf16(WnGemmTnArgs g) {
     constexpr int T = 128, TB = 32 * WAVES, KC = 32, LD = KC + 8;  // fp32-stored operand: LDS rows [column][KC rows of the chunk] bf16, padded to 80 bytes
     constexpr int RSA = T * 2 + 64, RSB = TB * 2 + 64;             // bf16-stored operand: bytes per row of its row-major image
     constexpr int ASZ = A16 ? KC * RSA / 2 : T * LD, BSZ = B16 ? KC * RSB / 2 : TB * LD;   // shorts per buffer
@@ -1271,7 +1227,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 &&
     // element offset of row m of a map (64-bit), and the wave-uniform origin of this workgroup's rows
     auto row_elem = [&](const WnRowMap& map, unsigned q, unsigned rem) -> long long { return (long long)q * map.batch_stride + (map.t0 + (long long)rem) * map.row_stride; };
     const unsigned q_wg = (unsigned)((unsigned long long)m_begin / (unsigned)g.rows_per_batch), rem_wg = (unsigned)m_begin - q_wg * (unsigned)g.rows_per_batch;
-    auto fetch16 = [&](const WnRowMap& map, int org, int ncols16, auto pprc, int lt, long long mc, int win_lo = 0, int vo = 0) {   // vo: first register of the set (DEEP)
+    auto fetch16 = [&](const WnRowMap& map, int org, int ncols16, auto pprc, int lt, long long mc, int win_lo = 0) {
         constexpr int PPR = decltype(pprc)::value;
         const int row16 = lt / PPR, piece16 = lt % PPR;
         const bool ok16 = org + 8 * piece16 < ncols16;
@@ -1284,7 +1240,7 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 &&
         for (int qq = 0; qq < 4; ++qq) {
             const bool okq = ok16 && m + 8 * qq < m_end && (int)rem >= win_lo;
             const wn_v4i got = __builtin_amdgcn_raw_buffer_load_b128(rs, okq ? off : WN_OOB, 0, 0);   // 8 bf16, moved as bits
-            v[vo + qq] = make_float4(__int_as_float(got.x), __int_as_float(got.y), __int_as_float(got.z), __int_as_float(got.w));
+            v[qq] = make_float4(__int_as_float(got.x), __int_as_float(got.y), __int_as_float(got.z), __int_as_float(got.w));
             rem += 8;
             if (rem >= (unsigned)g.rows_per_batch) {   // the row 8 further down is in a later batch entry
                 do { rem -= (unsigned)g.rows_per_batch; ++q; } while (rem >= (unsigned)g.rows_per_batch);
@@ -1294,17 +1250,17 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 &&
             }
         }
     };
-    auto stash16 = [&](unsigned short* imgs, int rs, auto pprc, int lt, int vo = 0) {
+    auto stash16 = [&](unsigned short* imgs, int rs, auto pprc, int lt) {
         constexpr int PPR = decltype(pprc)::value;
         char* img = reinterpret_cast<char*>(imgs);
 #pragma unroll
-        for (int qq = 0; qq < 4; ++qq) *reinterpret_cast<float4*>(img + (lt / PPR + 8 * qq) * rs + 16 * (lt % PPR)) = v[vo + qq];
+        for (int qq = 0; qq < 4; ++qq) *reinterpret_cast<float4*>(img + (lt / PPR + 8 * qq) * rs + 16 * (lt % PPR)) = v[qq];
     };
-    auto fetch = [&](long long mc, int vo = 0) {
-        if (B16 && is_b) { if (loads) fetch16(g.b, nb0, g.Nb, std::integral_constant<int, TB / 8>{}, tid - 128, mc, 0, vo); return; }
+    auto fetch = [&](long long mc) {
+        if (B16 && is_b) { if (loads) fetch16(g.b, nb0, g.Nb, std::integral_constant<int, TB / 8>{}, tid - 128, mc); return; }
         if (A16 && !is_b) {   // (the two tap views of the filter/gate weight gradient: block-uniform choice, the maps' fields stay scalar)
-            if (second) fetch16(g.a1, ka0 - g.ka_split, g.Ka - g.ka_split, std::integral_constant<int, T / 8>{}, tid, mc, 0, vo);
-            else fetch16(g.a, ka0, g.ka_split > 0 ? g.ka_split : g.Ka, std::integral_constant<int, T / 8>{}, tid, mc, g.a_skip_lo, vo);
+            if (second) fetch16(g.a1, ka0 - g.ka_split, g.Ka - g.ka_split, std::integral_constant<int, T / 8>{}, tid, mc);
+            else fetch16(g.a, ka0, g.ka_split > 0 ? g.ka_split : g.Ka, std::integral_constant<int, T / 8>{}, tid, mc, g.a_skip_lo);
             return;
         }
         long long m = mc + mg * 8;
@@ -1326,10 +1282,10 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 &&
             }
         }
     };
-    auto stash = [&](int buf, int vo = 0) {
+    auto stash = [&](int buf) {
         if (!loads) return;
-        if (B16 && is_b) { stash16(b_s[buf], RSB, std::integral_constant<int, TB / 8>{}, tid - 128, vo); return; }
-        if (A16 && !is_b) { stash16(a_s[buf], RSA, std::integral_constant<int, T / 8>{}, tid, vo); return; }
+        if (B16 && is_b) { stash16(b_s[buf], RSB, std::integral_constant<int, TB / 8>{}, tid - 128); return; }
+        if (A16 && !is_b) { stash16(a_s[buf], RSA, std::integral_constant<int, T / 8>{}, tid); return; }
         unsigned short* dst = (is_b ? b_s[buf] : a_s[buf]) + lcol * LD + mg * 8;
         if (relu) {
 #pragma unroll
@@ -1376,43 +1332,18 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 &&
             }
         }
     };
-    // DEEP (both operands stored as bf16: a loader thread moves four 16-byte pieces per chunk, half of v[]): TWO chunks in flight per workgroup.  Alone on the
-    // chip the one-chunk loop ran the filter/gate weight gradient at 2.5 TB/s -- 3.7 us per 24 KB chunk and workgroup, a load round trip per chunk, where the
-    // layer kernels stream 5 TB/s (profiles/r06_train_step_sq_counters.txt) -- and the step is the sum of its kernels' stand-alone times.  Chunk k + 2 is
-    // requested before the products of chunk k, chunk k + 1 goes from its registers to LDS behind them; the barrier is the LDS-only one (a __syncthreads
-    // would drain the loads in flight).  Loads past the split's last row are predicated off (zeros), so every path issues the same sequence and the
-    // compiler's wait counts stay exact.
-    constexpr bool DEEP = A16 && B16 && WN_TN_DEEP;
-    if constexpr (DEEP) {
-        fetch(m_begin, 0);
-        stash(0, 0);
-        fetch(m_begin + KC, 4);
-        wn_lds_barrier();
-        for (long long mc = m_begin;;) {
-            fetch(mc + 2 * KC, 0);
-            products(0);
-            stash(1, 4);
-            wn_lds_barrier();
-            mc += KC;
-            if (mc >= m_end) break;
-            fetch(mc + 2 * KC, 4);
-            products(1);
-            stash(0, 0);
-            wn_lds_barrier();
-            mc += KC;
-            if (mc >= m_end) break;
-        }
-    } else {
-        fetch(m_begin);
-        stash(0);
+    // ONE chunk in flight per workgroup.  (Two -- chunk k + 2 requested before the products of chunk k, where both operands are stored as bf16 -- spill at the
+    // 128-register cap of the 256-column form and are level at 256 registers, one workgroup per CU: profiles/r06_tn_loads.txt; wn_bwd_wfg_bf16 below is the
+    // form with more bytes in flight.)
+    fetch(m_begin);
+    stash(0);
+    __syncthreads();
+    int buf = 0;
+    for (long long mc = m_begin; mc < m_end; mc += KC, buf ^= 1) {
+        if (mc + KC < m_end) fetch(mc + KC);
+        products(buf);
+        if (mc + KC < m_end) stash(buf ^ 1);
         __syncthreads();
-        int buf = 0;
-        for (long long mc = m_begin; mc < m_end; mc += KC, buf ^= 1) {
-            if (mc + KC < m_end) fetch(mc + KC);
-            products(buf);
-            if (mc + KC < m_end) stash(buf ^ 1);
-            __syncthreads();
-        }
     }
     const int col = lane & 31;
 #pragma unroll
@@ -1422,13 +1353,9 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? WN_TN_BF16_MINB : ((A16 &&
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
             const int nb = nb0 + 128 * wc + 32 * j + col;
-#if WN_ABL_TN_PLAIN_STORE   // timing ablation (results wrong): what the fp32 atomics of the row splits cost
-            if (nb < g.Nb) g.c[g.c_trans ? (size_t)nb * g.ldc + ka : (size_t)ka * g.ldc + nb] = acc[j][i];
-#else
             if (nb >= g.Nb) continue;
             if (g.part) g.part[((size_t)split * g.Ka + ka) * g.Nb + nb] = acc[j][i];
             else unsafeAtomicAdd(g.c + (g.c_trans ? (size_t)nb * g.ldc + ka : (size_t)ka * g.ldc + nb), acc[j][i]);
-#endif
         }
     }
 }
@@ -1597,7 +1524,7 @@ __global__ __launch_bounds__(256) void wn_bwd_gate(const float* dz, const float*
         const unsigned n = (unsigned)m / (unsigned)rows, tt = (unsigned)m - n * (unsigned)rows;
         if ((int)tt >= rows - out_len) {
             const long long off = ((long long)n * out_len + ((int)tt - (rows - out_len))) * ldg + ch;
-            if (PACKED && WN_DZG_BF16) {   // (the bf16 step stores dzg as bf16: `dzg` points at unsigned short, ldg counts bf16 elements)
+            if (PACKED) {   // (the bf16 step stores dzg as bf16: `dzg` points at unsigned short, ldg counts bf16 elements)
                 const uint2 e = *reinterpret_cast<const uint2*>(reinterpret_cast<const unsigned short*>(dzg) + off);
                 d.x += __uint_as_float(e.x << 16); d.y += __uint_as_float(e.x & 0xffff0000u); d.z += __uint_as_float(e.y << 16); d.w += __uint_as_float(e.y & 0xffff0000u);
             } else {

@@ -34,7 +34,7 @@
 // taps are [G][...] in LDS; the tap FIFO is unchanged (every queue wave still issues one tap load per item).  The two streams'
 // dependency chains of a window are written as ONE basic block (unconditional LDS reads, selects, stores after both chains):
 // a lane-predicated store between them makes the compiler emit the second stream's whole chain after the first one's.  In this
-// form a critical lane computes the filter AND the gate row of a channel on half an x slice (WN_V3_PAIR_ROWS).  A trip through a
+// form a critical lane computes the filter AND the gate row of a channel on half an x slice (PAIR in wn_v3_layer).  A trip through a
 // stage is longer (0.10 + 0.37 + 0.26 us against 0.08 + 0.26 + 0.17), which is why few streams keep G = 1.
 //
 // LDS hazards (i = item index; x and the late layers' tap are double buffered, everything else single; W = written in, R = read in):
@@ -55,78 +55,18 @@
 #endif
 #define WN_V3_MIN_STREAMS 1
 #define WN_V3_TAP_AHEAD 6
-#ifndef WN_SAMPLER_PREFETCH
-#define WN_SAMPLER_PREFETCH 2  // the sampler asks for the item's uniform BEFORE it waits for the logits (2; 1: also temperature / given sample -- the
-                               // build whose scalar pressure spilled the input poll's base pointers, see WN_AP_SGPR_HAZARD; 0: everything behind the logits)
-#endif
-#ifndef WN_V3_WIDE_SAMPLER
-#define WN_V3_WIDE_SAMPLER 0  // experiment: head slices from which the samplers of variant 3 collect the logits with four waves (0 = never)
-#endif
 #define WN_V3_COMPILER_VGPRS 152  // v152-v167: request sets of the input poll / the queue group's tap FIFO (see wn_ap_*, wn_q_*)
-// ---- experiment switches.  A product build (build.py) leaves every one of them at its default; setting one requires -DWN_EXPERIMENT,
-// which build.py never passes (tools/ builds the A/B variants): a library with wrong-on-purpose timing ablations cannot ship by accident.
-#if !defined(WN_EXPERIMENT) && (defined(WN_V3_SKIP_DEFER) || defined(WN_V3_QUEUE_DEFER) || defined(WN_V3_SKIP_SLEEP) || defined(WN_V3_ABL) || defined(WN_V3_PAIR_ROWS) || defined(WN_V3_PRIO) || defined(WN_V3_LAST_SKIP_PRIO) || defined(WN_V3_SKIP_CHAINS) || defined(WN_V3_FG_CHAINS) || defined(WN_V3_SKIP_SLOTS) || defined(WN_V3_TAP_AT_A) || defined(WN_V3_FAST_GATE) || defined(WN_V3_KPACK))
-#error "WN_V3_* experiment switches need -DWN_EXPERIMENT"
-#endif
-#ifndef WN_V3_SKIP_DEFER
-#define WN_V3_SKIP_DEFER 0   // two-streams-per-item form: s_sleep count (64 clocks each) at the head of the skip group's chunk behind barrier B (not the last
-                             // layer's: its lanes are the head's input) -- the chunk then runs while the critical waves wait for the next token instead of next
-                             // to their residual dot, the piece of the window that is on the token's path
-#endif
-#ifndef WN_V3_QUEUE_DEFER
-#define WN_V3_QUEUE_DEFER 0  // ... and the same in front of the queue group's chunk behind barrier B (push, tap-0 dot of the next timestep)
-#endif
-#ifndef WN_V3_SKIP_SLEEP
-#define WN_V3_SKIP_SLEEP 0  // s_sleep between the skip group's poll retries (the skip lane is not latency critical; fewer polls on the fabric)
+// ---- the one experiment switch left.  A product build (build.py) leaves it at 0; setting it requires -DWN_EXPERIMENT, which build.py never
+// passes (tools/ablate.sh builds the variants): a library with wrong-on-purpose timing ablations cannot ship by accident.  (The A/B switches of
+// rounds 2-6 are settled and gone: each decision carries its numbers where it is now fixed in the code, the table is in profiles/HISTORY.md,
+// "Retired compile-time switches".)
+#if !defined(WN_EXPERIMENT) && defined(WN_V3_ABL)
+#error "WN_V3_ABL needs -DWN_EXPERIMENT"
 #endif
 #ifndef WN_V3_ABL
 #define WN_V3_ABL 0  // timing ablations (results are WRONG when != 0): 1 the skip group only polls the input and passes its barriers, 2 the queue group, 3 both;
                      // 4: the skip group publishes its own dot WITHOUT the upstream lane (no chain through the layers), 8: the upstream lane is taken as it
                      // comes back from the request at barrier A, fresh or not (no polling)
-#endif
-#ifndef WN_V3_PAIR_ROWS
-#define WN_V3_PAIR_ROWS 2  // a critical lane computes the filter AND the gate row of one channel on a half-width slice of x (see wn_v3_layer):
-                           // 0 never, 1 always, 2 in the two-streams-per-item form only (64 streams: 961 -> 974 k samples/s, 128: 1.464 -> 1.478 M;
-                           // one stream: 18.87 -> 18.74 k -- the longer lane reduction is on the single token's path; profiles/archive/r02_v3_forms_final.txt)
-#endif
-#ifndef WN_V3_LAST_SKIP_PRIO
-#define WN_V3_LAST_SKIP_PRIO 3  // wave priority of the LAST layer's skip group in the two-streams-per-item form (64 streams: 998.6 -> 1004.5 k)
-#endif
-#ifndef WN_V3_SKIP_SLOTS
-#define WN_V3_SKIP_SLOTS 0   // > 0: hand-off slots of a skip lane that stays inside one XCD are re-used per in-flight ITEM instead of one per stream (0: per
-                             // stream), in EVERY kernel (experiment switch).  Correct, cuts the job's L2 <-> fabric traffic, and LOSES 2-6 % where the ring is
-                             // latency bound (cfg3 up to 80 streams; round 4: profiles/r04_skip_lane_slot_reuse_experiment.txt) -- and GAINS 1-6 % where it is
-                             // throughput bound (cfg3 from 96 streams: 128 streams 1.50 -> 1.58 M): the product has it as a FORM of the cfg3 kernel (template
-                             // parameter SK = 4 of wn_generate_kernel_v3m, chosen by the host from 96 streams up: wn_v3_slots_for).  Other shapes lose with it
-                             // at every stream count (cfg2 x 128 -21 %, the train_script shape x 64 -25 %) and have no such form.
-#endif
-#ifndef WN_V3_SKIP_CHAINS
-#define WN_V3_SKIP_CHAINS 1  // independent FMA chains per row pair of the skip group's dot (1: one chain of DC packed FMAs, the arithmetic of rounds 2-3)
-#endif
-#ifndef WN_V3_FG_CHAINS
-#define WN_V3_FG_CHAINS 4    // ... per stream of the critical group's filter/gate dot in the pair-rows form (2: rounds 2-3; 4: 64 streams 1000 -> 1010 k, profiles/r04_fma_chain_experiments.txt)
-#endif
-#ifndef WN_V3_TAP_AT_A
-#define WN_V3_TAP_AT_A 2     // when a late layer's queue waves request the tap of item i + 6: 0 behind their tap-0 dot after barrier B(i) (rounds 2-4), 1 right behind
-                             // barrier A(i), 2 behind A in the two-streams-per-item form only.  The rings of the layers with d >= 64 do not fit the L2 at 64
-                             // streams: such a tap load is a ~1 us miss, and whatever this CU requests behind it -- the critical group's input polls -- is
-                             // answered behind it.  Requested after the dot the miss was in flight when the next token arrived; behind barrier A it has the
-                             // item's whole service time and the wait for the next token to itself (round 5: hop into a layer with d >= 64 0.50 -> 0.35 us,
-                             // 64 streams 1.002 -> 1.069 M samples/s; one stream per item loses 1-3 %: profiles/r05_tap_request_behind_barrier_a.txt)
-#endif
-#ifndef WN_V3_FAST_GATE
-#define WN_V3_FAST_GATE 1    // e^-v of the gated unit as exp2(v * -log2 e) -- three instructions (select, multiply by a per-lane constant, v_exp_f32) instead of
-                             // the eleven of the library-accurate wn_exp; the single rounding of the product moves sigma by <= 1.4e-8 (the bound of variant 4's
-                             // gate, wn_kernel_v4.h).  The filter/gate window of a layer is ISSUE bound (round 5: ~125 instructions of one wave per SIMD in 0.39 us):
-                             // every instruction taken out of it is ~2.5 ns per layer, 0.12 us per timestep of the 64-stream ring.  0: wn_exp as in rounds 2-4
-#endif
-#ifndef WN_V3_KPACK
-#define WN_V3_KPACK 1        // pair-rows form: the packed FMAs pair CONSECUTIVE x elements {x[k], x[k+1]} against {w[k], w[k+1]} of the filter row and of the gate
-                             // row (no broadcast of one x element into both halves: the compiler spent a v_mov per fourth element on those), and the parked tap-0
-                             // sums enter through one FMA with a per-lane 0 / 1 factor behind the dot instead of two selects in front of it.  0: {filter, gate} pairs
-#endif
-#ifndef WN_V3_PRIO
-#define WN_V3_PRIO 1  // 1: critical waves at a higher static wave priority (the queue and skip waves share their SIMDs: x64 911 -> 919 k, profiles/archive/r02_v3_tap_fifo.txt)
 #endif
 
 // ---- 16-byte skip-lane hand-offs.  A lane of the skip group owns rows t and t + 256 of the running skip sum.  Written as two
@@ -149,14 +89,13 @@ static __device__ __forceinline__ void wn_st_pair(__amdgpu_buffer_rsrc_t rs, uns
     else __builtin_amdgcn_raw_buffer_store_b128(d, rs, byte_off, 0, 16);        // write-through
 }
 // spins until both halves of the pair carry `tag` (bounded like wn_poll_fixed)
-static __device__ __forceinline__ wn_v4i wn_poll_pair(WnCtx& cx, __amdgpu_buffer_rsrc_t rs, unsigned byte_off, uint32_t tag, int where, long long e, int s, int sleep = 0) {
+static __device__ __forceinline__ wn_v4i wn_poll_pair(WnCtx& cx, __amdgpu_buffer_rsrc_t rs, unsigned byte_off, uint32_t tag, int where, long long e, int s) {
     wn_v4i v = {0, 0, 0, 0};
     if (cx.fail) return v;
     unsigned spins = 0;
     for (;;) {
         v = wn_ld_pair(rs, byte_off);
         if ((uint32_t)v.y == tag && (uint32_t)v.w == tag) return v;
-        if (sleep > 0) __builtin_amdgcn_s_sleep(WN_V3_SKIP_SLEEP > 0 ? WN_V3_SKIP_SLEEP : 1);
         if ((++spins & 127u) == 0u) {
             if (__hip_atomic_load(cx.p->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { cx.fail = 1; return v; }
             const long long now = (long long)wall_clock64();
@@ -196,9 +135,6 @@ static __device__ __forceinline__ wn_v4i wn_poll_pair(WnCtx& cx, __amdgpu_buffer
 // to this default when the check finds one.  Any other way of compiling this file gets the safe form.
 #ifndef WN_AP_SGPR_HAZARD
 #define WN_AP_SGPR_HAZARD "s_nop 4\n\t"
-#endif
-#ifndef WN_AP_LOOP_ALIGN
-#define WN_AP_LOOP_ALIGN ""   // e.g. ".p2align 6\n\t": the head of the polling loops on an instruction-cache line (filled with s_nop, executed once per entry)
 #endif
 // (addresses: a wave-uniform base per partial in an SGPR pair + ONE 32-bit byte offset per lane -- four 64-bit lane pointers were
 //  eight registers of the polling waves' budget)
@@ -271,7 +207,6 @@ static __device__ __forceinline__ void wn_ap_issue_a1(unsigned off, const wn_u64
         WN_AP_ISSUE4(160, 161, 162, 163, 164, 165, 166, 167)                      \
         "s_sleep 2\n\t"                                                           \
         WN_AP_ISSUE4(152, 153, 154, 155, 156, 157, 158, 159)                      \
-        WN_AP_LOOP_ALIGN                                                          \
         "1:\n\t"                                                                  \
         "s_waitcnt vmcnt(4)\n\t"                                                  \
         WN_AP_CHECK4(160, 161, 162, 163, 164, 165, 166, 167)                      \
@@ -327,7 +262,6 @@ static __device__ __forceinline__ int wn_ap_spin4(unsigned off, const wn_u64* p0
         WN_AP_ISSUE2(160, 161, 162, 163)                                          \
         "s_sleep 2\n\t"                                                           \
         WN_AP_ISSUE2(152, 153, 154, 155)                                          \
-        WN_AP_LOOP_ALIGN                                                          \
         "1:\n\t"                                                                  \
         "s_waitcnt vmcnt(2)\n\t"                                                  \
         WN_AP_CHECK2(160, 161, 162, 163)                                          \
@@ -371,7 +305,6 @@ static __device__ __forceinline__ int wn_ap_spin2(unsigned off, const wn_u64* p0
         "global_load_dwordx2 v[160:161], %[off], %[p0] sc1\n\t"                      \
         "s_sleep 2\n\t"                                                           \
         "global_load_dwordx2 v[152:153], %[off], %[p0] sc1\n\t"                      \
-        WN_AP_LOOP_ALIGN                                                          \
         "1:\n\t"                                                                  \
         "s_waitcnt vmcnt(1)\n\t"                                                  \
         WN_AP_CHECK1(160, 161)                                                    \
@@ -609,34 +542,34 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
     };
     if (group == 0) {
         // ================================================================== critical group
-#if WN_V3_PRIO
+        // critical waves at a higher static wave priority: the queue and skip waves share their SIMDs (64 streams 911 -> 919 k, profiles/archive/r02_v3_tap_fifo.txt)
         __builtin_amdgcn_s_setprio(3);
-#endif
         // Filter/gate lanes.  The register images give lane (row, kq1) the K1 tap-1 weights of ONE filter or gate row on x slice kq1;
         // the 2 DC / T1-lane groups of a wave then read the same x slices from LDS, 8 x 16 bytes per lane and stream -- and the LDS
         // pipe (128 bytes a clock for the whole CU), not the FMA issue, is what the filter/gate window waits for.  A critical lane
         // therefore takes BOTH rows of a channel on HALF a slice: lane (ch8, kq8), 2 T1 lanes per channel, K1 / 2 x values per lane
         // (half the LDS reads per row pair), each feeding one packed FMA {filter, gate}; its weights are those of the images' lanes
-        // (2 ch8, kq8 / 2) and (2 ch8 + 1, kq8 / 2), rows (kq8 & 1) K1/2 ..., gathered here once.
+        // (2 ch8, kq8 / 2) and (2 ch8 + 1, kq8 / 2), rows (kq8 & 1) K1/2 ..., gathered here once.  In the two-streams-per-item form only: 64 streams
+        // 961 -> 974 k samples/s, 128: 1.464 -> 1.478 M; one stream 18.87 -> 18.74 k -- the longer lane reduction is on the single token's path
+        // (profiles/archive/r02_v3_forms_final.txt).
+        // The packed FMAs pair CONSECUTIVE x elements {x[k], x[k+1]} against {w[k], w[k+1]} of the filter row and of the gate row -- pairing {filter, gate}
+        // against one x element broadcast into both halves cost a v_mov per fourth element -- in four chains per stream (two: 64 streams 1000 -> 1010 k,
+        // profiles/r04_fma_chain_experiments.txt), and the parked tap-0 sums enter through one FMA with a per-lane 0 / 1 factor behind the dot instead of
+        // two selects in front of it (profiles/r05_instruction_trims_and_alignment.txt).
         constexpr int T8 = 2 * T1, K8 = K1 / 2;
-        constexpr bool PAIR = WN_V3_PAIR_ROWS == 1 || (WN_V3_PAIR_ROWS == 2 && G >= 2);
+        constexpr bool PAIR = G >= 2;
         static_assert(!PAIR || (K1 % 8 == 0 && T8 <= 16), "half slices are read as float4");
         const int ch8 = t / T8, kq8 = t % T8, half8 = kq8 & 1;
         const int t_f = (2 * ch8) * T1 + kq8 / 2;  // the image lane of the channel's filter row (gate row: + T1)
         float w1[PAIR ? 1 : K1], w2[K2];
         wn_f2 wfg[PAIR ? K8 : 1];
-        constexpr bool KPACK = PAIR && WN_V3_KPACK != 0;
-        if constexpr (KPACK) {   // wfg[2 j] = {w_f[2 j], w_f[2 j + 1]}, wfg[2 j + 1] = {w_g[2 j], w_g[2 j + 1]} of this lane's half slice
+        if constexpr (PAIR) {   // wfg[2 j] = {w_f[2 j], w_f[2 j + 1]}, wfg[2 j + 1] = {w_g[2 j], w_g[2 j + 1]} of this lane's half slice
             const float* imw = p.blobs + (size_t)cx.w * (SH::NWL * 256);
 #pragma unroll
             for (int j = 0; j < K8 / 2; ++j) {
                 wfg[2 * j] = wn_f2{imw[(size_t)(half8 * K8 + 2 * j) * 256 + t_f], imw[(size_t)(half8 * K8 + 2 * j + 1) * 256 + t_f]};
                 wfg[2 * j + 1] = wn_f2{imw[(size_t)(half8 * K8 + 2 * j) * 256 + t_f + T1], imw[(size_t)(half8 * K8 + 2 * j + 1) * 256 + t_f + T1]};
             }
-        } else if constexpr (PAIR) {
-            const float* imw = p.blobs + (size_t)cx.w * (SH::NWL * 256);
-#pragma unroll
-            for (int k = 0; k < K8; ++k) wfg[k] = wn_f2{imw[(size_t)(half8 * K8 + k) * 256 + t_f], imw[(size_t)(half8 * K8 + k) * 256 + t_f + T1]};
         } else {
 #pragma unroll
             for (int k = 0; k < K1; ++k) w1[k] = img[(size_t)k * 256];
@@ -644,7 +577,11 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
 #pragma unroll
         for (int k = 0; k < K2; ++k) w2[k] = img[(size_t)(2 * K1 + k) * 256];
         const float bres = img[(size_t)(2 * K1 + K2 + RS * DC + 1) * 256];
-        // per-lane constants of the gate: the lane with the first half of a slice evaluates the filter factor 2 s(2 f) - 1, its neighbour the gate factor s(g)
+        // per-lane constants of the gate: the lane with the first half of a slice evaluates the filter factor 2 s(2 f) - 1, its neighbour the gate factor s(g).
+        // e^-v as exp2(v * -log2 e): three instructions (select, multiply by the per-lane constant, v_exp_f32) instead of the eleven of a library-accurate
+        // exp; the single rounding of the product moves sigma by <= 1.4e-8 (the bound of variant 4's gate, wn_kernel_v4.h).  The filter/gate window is
+        // ISSUE bound (~125 instructions of one wave per SIMD in 0.39 us): every instruction out of it is ~2.5 ns per layer, 0.12 us per timestep of the
+        // 64-stream ring (profiles/r05_instruction_trims_and_alignment.txt).
         const float gate_c = (PAIR ? half8 : is_gate) ? -1.44269504088896341f : -2.88539008177792681f;   // -log2 e, -2 log2 e
         const float pre_m = half8 ? 0.f : 1.f;   // (the lane that takes the parked tap-0 sums of its slice)
         const float res_m = (c == 0 && kq2 == 0) ? 1.f : 0.f;   // (the lane that adds x[t] to its row of the residual partial: wavenet_model.py:165)
@@ -675,7 +612,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                 float xres[G];   // x[t] of this lane's row: the residual add (slice 0's lane kq2 == 0 adds it: res_m), one FMA behind the residual dot
 #pragma unroll
                 for (int g = 0; g < G; ++g) xres[g] = xb[g * L::XR + SH::xpad(row2)];
-                if constexpr (KPACK) {
+                if constexpr (PAIR) {
                     // lane (ch8, kq8): filter row AND gate row of channel ch8 on half a slice of x, K8 elements: per float4 of x two packed FMAs per row
                     // ({x0, x1} and {x2, x3} against the rows' consecutive weights) -- four chains per stream, the streams interleaved
                     wn_f2 f01[G], f23[G], g01[G], g23[G];
@@ -706,54 +643,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                     for (int g = 0; g < G; ++g) {
                         const wn_f2 fs = f01[g] + f23[g], gs = g01[g] + g23[g];
                         const float f = wn_reduce<T8>(fmaf(pf[g], pre_m, fs.x + fs.y)), gt = wn_reduce<T8>(fmaf(pg[g], pre_m, gs.x + gs.y));
-                        const float rc = __builtin_amdgcn_rcpf(1.0f + (WN_V3_FAST_GATE ? __builtin_amdgcn_exp2f((half8 ? gt : f) * gate_c) : wn_exp(half8 ? -gt : -2.0f * f)));
-                        const float fac = half8 ? rc : fmaf(2.0f, rc, -1.0f);
-                        z[g] = fac * wn_partner<1>(fac);  // (the DPP move outside any lane-dependent branch)
-                    }
-                    if (kq8 == 0) {
-#pragma unroll
-                        for (int g = 0; g < G; ++g) zs[g * L::DCP + ch8] = z[g];
-                    }
-                } else if constexpr (PAIR) {
-                    // the parked tap-0 sums are per image lane (row, kq1): the lane with the first half of slice kq1 takes both rows' sums
-                    wn_f2 a0[G], a1[G], a2[G], a3x[G];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        const float pf = pre[(s + g) * 256 + t_f], pg = pre[(s + g) * 256 + t_f + T1];
-                        a0[g] = half8 ? wn_f2{0.f, 0.f} : wn_f2{pf, pg};
-                        a1[g] = a2[g] = a3x[g] = wn_f2{0.f, 0.f};
-                    }
-                    float4 v[G][K8 / 4];
-                    const float* xsl = xb + (kq8 / 2) * (K1 + 4) + half8 * K8;
-#pragma unroll
-                    for (int g = 0; g < G; ++g)
-#pragma unroll
-                        for (int k = 0; k < K8 / 4; ++k) v[g][k] = reinterpret_cast<const float4*>(xsl + g * L::XR)[k];
-#pragma unroll
-                    for (int k = 0; k < K8 / 4; ++k)
-#pragma unroll
-                        for (int g = 0; g < G; ++g) {  // two (or four) chains of packed {filter, gate} FMAs per stream, the streams interleaved
-                            a0[g] = __builtin_elementwise_fma(wfg[4 * k], wn_f2{v[g][k].x, v[g][k].x}, a0[g]);
-                            a1[g] = __builtin_elementwise_fma(wfg[4 * k + 1], wn_f2{v[g][k].y, v[g][k].y}, a1[g]);
-                            if constexpr (WN_V3_FG_CHAINS == 4) {
-                                a2[g] = __builtin_elementwise_fma(wfg[4 * k + 2], wn_f2{v[g][k].z, v[g][k].z}, a2[g]);
-                                a3x[g] = __builtin_elementwise_fma(wfg[4 * k + 3], wn_f2{v[g][k].w, v[g][k].w}, a3x[g]);
-                            } else {
-                                a0[g] = __builtin_elementwise_fma(wfg[4 * k + 2], wn_f2{v[g][k].z, v[g][k].z}, a0[g]);
-                                a1[g] = __builtin_elementwise_fma(wfg[4 * k + 3], wn_f2{v[g][k].w, v[g][k].w}, a1[g]);
-                            }
-                        }
-                    if constexpr (WN_V3_FG_CHAINS == 4) {
-#pragma unroll
-                        for (int g = 0; g < G; ++g) { a0[g] = a0[g] + a2[g]; a1[g] = a1[g] + a3x[g]; }
-                    }
-                    // tanh(f) * sigmoid(g): even lanes of the channel's group evaluate the filter factor 2 sigmoid(2f) - 1, odd lanes the gate
-                    // factor sigmoid(g) (one exp and one reciprocal per lane), and each takes the other from its neighbour
-                    float z[G];
-#pragma unroll
-                    for (int g = 0; g < G; ++g) {
-                        const float f = wn_reduce<T8>(a0[g].x + a1[g].x), gt = wn_reduce<T8>(a0[g].y + a1[g].y);
-                        const float rc = __builtin_amdgcn_rcpf(1.0f + (WN_V3_FAST_GATE ? __builtin_amdgcn_exp2f((half8 ? gt : f) * gate_c) : wn_exp(half8 ? -gt : -2.0f * f)));
+                        const float rc = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((half8 ? gt : f) * gate_c));
                         const float fac = half8 ? rc : fmaf(2.0f, rc, -1.0f);
                         z[g] = fac * wn_partner<1>(fac);  // (the DPP move outside any lane-dependent branch)
                     }
@@ -773,7 +663,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                     // product is the same two numbers multiplied: bit-identical
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
-                        const float rc = __builtin_amdgcn_rcpf(1.0f + (WN_V3_FAST_GATE ? __builtin_amdgcn_exp2f(acc[g] * gate_c) : wn_exp(is_gate ? -acc[g] : -2.0f * acc[g])));
+                        const float rc = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(acc[g] * gate_c));
                         const float fac = is_gate ? rc : fmaf(2.0f, rc, -1.0f);
                         const float z = fac * wn_partner<T1>(fac);  // (the DPP move outside any lane-dependent branch)
                         if (!is_gate && kq1 == 0) zs[g * L::DCP + ch] = z;
@@ -825,11 +715,10 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
 
     if (group == 1) {
         // ================================================================== skip group
-#if WN_V3_LAST_SKIP_PRIO
         // the LAST layer's skip lanes are the head's input -- the one place where this group is on the token's critical path (and the
-        // critical group of that layer has nothing to do after barrier B: it publishes no x')
-        if (G >= 2 && l == NL - 1) __builtin_amdgcn_s_setprio(WN_V3_LAST_SKIP_PRIO);
-#endif
+        // critical group of that layer has nothing to do after barrier B: it publishes no x'): wave priority 3 in the two-streams-per-item form,
+        // 64 streams 998.6 -> 1004.5 k (round 3: profiles/HISTORY.md)
+        if (G >= 2 && l == NL - 1) __builtin_amdgcn_s_setprio(3);
         // A lane owns the rows t + 256 q (q < RS) of this slice's lane of the running skip sum.  Rows 2h and 2h+1 of a lane sit side by
         // side: one packed FMA (v_pk_fma_f32) per z element and row pair, one 16-byte hand-off {v(t + 512 h), tag, v(t + 512 h + 256), tag} at
         // byte 4096 h + 16 t of the lane.  An odd RS (S = 256: one row per lane) leaves a last row without a partner in its lane: its dot runs
@@ -867,14 +756,15 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
         // of the reader's own lane of item i - NSLOT before it stores (requested a window ahead, next to the upstream request: normally fresh).
         // Tags of re-used slots count items (item + 1), the others evaluations (e + 1) as before.  The last layer's lanes (read by the head
         // replicas, which publish no lane) and every lane that crosses an XCD boundary keep one slot per stream.
-#ifndef WN_V3_SLOT_DEBUG
-#define WN_V3_SLOT_DEBUG 0   // timing experiments (-DWN_EXPERIMENT): 1 = re-used slots WITHOUT the back-pressure look (unsafe), 2 = the look without re-use
-#endif
-        constexpr int NSLOT_C = SK > 0 ? SK : WN_V3_SKIP_SLOTS;   // (SK: the form the host picks for cfg3 from 96 streams up, wn_v3_slots_for)
+        // A FORM of the kernel (SK = 4), not the rule: re-use cuts the job's L2 <-> fabric traffic and LOSES 2-6 % where the ring is latency bound (cfg3 up
+        // to 80 streams), GAINS 1-6 % where it is throughput bound (cfg3 x 128: 1.50 -> 1.58 M) -- the host picks it for cfg3 from 96 streams up
+        // (wn_v3_slots_for); other shapes lose with it at every stream count (cfg2 x 128 -21 %) and have no such form
+        // (profiles/r04_skip_lane_slot_reuse_experiment.txt, r05_skip_lane_slots_by_stream_count.txt).
+        constexpr int NSLOT_C = SK;
         const int NSLOT = NSLOT_C > 0 && NSLOT_C * G <= ns ? NSLOT_C : 0;
-        const bool slot_look = NSLOT > 0 && l < NL - 1 && local_s && WN_V3_SLOT_DEBUG != 1;
-        const bool slot_out = NSLOT > 0 && l < NL - 1 && local_s && WN_V3_SLOT_DEBUG != 2;                 // my lane: re-used slots
-        const bool slot_in = NSLOT > 0 && l > 0 && locflags[2] != 0 && WN_V3_SLOT_DEBUG != 2;              // the upstream's lane (its slot_out: the same relation seen from the other side)
+        const bool slot_look = NSLOT > 0 && (l < NL - 1 && local_s);   // (this grouping: the flat one makes the compiler order the SK = 4 kernel differently, +15 instructions)
+        const bool slot_out = NSLOT > 0 && l < NL - 1 && local_s;                 // my lane: re-used slots
+        const bool slot_in = NSLOT > 0 && l > 0 && locflags[2] != 0;              // the upstream's lane (its slot_out: the same relation seen from the other side)
         const bool slot_cons = NSLOT > 0 && l < NL - 2 && locflags[3] != 0;       // the reader's OWN lane (where its progress is visible)
         const size_t cons_wg = (size_t)(l < NL - 1 ? l + 1 : l) * P + c;
         int slot = 0;   // item mod NSLOT
@@ -910,7 +800,6 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             const uint32_t tag = (uint32_t)(e + 1);
             for (int s = 0; s < ns; s += G, ++item) {
                 if (wn_barrier_failed(cx, failflag)) return;  // ---- B(i): z of this item staged
-                if (WN_V3_SKIP_DEFER > 0 && G >= 2 && l < NL - 1) __builtin_amdgcn_s_sleep(WN_V3_SKIP_DEFER);
                 const bool stamp = r.prof && item < r.prof_items && tid == 256;
                 const long long t0 = stamp ? (long long)wall_clock64() : 0;
                 const int s2 = s + G < ns ? s + G : 0;  // the coming item's first stream
@@ -926,17 +815,15 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                     for (int q = 0; q < RS; ++q) a3[g][q] = 0.f;
                 const bool work = !prime && !(WN_V3_ABL & 1);
                 if (work) {
-                    // per row: bias, then + w[k] z[k] for k = 0..DC-1 in order (one fused multiply-add each), as before the packing
-                    constexpr int SC = WN_V3_SKIP_CHAINS;
-                    static_assert(SC == 1 || SC == 2 || SC == 4, "chains per row pair");
-                    wn_f2 a3c[G][NPL > 0 ? NPL : 1][SC], a3o[G];
+                    // per row: bias, then + w[k] z[k] for k = 0..DC-1 in order (one fused multiply-add each), as before the packing: ONE chain of DC
+                    // packed FMAs per row pair (two independent chains are level, four lose ~1 % -- more live accumulators in a 152-register budget --, and
+                    // either changes the sums: profiles/r04_fma_chain_experiments.txt)
+                    wn_f2 a3c[G][NPL > 0 ? NPL : 1], a3o[G];
 #pragma unroll
                     for (int g = 0; g < G; ++g) {
 #pragma unroll
                         for (int h2 = 0; h2 < NPL; ++h2) {
-                            a3c[g][h2][0] = wn_f2{bskip[2 * h2], bskip[2 * h2 + 1]};
-#pragma unroll
-                            for (int c2 = 1; c2 < SC; ++c2) a3c[g][h2][c2] = wn_f2{0.f, 0.f};
+                            a3c[g][h2] = wn_f2{bskip[2 * h2], bskip[2 * h2 + 1]};
                         }
                         a3o[g] = wn_f2{ODD ? bskip[RS - 1] : 0.f, 0.f};
                     }
@@ -950,11 +837,11 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
 #pragma unroll
                         for (int g = 0; g < G; ++g) {  // (the streams' chains interleaved in program order)
 #pragma unroll
-                            for (int h2 = 0; h2 < NPL; ++h2) {   // (chain j takes the z elements 4 k + j', j' = j mod SC)
-                                a3c[g][h2][0] = __builtin_elementwise_fma(w3p[h2][4 * k], wn_f2{z4[g][k].x, z4[g][k].x}, a3c[g][h2][0]);
-                                a3c[g][h2][1 % SC] = __builtin_elementwise_fma(w3p[h2][4 * k + 1], wn_f2{z4[g][k].y, z4[g][k].y}, a3c[g][h2][1 % SC]);
-                                a3c[g][h2][2 % SC] = __builtin_elementwise_fma(w3p[h2][4 * k + 2], wn_f2{z4[g][k].z, z4[g][k].z}, a3c[g][h2][2 % SC]);
-                                a3c[g][h2][3 % SC] = __builtin_elementwise_fma(w3p[h2][4 * k + 3], wn_f2{z4[g][k].w, z4[g][k].w}, a3c[g][h2][3 % SC]);
+                            for (int h2 = 0; h2 < NPL; ++h2) {
+                                a3c[g][h2] = __builtin_elementwise_fma(w3p[h2][4 * k], wn_f2{z4[g][k].x, z4[g][k].x}, a3c[g][h2]);
+                                a3c[g][h2] = __builtin_elementwise_fma(w3p[h2][4 * k + 1], wn_f2{z4[g][k].y, z4[g][k].y}, a3c[g][h2]);
+                                a3c[g][h2] = __builtin_elementwise_fma(w3p[h2][4 * k + 2], wn_f2{z4[g][k].z, z4[g][k].z}, a3c[g][h2]);
+                                a3c[g][h2] = __builtin_elementwise_fma(w3p[h2][4 * k + 3], wn_f2{z4[g][k].w, z4[g][k].w}, a3c[g][h2]);
                             }
                             if constexpr (ODD) {
                                 a3o[g] = __builtin_elementwise_fma(w3o[2 * k], wn_f2{z4[g][k].x, z4[g][k].y}, a3o[g]);
@@ -966,10 +853,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                     for (int g = 0; g < G; ++g) {
 #pragma unroll
                         for (int h2 = 0; h2 < NPL; ++h2) {
-                            wn_f2 v = a3c[g][h2][0];
-                            if constexpr (SC == 2) v = v + a3c[g][h2][1];
-                            if constexpr (SC == 4) v = (v + a3c[g][h2][1]) + (a3c[g][h2][2] + a3c[g][h2][3]);
-                            a3[g][2 * h2] = v.x; a3[g][2 * h2 + 1] = v.y;
+                            a3[g][2 * h2] = a3c[g][h2].x; a3[g][2 * h2 + 1] = a3c[g][h2].y;
                         }
                         if constexpr (ODD) a3[g][RS - 1] = a3o[g].x + a3o[g].y;
                     }
@@ -979,13 +863,13 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
 #pragma unroll
                             for (int h2 = 0; h2 < NPL; ++h2) {
                                 wn_v4i v = sk_req[g][h2];   // (only ever this item's streams: re-requested after every barrier A)
-                                if (!(WN_V3_ABL & 8) && ((uint32_t)v.y != tag_in || (uint32_t)v.w != tag_in)) v = wn_poll_pair(cx, rs_gs, base_up + g * SB + h2 * 4096 + lane16, tag_in, WN_W_SKIN, e, s + g, WN_V3_SKIP_SLEEP);
+                                if (!(WN_V3_ABL & 8) && ((uint32_t)v.y != tag_in || (uint32_t)v.w != tag_in)) v = wn_poll_pair(cx, rs_gs, base_up + g * SB + h2 * 4096 + lane16, tag_in, WN_W_SKIN, e, s + g);
                                 a3[g][2 * h2] += __int_as_float(v.x);
                                 a3[g][2 * h2 + 1] += __int_as_float(v.z);
                             }
                             if constexpr (ODD) {  // (both halves of the pair come from ONE store of the upstream's even lane)
                                 wn_v4i v = sk_req[g][NPL];
-                                if ((uint32_t)v.y != tag_in || (uint32_t)v.w != tag_in) v = wn_poll_pair(cx, rs_gs, base_up + g * SB + odd_ld, tag_in, WN_W_SKIN, e, s + g, WN_V3_SKIP_SLEEP);
+                                if ((uint32_t)v.y != tag_in || (uint32_t)v.w != tag_in) v = wn_poll_pair(cx, rs_gs, base_up + g * SB + odd_ld, tag_in, WN_W_SKIN, e, s + g);
                                 a3[g][RS - 1] += __int_as_float((t & 1) ? v.z : v.x);
                             }
                         }
@@ -998,7 +882,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                         const int sj = s - NSLOT * G < 0 ? s - NSLOT * G + ns : s - NSLOT * G;
                         const long long ej = s - NSLOT * G < 0 ? e - 1 : e;
                         if (ej >= n_prime && ej >= 0) {
-                            const uint32_t want = WN_V3_SLOT_DEBUG == 2 ? 0u : slot_cons ? (uint32_t)(item - NSLOT + 1) : (uint32_t)(ej + 1);
+                            const uint32_t want = slot_cons ? (uint32_t)(item - NSLOT + 1) : (uint32_t)(ej + 1);
                             wn_v4i v = ck_req;
                             unsigned spins = 0;
                             while ((int32_t)((uint32_t)v.y - want) < 0 && !cx.fail) {   // (bounded like wn_poll_pair)
@@ -1039,7 +923,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
     // dot is its longest piece (128 streams: its 0.76 us after barrier B set the pace).  The lane pair of a slice adds its halves (one
     // DPP move) and the even lane parks both rows' sums where the image lanes' sums go: pre[] keeps its layout.
     constexpr int QT8 = 2 * T1, QK8 = K1 / 2;
-    constexpr bool QPAIR = (WN_V3_PAIR_ROWS == 1 || (WN_V3_PAIR_ROWS == 2 && G >= 2)) && K1 % 8 == 0 && QT8 <= 16;
+    constexpr bool QPAIR = G >= 2 && K1 % 8 == 0 && QT8 <= 16;
     const int qch8 = t / QT8, qkq8 = t % QT8, qhalf8 = qkq8 & 1;
     const int qt_f = (2 * qch8) * T1 + qkq8 / 2;  // the image lane of the channel's filter row (gate row: + T1)
     float w0[QPAIR ? 1 : K1];
@@ -1181,7 +1065,12 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
     constexpr int D = WN_V3_TAP_AHEAD;
     const int xq = tg * L::XR + SH::xpad(tr);  // this lane's element in a [G][XR] staging area
     if (late && n_items > 0) xol[xq] = wn_q_take_slot<D - 1>(0);  // item 0's tap (D - 1 younger loads of the initial fill)
-    constexpr bool TAP_A = WN_V3_TAP_AT_A == 1 || (WN_V3_TAP_AT_A == 2 && G >= 2);   // the tap request behind barrier A (see WN_V3_TAP_AT_A)
+    // Two-streams-per-item form: a late layer's queue waves request the tap of item i + 6 right behind barrier A(i), not behind their tap-0 dot after B(i).
+    // The rings of the layers with d >= 64 do not fit the L2 at 64 streams: such a load is a ~1 us miss, and whatever this CU requests behind it -- the
+    // critical group's input polls -- is answered behind it.  Behind A it has the item's whole service time and the wait for the next token to itself
+    // (hop into a layer with d >= 64 0.50 -> 0.35 us, 64 streams 1.002 -> 1.069 M samples/s; one stream per item loses 1-3 % and keeps the request
+    // behind the dot: profiles/r05_tap_request_behind_barrier_a.txt)
+    constexpr bool TAP_A = G >= 2;
     const float* q_next = (TAP_A && late) ? next_tap_ptr() : nullptr;   // address of the tap of item D (requested behind barrier A of item 0)
     // ... and the push of a late layer is done by the waves that load no taps (lanes R..2R-1, when there are that many): the tap
     // waves then issue nothing but tap loads, and an entry always has exactly D - 1 younger operations
@@ -1219,7 +1108,6 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                 hx[0] = xv;
             }
             if (wn_barrier_failed(cx, failflag)) return;  // ---- B(i): the tap is staged
-            if (WN_V3_QUEUE_DEFER > 0 && G >= 2) __builtin_amdgcn_s_sleep(WN_V3_QUEUE_DEFER);
             const long long t1 = stamp ? (long long)wall_clock64() : 0;
             // ---- tap-0 half of the dilated conv for the NEXT timestep of this stream, parked for the critical group
             if (!(WN_V3_ABL & 2)) {
@@ -1603,6 +1491,7 @@ static __device__ __forceinline__ void wn_poll_class(WnCtx& cx, __amdgpu_buffer_
 // WIDE (many head slices, a single stream's ring: 16 slices are 32 KB of granules per token -- one wave needs ~0.6 us per look at them):
 // the caller lets the workgroup's first FOUR waves in, thread c collects class c from every slice (8-byte loads, 16 in flight), the
 // sums meet in LDS (lds_lg, 256 floats) and wave 0 draws as in the one-wave form -- same sums in the same order, two LDS barriers more.
+// (Variant 4 takes WIDE from eight head slices up, wn_kernel_v4.h; in variant 3 it was level and is not used: profiles/r04_sampler_prefetch_and_wide_sampler.txt.)
 template <class SH, bool WIDE = false>
 static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds_smp, float* lds_tab, int j, float* lds_lg = nullptr) {
     constexpr int R = SH::R, NP = (R / 2 + 63) / 64;  // pairs of row elements per lane
@@ -1640,18 +1529,12 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
             // The item's uniform (streamed from HBM, eight bytes per item) is requested BEFORE the wait for the logits: a global load behind
             // their arrival sat on the ring (a single stream's timestep is 8 - 20 us, an HBM miss is half a microsecond of it).  The
             // temperature and the given sample (kernel argument / L2 hits) stay behind the wait -- asking for them early as well raised
-            // the kernels' scalar pressure to where the input poll's base pointers were spilled (WN_AP_SGPR_HAZARD).
+            // the kernels' scalar pressure to where the input poll's base pointers were spilled (WN_AP_SGPR_HAZARD;
+            // profiles/r04_sampler_prefetch_and_wide_sampler.txt).
             // (+ lane0: 0 for every lane of this wave, unknown to the compiler -- vector loads into VGPRs; as scalar loads the values sit in
             //  SGPRs across the poll, and the kernel's scalar registers are already spilling into VGPR lanes)
             const long long g = e - r.n_given;
-#if WN_SAMPLER_PREFETCH == 1
-            const float temp = r.stream_temps ? r.stream_temps[s + lane0] : r.temperature;
-            const bool greedy = r.greedy != 0 || !(temp > 0.f);
-            const double u = (g >= 0 && !greedy) ? r.uniforms[(size_t)s * r.num_samples + g + lane0] : 0.;
-            const int given = g < 0 ? r.first[(size_t)s * r.n_given + e + lane0] : 0;
-#elif WN_SAMPLER_PREFETCH == 2   // only the uniform (the one that streams from HBM), taken whatever the temperature says: r.uniforms != NULL is all it needs
-            const double u = (g >= 0 && r.uniforms) ? r.uniforms[(size_t)s * r.num_samples + g + lane0] : 0.;
-#endif
+            const double u = (g >= 0 && r.uniforms) ? r.uniforms[(size_t)s * r.num_samples + g + lane0] : 0.;   // (taken whatever the temperature says)
             float logit[4] = {0.f, 0.f, 0.f, 0.f};
             if constexpr (WIDE) {   // class threadIdx.x: the PA partial logits summed in the order h = 0 .. PA-1, then four classes per lane of wave 0
                 float mine1 = 0.f;
@@ -1679,16 +1562,9 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
                 if (cx.fail) return;
             }
             wn_stamp(r, park, item, 1);
-#if WN_SAMPLER_PREFETCH == 0   // (A/B switch: the loads behind the logits' arrival, as before round 4)
-            const float temp = r.stream_temps ? r.stream_temps[s + lane0] : r.temperature;
-            const bool greedy = r.greedy != 0 || !(temp > 0.f);
-            const double u = (g >= 0 && !greedy) ? r.uniforms[(size_t)s * r.num_samples + g + lane0] : 0.;
-            const int given = g < 0 ? r.first[(size_t)s * r.n_given + e + lane0] : 0;
-#elif WN_SAMPLER_PREFETCH == 2
             const float temp = r.stream_temps ? r.stream_temps[s + lane0] : r.temperature;
             const bool greedy = r.greedy != 0 || !(temp > 0.f);
             const int given = g < 0 ? r.first[(size_t)s * r.n_given + e + lane0] : 0;
-#endif
             int idx;
             if (g < 0) {
                 idx = given;
@@ -1741,10 +1617,6 @@ void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
     }
     if (threadIdx.x >= WN_THREADS) return;  // the head role is a 256-thread role, the sampler role a one-wave role
     if (w < n_layer_wg + p.PA * p.HR) wn_v3_head<SH, P>(p, r, cx, wn_lds3m, w - n_layer_wg);
-#if WN_V3_WIDE_SAMPLER
-    else if (p.PA >= WN_V3_WIDE_SAMPLER)
-        wn_v3_sampler<SH, true>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR, wn_lds3m + WnV3Lds<SH, 1>::sk);
-#endif
     else if (threadIdx.x < 64) wn_v3_sampler<SH>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
 }
 

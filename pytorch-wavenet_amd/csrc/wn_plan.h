@@ -299,9 +299,7 @@ static inline void wn_pack_blobs(const WnPlan& pl, const WnHostWeights& w, std::
 // The throughput form pays once the ring holds more tokens than it has stages (one stream per item then runs into the stages' cycle):
 // from n_layers + WN_V3_G2_MARGIN streams -- cfg3 (50 layers): 56 streams (895 k against 887 k samples/s; 48: 783 k against 800 k);
 // cfg2 (30 layers): 36 (32 streams: 999 k against 956 k, 64: 1.53 M against 0.96 M); cfg1 (10 layers): 16.
-#ifndef WN_V3_G2_MARGIN
 #define WN_V3_G2_MARGIN 6
-#endif
 #define WN_V3_ROUND_STREAMS 128   // streams per round when a job exceeds what one chain holds (wn_handle::rounds)
 // bit 0: two streams per pipeline item of a layer workgroup (needs an even stream count); bit 1: two replicas of the head
 // workgroups.  `pin`: the WN_V3_MODE environment override ("0".."3"), or NULL.
@@ -312,7 +310,7 @@ static inline int wn_v3_mode_for(int n_streams, const char* pin, int n_layers = 
     if (n_streams < 2) mode = 0;
     return mode;
 }
-// Skip-lane slot re-use (wn_kernel_v3.h, WN_V3_SKIP_SLOTS): a form of the two-streams-per-item kernel of shapes that have it (`has_form`: cfg3's), taken
+// Skip-lane slot re-use (wn_kernel_v3.h, the skip group's NSLOT): a form of the two-streams-per-item kernel of shapes that have it (`has_form`: cfg3's), taken
 // where the chain is throughput bound -- measured crossover on cfg3 (50 layers): 80 streams -2 %, 96 +1 %, 112 +4 %, 128 +6 %, 150 +2.5 %
 // (profiles/r05_skip_lane_slots_by_stream_count.txt).  `pin`: the WN_V3_SLOTS environment override ("0" / "4"), or NULL.  Returns the slot count (0 = off).
 static inline int wn_v3_slots_for(int n_streams, int mode, bool has_form, const char* pin, int n_layers = 50) {

@@ -204,9 +204,6 @@ static void wn_launch_cvt_t(hipStream_t st, const float* in, long long in_batch_
                        in, in_batch_stride, out, rows, cols);
 }
 
-#ifndef WN_TN_MERGE_TAPS
-#define WN_TN_MERGE_TAPS 1
-#endif
 // Deterministic mode (wn_train_set_deterministic / WN_DETERMINISTIC=1): the row splits of a weight-gradient product and the row blocks of a bias
 // gradient store their partial results in a workspace -- one per stream the backward uses: the two run side by side -- and a second kernel adds them
 // in order.  Bit-equal gradients from run to run for the price of one write and one read of the partial tiles (at most 67 MB per product).
@@ -554,8 +551,8 @@ extern "C" int wn_train_backward(wn_handle* h, const float* params, const float*
     // dzg_b to dz on the skip rows.  Both products only need dskip: all blocks are enqueued NOW on the side stream, last block first --
     // the chain waits 1.2 ms for the last block's dzg (as it always did) and finds the others ready (one dzg buffer per block).
     std::vector<hipEvent_t> dzg_ready(t.nblk, nullptr);
-    // bf16 step: dzg is STORED as bf16 (WN_DZG_BF16, wn_forward.h) -- element (block b, row, column) of the buffer, as a float pointer the row maps carry
-    const bool dzg16 = t.bf16 && WN_DZG_BF16;
+    // bf16 step: dzg is STORED as bf16 (wn_gemm_epilogue, wn_forward.h) -- element (block b, row, column) of the buffer, as a float pointer the row maps carry
+    const bool dzg16 = t.bf16;
     auto dzg_at = [&](int b, size_t col) -> float* {
         const size_t e = (size_t)b * ((size_t)Mo * t.G * D) + col;
         return dzg16 ? reinterpret_cast<float*>(reinterpret_cast<unsigned short*>(ws + t.dzg) + e) : ws + t.dzg + e;
@@ -602,7 +599,7 @@ extern "C" int wn_train_backward(wn_handle* h, const float* params, const float*
         WnGemmArgs g = wn_nn(wn_rows(dx_in, L, R, L - rows_k), R, ws + t.res_o + (size_t)k * R * D, D, nullptr, wn_rows(ws + ((k & 1) ? t.dfg2 : t.dfg), rows_k, 2 * D),
                              N * rows_k, rows_k);
         g.c_bf16 = t.bf16 ? 1 : 0;
-        g.c2 = wn_rows(dzg_at(k / t.G, (size_t)(k % t.G) * D), out_len, (long long)cnt_k * D);   // (bf16 step: bf16 elements, WN_DZG_BF16)
+        g.c2 = wn_rows(dzg_at(k / t.G, (size_t)(k % t.G) * D), out_len, (long long)cnt_k * D);   // (bf16 step: bf16 elements)
         g.c2_first_row = (int)(rows_k - out_len);
         g.gate_t = ws + t.th[k]; g.gate_g = ws + t.sg[k]; g.gate_packed = t.bf16 ? 1 : 0;
         return g;
@@ -638,7 +635,8 @@ extern "C" int wn_train_backward(wn_handle* h, const float* params, const float*
         }
         ts.wait_for(sd, ts.signal(st));   // [dF|dG] of this layer is complete
         // dWfg^T [2R][2D]: rows 0..R-1 = x_l(t - d)^T . dfg (tap 0), rows R.. = x_l(t)^T . dfg (tap 1) -- one launch, the taps are two
-        // row views of A (ka_split): the workgroups of the two taps run side by side and read the same rows of dfg.
+        // row views of A (ka_split): the workgroups of the two taps run side by side and read the same rows of dfg (worth 5 ms of the round-3 step against a
+        // launch per tap: profiles/archive/r03_train_step_gate_epilogue_merged_taps.txt; shapes whose R is no multiple of the tile keep the two launches).
         const bool shadow = t.bf16 && !t.xh.empty();   // (the bf16 shadow of x: both operands of this product are stored as bf16 then)
         const float* xop = shadow ? ws + t.xh[l] : xin;
         const WnRowMap dfg_map = wn_rows(dfg, rows, 2 * D);
@@ -646,11 +644,9 @@ extern "C" int wn_train_backward(wn_handle* h, const float* params, const float*
         g.a1 = wn_rows(xop, L, R, t0); g.ka_split = R;
         g.a_bf16 = shadow ? 1 : 0; g.b_bf16 = t.bf16 ? 1 : 0;
         g.a_skip_lo = (int)t.zlo[l];   // tap 0 on the rows where the forward read a pad zero: no contribution
-#if WN_TN_MERGE_TAPS
         if (R % 128 == 0) {
             wn_launch_tn(sd, g, t.bf16);
         } else
-#endif
         for (int tap = 0; tap < 2; ++tap) {
             WnGemmTnArgs g1 = g;
             g1.a = tap ? g.a1 : g.a; g1.ka_split = 0; g1.Ka = R; g1.c = g.c + (size_t)tap * R * 2 * D;

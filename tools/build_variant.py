@@ -1,7 +1,7 @@
 """dev tool: build an A/B variant of the engine into tools/variants/libwn_<name>.so with the product's own recipe (fast poll form first,
 the disassembly check decides; see build.py) plus -DWN_EXPERIMENT and the given -D flags.
 
-    python tools/build_variant.py tapA -DWN_V3_TAP_AT_A=1
+    python tools/build_variant.py noskip -DWN_V3_ABL=1
 """
 import os
 import subprocess
