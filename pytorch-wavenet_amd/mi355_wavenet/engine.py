@@ -9,31 +9,7 @@ import ctypes
 
 import numpy as np
 
-from . import _abi
-
-
-def stack_state(cfg, weights):
-    """name -> array (reference Conv1d layout) -> dict of the 14 stacked fp32 host arrays of wn_weight_ptrs."""
-    nl = cfg["layers"] * cfg["blocks"]
-    bias = bool(cfg.get("bias", False))
-
-    def arr(x):
-        if hasattr(x, "detach"):
-            x = x.detach().cpu().numpy()
-        return np.ascontiguousarray(np.asarray(x), dtype=np.float32)
-
-    def cat(fmt):
-        return np.ascontiguousarray(np.stack([arr(weights[fmt % i]) for i in range(nl)]))
-
-    return {
-        "start_w": arr(weights["start_conv.weight"]), "start_b": arr(weights["start_conv.bias"]) if bias else None,
-        "filter_w": cat("filter_convs.%d.weight"), "filter_b": cat("filter_convs.%d.bias") if bias else None,
-        "gate_w": cat("gate_convs.%d.weight"), "gate_b": cat("gate_convs.%d.bias") if bias else None,
-        "res_w": cat("residual_convs.%d.weight"), "res_b": cat("residual_convs.%d.bias") if bias else None,
-        "skip_w": cat("skip_convs.%d.weight"), "skip_b": cat("skip_convs.%d.bias") if bias else None,
-        "end1_w": arr(weights["end_conv_1.weight"]), "end1_b": arr(weights["end_conv_1.bias"]),
-        "end2_w": arr(weights["end_conv_2.weight"]), "end2_b": arr(weights["end_conv_2.bias"]),
-    }
+from . import _abi, params
 
 
 def regularizer_array(classes, regularize):
@@ -115,8 +91,8 @@ class Engine:
 
     # -- ABI calls
     def load_weights(self, weights):
-        st = stack_state(self.cfg, weights)
-        w = _abi.wn_weight_ptrs(*[st[n].ctypes.data if st[n] is not None else None for n in _abi.WEIGHT_FIELDS])
+        st = params.stacked(weights, self.cfg)   # (host arrays, alive until wn_load_weights has copied them)
+        w = _abi.wn_weight_ptrs(*[st[n].ctypes.data if n in st else None for n in _abi.WEIGHT_FIELDS])
         self.lib.check(self.lib.dll.wn_load_weights(self._h, ctypes.byref(w)))
 
     def info(self):

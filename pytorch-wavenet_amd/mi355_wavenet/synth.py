@@ -14,6 +14,8 @@ from collections import OrderedDict
 
 import numpy as np
 
+from . import params
+
 # BASELINE.json configs: name -> ctor kwargs
 CONFIGS = {
     "cfg1": dict(layers=5, blocks=2, dilation_channels=32, residual_channels=32, skip_channels=256,
@@ -51,37 +53,9 @@ def receptive_field(cfg):
 
 
 def param_shapes(cfg):
-    """OrderedDict name -> shape, in the reference's ``state_dict`` naming."""
+    """OrderedDict name -> shape, in the reference's ``state_dict`` naming and order."""
     c = full_config(**cfg)
-    R, D, S, E, C, k = (c["residual_channels"], c["dilation_channels"], c["skip_channels"],
-                        c["end_channels"], c["classes"], c["kernel_size"])
-    shapes = OrderedDict()
-    nl = c["layers"] * c["blocks"]
-    # registration order of the reference ctor: ModuleLists first, then start_conv, end convs
-    for i in range(nl):
-        shapes["filter_convs.%d.weight" % i] = (D, R, k)
-        if c["bias"]:
-            shapes["filter_convs.%d.bias" % i] = (D,)
-    for i in range(nl):
-        shapes["gate_convs.%d.weight" % i] = (D, R, k)
-        if c["bias"]:
-            shapes["gate_convs.%d.bias" % i] = (D,)
-    for i in range(nl):
-        shapes["residual_convs.%d.weight" % i] = (R, D, 1)
-        if c["bias"]:
-            shapes["residual_convs.%d.bias" % i] = (R,)
-    for i in range(nl):
-        shapes["skip_convs.%d.weight" % i] = (S, D, 1)
-        if c["bias"]:
-            shapes["skip_convs.%d.bias" % i] = (S,)
-    shapes["start_conv.weight"] = (R, C, 1)
-    if c["bias"]:
-        shapes["start_conv.bias"] = (R,)
-    shapes["end_conv_1.weight"] = (E, S, 1)
-    shapes["end_conv_1.bias"] = (E,)
-    shapes["end_conv_2.weight"] = (C, E, 1)
-    shapes["end_conv_2.bias"] = (C,)
-    return shapes
+    return OrderedDict((name, params.shape(key, c)) for name, key in params.entries(c))
 
 
 def init_weights(cfg, seed=0, gain=1.0, bias_std=0.1):

@@ -14,77 +14,24 @@ import ctypes
 
 import torch
 
-from . import _abi
+from . import _abi, params
+from .params import PARAM_ORDER, SINGLE_KEYS  # noqa: F401  (read by the tests and tools/)
 
 
-class StackRunner:
-    """Owns one engine handle (for the plan / layout / workspace) and runs the packed forward / backward."""
+class StackLayout:
+    """The flat GEMM layout of wn_train_layout for one channel shape, and the reference Conv1d layouts <-> it in torch ops: needs no engine."""
 
-    def __init__(self, engine, model_shape=None):
-        """model_shape: (R, D, S, E) of the MODEL when the engine was created for a zero-padded channel shape (wavenet_model.py:
-        _native_train_forward pads channel counts that are not multiples of 32 up to multiples of 64): the parameters then travel through
-        zero-filled tensors of the engine's shape (pad_tensors) and only their own block of the gradients comes back (crop_grads)."""
-        self.eng = engine
-        lay = _abi.wn_train_layout()
-        engine.lib.check(engine.lib.dll.wn_train_get_layout(engine._h, ctypes.byref(lay)))
-        self.total = int(lay.total)
-        self.off = {n: int(getattr(lay, n)) for n in _abi.TRAIN_SECTIONS}
-        c = engine.cfg
-        self.NL = c["layers"] * c["blocks"]
-        self.R, self.D, self.S, self.E, self.C = (c["residual_channels"], c["dilation_channels"], c["skip_channels"],
-                                                  c["end_channels"], c["classes"])
-        self.bias = bool(c.get("bias", False))
-        self.ticket = 0
-        self.device = engine.mem.device
-        self._flat = None        # the packed parameters of the step in flight (one buffer per model: stable addresses)
-        self._gflat = None       # the flat gradient wn_train_backward writes
-        self._ptr_key = None     # the parameter tensors the cached pointer tables below were built for
-        self._ptr_tabs = None
-        self.padded = model_shape is not None and tuple(model_shape) != (self.R, self.D, self.S, self.E)
-        self._pad_bufs = {}      # (key, index) -> the zero-filled tensor of the engine's shape a parameter is copied into every step
+    def __init__(self, NL, R, D, S, E, C, bias, total, off, device):
+        self.NL, self.R, self.D, self.S, self.E, self.C, self.bias = NL, R, D, S, E, C, bool(bias)
+        self.total, self.off, self.device = total, off, device
 
-    # ---- zero padding of the channel shape (training on channel counts that are not multiples of 32) -----------------------------
-    # Padded channels carry zeros through the whole step: zero start_conv rows and zero residual rows keep the extra residual channels at 0,
-    # zero filter / gate rows give tanh(0) * sigmoid(0) = 0, extra skip / end channels are relu(0) = 0 against zero weights -- and no gradient
-    # reaches a real weight through them, nor a padded weight at all (its activation or its incoming gradient is zero).  The logits and the real
-    # parameters' gradients are those of the model's own shape; the tests compare them with torch autograd.
-    def padded_shape(self, key):
-        R, D, S, E, C = self.R, self.D, self.S, self.E, self.C
-        return {"start_w": (R, C, 1), "start_b": (R,), "filter_w": (D, R, 2), "gate_w": (D, R, 2), "filter_b": (D,), "gate_b": (D,),
-                "res_w": (R, D, 1), "res_b": (R,), "skip_w": (S, D, 1), "skip_b": (S,), "end1_w": (E, S, 1), "end1_b": (E,),
-                "end2_w": (C, E, 1), "end2_b": (C,)}[key]
-
-    def pad_tensors(self, by_key):
-        """{key: [parameter tensors]} -> the same parameters inside zero-filled tensors of the engine's channel shape (kept from step to step:
-        only a parameter's own block is ever written)."""
-        out = {}
-        for key, ts in by_key.items():
-            shape = self.padded_shape(key)
-            row = []
-            for i, t in enumerate(ts):
-                buf = self._pad_bufs.get((key, i))
-                if buf is None or buf.device != t.device:
-                    buf = torch.zeros(shape, dtype=torch.float32, device=t.device)
-                    self._pad_bufs[(key, i)] = buf
-                buf[tuple(slice(0, n) for n in t.shape)].copy_(t)
-                row.append(buf)
-            out[key] = row
-        return out
-
-    @staticmethod
-    def crop_grads(grads, real):
-        """Gradients of the padded tensors -> the parameters' own blocks (contiguous copies; None stays None)."""
-        return {key: [None if g is None else g[tuple(slice(0, n) for n in t.shape)].contiguous() for g, t in zip(gs, real[key])] for key, gs in grads.items()}
-
-    # ---- layout conversion (reference Conv1d layouts <-> wn_train_layout) ------------------------------------------
     def sizes(self):
         NL, R, D, S, E, C = self.NL, self.R, self.D, self.S, self.E, self.C
         return {"fg": NL * 2 * R * 2 * D, "bfg": NL * 2 * D, "res": NL * D * R, "bres": NL * R, "skip": NL * D * S,
                 "bskip": NL * S, "bskip_total": S, "w1": S * E, "b1": E, "w2": E * C, "b2": C, "start_t": C * R, "start_b": R}
 
     def pack(self, p):
-        """p: dict with stacked tensors start_w (R,C,1), filter_w/gate_w (NL,D,R,2), res_w (NL,R,D,1), skip_w (NL,S,D,1),
-        end1_w (E,S,1), end2_w (C,E,1), end1_b, end2_b and, with bias, start_b, filter_b, gate_b (NL,D), res_b, skip_b."""
+        """p: {key: tensor} of the keys of params.order(bias), the per-layer ones stacked over the layers (params.stacked)."""
         NL, R, D, S, E, C = self.NL, self.R, self.D, self.S, self.E, self.C
         flat = torch.zeros(self.total, dtype=torch.float32, device=self.device)
         sz, off = self.sizes(), self.off
@@ -131,6 +78,54 @@ class StackRunner:
                         "skip_b": get("bskip").reshape(NL, S).clone(), "start_b": get("start_b").clone()})
         return out
 
+
+class StackRunner(StackLayout):
+    """A StackLayout plus one engine handle (for the plan / layout / workspace): runs the packed forward / backward."""
+
+    def __init__(self, engine, model_shape=None):
+        """model_shape: (R, D, S, E) of the MODEL when the engine was created for a zero-padded channel shape (wavenet_model.py:
+        _native_train_forward pads channel counts that are not multiples of 32 up to multiples of 64): the parameters then travel through
+        zero-filled tensors of the engine's shape (pad_tensors) and only their own block of the gradients comes back (crop_grads)."""
+        self.eng = engine
+        lay = _abi.wn_train_layout()
+        engine.lib.check(engine.lib.dll.wn_train_get_layout(engine._h, ctypes.byref(lay)))
+        c = engine.cfg
+        super().__init__(c["layers"] * c["blocks"], c["residual_channels"], c["dilation_channels"], c["skip_channels"], c["end_channels"],
+                         c["classes"], c.get("bias", False), int(lay.total), {n: int(getattr(lay, n)) for n in _abi.TRAIN_SECTIONS}, engine.mem.device)
+        self.ticket = 0
+        self._flat = None        # the packed parameters of the step in flight (one buffer per model: stable addresses)
+        self._gflat = None       # the flat gradient wn_train_backward writes
+        self._ptr_key = None     # the parameter tensors the cached pointer tables below were built for
+        self._ptr_tabs = None
+        self.padded = model_shape is not None and tuple(model_shape) != (self.R, self.D, self.S, self.E)
+        self._pad_bufs = {}      # (key, index) -> the zero-filled tensor of the engine's shape a parameter is copied into every step
+
+    # ---- zero padding of the channel shape (training on channel counts that are not multiples of 32) -----------------------------
+    # Padded channels carry zeros through the whole step: zero start_conv rows and zero residual rows keep the extra residual channels at 0,
+    # zero filter / gate rows give tanh(0) * sigmoid(0) = 0, extra skip / end channels are relu(0) = 0 against zero weights -- and no gradient
+    # reaches a real weight through them, nor a padded weight at all (its activation or its incoming gradient is zero).  The logits and the real
+    # parameters' gradients are those of the model's own shape; the tests compare them with torch autograd.
+    def pad_tensors(self, by_key):
+        """{key: [parameter tensors]} -> the same parameters inside zero-filled tensors of the engine's channel shape (kept from step to step:
+        only a parameter's own block is ever written)."""
+        out = {}
+        for key, ts in by_key.items():
+            row = []
+            for i, t in enumerate(ts):
+                buf = self._pad_bufs.get((key, i))
+                if buf is None or buf.device != t.device:
+                    buf = torch.zeros(params.shape(key, self.eng.cfg), dtype=torch.float32, device=t.device)
+                    self._pad_bufs[(key, i)] = buf
+                buf[tuple(slice(0, n) for n in t.shape)].copy_(t)
+                row.append(buf)
+            out[key] = row
+        return out
+
+    @staticmethod
+    def crop_grads(grads, real):
+        """Gradients of the padded tensors -> the parameters' own blocks (contiguous copies; None stays None)."""
+        return {key: [None if g is None else g[tuple(slice(0, n) for n in t.shape)].contiguous() for g, t in zip(gs, real[key])] for key, gs in grads.items()}
+
     # ---- native layout conversion: the tensors themselves in, a view per gradient out ---------------------------------------
     @staticmethod
     def _tensor_table(by_key, NL):
@@ -138,17 +133,15 @@ class StackRunner:
         t = _abi.wn_train_tensors()
         t.n_layers, t.reserved = NL, 0
         keep = []
-        names = {"filter_w": "filter_w", "gate_w": "gate_w", "res_w": "res_w", "skip_w": "skip_w", "filter_b": "filter_b", "gate_b": "gate_b",
-                 "res_b": "res_b", "skip_b": "skip_b"}
-        for key, field in names.items():
+        for key in _abi.TRAIN_TENSOR_ARRAYS:
             ts = by_key.get(key)
             if ts is None:
-                setattr(t, field, None)
+                setattr(t, key, None)
                 continue
             arr = (ctypes.c_void_p * NL)(*[(x.data_ptr() if x is not None else None) for x in ts])
             keep.append(arr)
-            setattr(t, field, ctypes.cast(arr, ctypes.c_void_p))
-        for key in ("start_w", "start_b", "end1_w", "end1_b", "end2_w", "end2_b"):
+            setattr(t, key, ctypes.cast(arr, ctypes.c_void_p))
+        for key in _abi.TRAIN_TENSOR_SINGLES:
             ts = by_key.get(key)
             setattr(t, key, ts[0].data_ptr() if ts is not None and ts[0] is not None else None)
         return t, keep
@@ -221,13 +214,6 @@ class StackRunner:
         e = self.eng
         e.lib.check(e.lib.dll.wn_train_export_params(e._h, flat.data_ptr(), e.mem.stream()))
         return flat
-
-
-PARAM_ORDER = ("start_w", "filter_w", "gate_w", "res_w", "skip_w", "end1_w", "end1_b", "end2_w", "end2_b",
-               "start_b", "filter_b", "gate_b", "res_b", "skip_b")
-
-
-SINGLE_KEYS = ("start_w", "start_b", "end1_w", "end1_b", "end2_w", "end2_b")
 
 
 class StackFunction(torch.autograd.Function):

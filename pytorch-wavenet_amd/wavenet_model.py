@@ -21,6 +21,7 @@ What is different underneath:
     multiples of 32 run natively, zero-padded: with and, since round 6, under autograd), and the input lengths for which the reference itself has no defined result (its error, or its shapes, are reproduced).
 """
 import collections
+import itertools
 import os
 import os.path
 import time
@@ -35,6 +36,23 @@ import torch.nn.functional as F
 
 # What WaveNetModel.score_indices returns: device tensors (see there).
 ScoreResult = collections.namedtuple("ScoreResult", ["loss", "accuracy", "n", "row_nll", "pred", "sums"])
+
+
+def _wn_defaults():
+    """What a module carries besides the reference's attributes: set by __init__, and by __setstate__ where a snapshot lacks them."""
+    return {
+        "_wn_engine": None, "_wn_engine_key": None, "_wn_train_runner": None,
+        "_wn_forward_calls": 0, "_wn_train_calls": 0, "_wn_fallbacks": {},     # wn_stats()
+        "_wn_forward_unsupported": None,   # the _forward_shape_key() this device's library has no native forward for
+        "_wn_expansion": None,             # (classes, table) of _expand_indices
+        # Extension: operand precision of the native matrix-core forward / backward GEMMs: "fp32" (default: equals the
+        # reference's fp32 graph to rounding) or "bf16" (bf16 operands, fp32 accumulation and fp32 residual stream;
+        # needs channel counts that are multiples of 64, otherwise fp32 is used)
+        "matrix_precision": "fp32",
+        # Extension: True = the native backward's weight / bias gradients are bit-reproducible from run to run (ordered reduction of the row splits'
+        # partial tiles instead of fp32 atomics: C ABI wn_train_set_deterministic); None = the library's default (off, or WN_DETERMINISTIC=1)
+        "deterministic_gradients": None,
+    }
 
 
 class WaveNetModel(nn.Module):
@@ -98,18 +116,7 @@ class WaveNetModel(nn.Module):
         self.end_conv_2 = nn.Conv1d(end_channels, classes, 1, bias=True)
         self.output_length = output_length
         self.receptive_field = receptive_field
-        self._wn_engine = None
-        self._wn_engine_key = None
-        self._wn_forward_calls = 0
-        self._wn_train_runner = None
-        self._wn_train_calls = 0
-        # Extension: operand precision of the native matrix-core forward / backward GEMMs: "fp32" (default: equals the
-        # reference's fp32 graph to rounding) or "bf16" (bf16 operands, fp32 accumulation and fp32 residual stream;
-        # needs channel counts that are multiples of 64, otherwise fp32 is used)
-        self.matrix_precision = "fp32"
-        # Extension: True = the native backward's weight / bias gradients are bit-reproducible from run to run (ordered reduction of the row splits'
-        # partial tiles instead of fp32 atomics: C ABI wn_train_set_deterministic); None = the library's default (off, or WN_DETERMINISTIC=1)
-        self.deterministic_gradients = None
+        self.__dict__.update(_wn_defaults())
 
     # ------------------------------------------------------------------ training path (torch ops)
     def wavenet(self, input, dilation_func):
@@ -153,7 +160,7 @@ class WaveNetModel(nn.Module):
 
     def _native_trainable(self):
         """Shapes the native training step covers: kernel_size 2 and a class count that is a multiple of 32 -- channel counts that are not multiples
-        of 32 are zero-padded up to multiples of 64 for it (round 6: mi355_wavenet/training.py StackRunner.pad_tensors; same logits, same gradients)."""
+        of 32 are zero-padded up to multiples of 64 for it (round 6: mi355_wavenet/training.py StackRunner.pad_tensors, shapes from mi355_wavenet/params.py; same logits, same gradients)."""
         return self.kernel_size == 2 and self.classes % 32 == 0
 
     def _padded_train_config(self):
@@ -170,7 +177,7 @@ class WaveNetModel(nn.Module):
     def _fallback(self, reason, warn=True):
         """forward() on a CUDA tensor is about to run the reference's algorithm in torch ops (MIOpen conv1d + autograd) instead of the
         native kernels: counted per reason (wn_stats()) and said out loud ONCE per reason -- the dual path is never silent."""
-        stats = self.__dict__.setdefault("_wn_fallbacks", {})
+        stats = self._wn_fallbacks
         stats[reason] = stats.get(reason, 0) + 1
         if warn and stats[reason] == 1:
             import warnings
@@ -182,8 +189,8 @@ class WaveNetModel(nn.Module):
         """Extension: which path forward() / model(x) calls of this module took so far: {'native_forward', 'native_train_forward',
         'torch_fallbacks': {reason: calls}} -- CPU tensors are not fallbacks (the reference's own path), everything else on a CUDA
         tensor that did not reach wn_forward / wn_train_* is."""
-        return {"native_forward": int(getattr(self, "_wn_forward_calls", 0)), "native_train_forward": int(getattr(self, "_wn_train_calls", 0)),
-                "torch_fallbacks": dict(self.__dict__.get("_wn_fallbacks", {}))}
+        return {"native_forward": int(self._wn_forward_calls), "native_train_forward": int(self._wn_train_calls),
+                "torch_fallbacks": dict(self._wn_fallbacks)}
 
     def _native_forward(self, input):
         """Matrix-core forward (C ABI wn_forward, or wn_train_forward + wn_train_backward behind a torch.autograd.Function
@@ -202,7 +209,7 @@ class WaveNetModel(nn.Module):
         want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         # Without autograd the engine decides: a channel shape that is not a multiple of 32 may still run natively, zero-padded into a
         # compiled shape (include/wn_abi.h: wn_create); with autograd the handle keeps the model's own shape and needs the multiples.
-        no_native = getattr(self, "_wn_forward_unsupported", None) == self._forward_shape_key(input.device)
+        no_native = self._wn_forward_unsupported == self._forward_shape_key(input.device)
         if want_grad and not self._native_trainable():
             return self._fallback("a class count that is not a multiple of 32 under autograd")
         if not want_grad and no_native and not self._native_supported():
@@ -234,7 +241,7 @@ class WaveNetModel(nn.Module):
                 #  the torch path reproduces what the reference does there: its error, or its shapes)
                 return self._fallback("the engine refused this call: %s" % e, warn=False)
             raise
-        self._wn_forward_calls = getattr(self, "_wn_forward_calls", 0) + 1
+        self._wn_forward_calls += 1
         return out.to(input.dtype)
 
     def _forward_shape_key(self, device):
@@ -243,17 +250,19 @@ class WaveNetModel(nn.Module):
     def _forward_engine(self):
         """The engine forward() runs on: the generation engine when it holds the current parameters -- whatever its stream count, so that a
         validation forward between two generate_fast() calls leaves it (and its deferred queues) alone --, else a one-stream engine."""
-        eng = self._wn_engine
-        if eng is not None and self._wn_engine_key is not None:
-            plist = list(self.parameters())
-            dev = plist[0].device
-            index = dev.index if dev.type == "cuda" and dev.index is not None else int(os.environ.get("WN_DEVICE", "0"))
-            if self._wn_engine_key[1:] == (index, tuple((v.data_ptr(), v._version) for v in plist)):
-                return eng
+        if self._wn_engine is not None and self._wn_engine_key is not None and self._wn_engine_key[1:] == self._parameters_key():
+            return self._wn_engine
         return self._engine(1)
 
+    def _parameters_key(self):
+        """(device index, (address, version) of every parameter): what an engine's copy of the weights was made from."""
+        plist = list(self.parameters())   # (every state_dict entry of this module is a parameter)
+        dev = plist[0].device
+        index = dev.index if dev.type == "cuda" and dev.index is not None else int(os.environ.get("WN_DEVICE", "0"))
+        return index, tuple((v.data_ptr(), v._version) for v in plist)
+
     def _apply_precision(self, eng):
-        want = getattr(self, "matrix_precision", "fp32") == "bf16"
+        want = self.matrix_precision == "bf16"
         c = eng.cfg   # (the ENGINE's channel shape: the training engine of a model with odd channel counts is zero-padded to multiples of 64)
         if want and any(c[k] % 64 for k in ("residual_channels", "dilation_channels", "skip_channels", "end_channels")):
             want = False
@@ -263,54 +272,24 @@ class WaveNetModel(nn.Module):
 
     def _native_train_forward(self, idx):
         """model(x) with a native backward: see mi355_wavenet/training.py."""
-        from mi355_wavenet import engine, training
-        runner = getattr(self, "_wn_train_runner", None)
+        from mi355_wavenet import engine, params, training
+        runner = self._wn_train_runner
         dev = next(self.parameters()).device
         if runner is None or runner.device != dev:
             cfg, shape = self._padded_train_config()
             weights = dict(self.state_dict())
             if shape is not None:   # (the handle is created on zero-padded weights of ITS shape; the step's parameters are passed per call)
-                probe = training.StackRunner.__new__(training.StackRunner)
-                probe.R, probe.D, probe.S, probe.E, probe.C = (cfg["residual_channels"], cfg["dilation_channels"], cfg["skip_channels"],
-                                                               cfg["end_channels"], cfg["classes"])
-                kinds = {"start_conv": "start", "end_conv_1": "end1", "end_conv_2": "end2", "filter_convs": "filter", "gate_convs": "gate",
-                         "residual_convs": "res", "skip_convs": "skip"}
-                padded = {}
-                for name, t in weights.items():
-                    parts = name.split(".")
-                    key = kinds[parts[0]] + ("_w" if parts[-1] == "weight" else "_b")
-                    buf = torch.zeros(probe.padded_shape(key), dtype=t.dtype, device=t.device)
-                    buf[tuple(slice(0, n) for n in t.shape)].copy_(t)
-                    padded[name] = buf
-                weights = padded
+                weights = params.padded(weights, cfg)
             eng = engine.Engine(cfg, weights, n_streams=1, device_index=dev.index or 0, pad_channels=False)
             runner = training.StackRunner(eng, model_shape=shape)  # the handle only provides plan, layout and workspace: parameters are passed per call
             self._wn_train_runner = runner
-        names, tensors = [], []
-
-        def add(key, ts):
-            names.append((key, len(ts)))
-            tensors.extend(ts)
-
-        add("start_w", [self.start_conv.weight])
-        add("filter_w", [m.weight for m in self.filter_convs])
-        add("gate_w", [m.weight for m in self.gate_convs])
-        add("res_w", [m.weight for m in self.residual_convs])
-        add("skip_w", [m.weight for m in self.skip_convs])
-        add("end1_w", [self.end_conv_1.weight]); add("end1_b", [self.end_conv_1.bias])
-        add("end2_w", [self.end_conv_2.weight]); add("end2_b", [self.end_conv_2.bias])
-        if self.start_conv.bias is not None:
-            add("start_b", [self.start_conv.bias])
-            add("filter_b", [m.bias for m in self.filter_convs])
-            add("gate_b", [m.bias for m in self.gate_convs])
-            add("res_b", [m.bias for m in self.residual_convs])
-            add("skip_b", [m.bias for m in self.skip_convs])
-        self._wn_train_calls = getattr(self, "_wn_train_calls", 0) + 1
+        by_key = params.from_module(self)
+        self._wn_train_calls += 1
         self._apply_precision(runner.eng)
-        det = getattr(self, "deterministic_gradients", None)
-        if det is not None:
-            runner.set_deterministic(bool(det))
-        return training.StackFunction.apply(runner, idx, self.output_length, tuple(names), *tensors)
+        if self.deterministic_gradients is not None:
+            runner.set_deterministic(bool(self.deterministic_gradients))
+        return training.StackFunction.apply(runner, idx, self.output_length, tuple((k, len(ts)) for k, ts in by_key.items()),
+                                            *itertools.chain.from_iterable(by_key.values()))
 
     def _checked_indices(self, indices, check, training=False):
         idx = torch.as_tensor(indices)
@@ -336,11 +315,7 @@ class WaveNetModel(nn.Module):
         dataset holds before audio_data.py:119-121 inflates it 256x.  Inference only (matrix-core path, no autograd).
         ``check=False`` skips the range check of the indices (one device sync) when the producer guarantees it."""
         idx = self._checked_indices(indices, check)
-        eng = self._forward_engine()
-        self._apply_precision(eng)
-        out = self._index_call(lambda: eng.forward_indices(idx, self.output_length))
-        self._wn_forward_calls = getattr(self, "_wn_forward_calls", 0) + 1
-        return out
+        return self._on_forward_engine(lambda eng: eng.forward_indices(idx, self.output_length))
 
     def score_indices(self, indices, targets=None, check=True, want_rows=False, want_pred=False):
         """Extension: teacher-forced scoring on class indices -- what WavenetTrainer.validate() computes per batch (wavenet_training.py:89-112) and
@@ -365,12 +340,17 @@ class WaveNetModel(nn.Module):
         if tgt.numel() != idx.size(0) * self.output_length:
             raise ValueError("targets hold %d values, %d items x output_length %d need %d" % (
                 tgt.numel(), idx.size(0), self.output_length, idx.size(0) * self.output_length))
-        eng = self._forward_engine()
-        self._apply_precision(eng)
-        out = self._index_call(lambda: eng.score(idx, tgt, self.output_length, want_rows=want_rows, want_pred=want_pred))
-        self._wn_forward_calls = getattr(self, "_wn_forward_calls", 0) + 1
+        out = self._on_forward_engine(lambda eng: eng.score(idx, tgt, self.output_length, want_rows=want_rows, want_pred=want_pred))
         sums = out["sums"]
         return ScoreResult(loss=sums[0] / sums[2], accuracy=sums[1] / sums[2], n=sums[2], row_nll=out["row_nll"], pred=out["row_pred"], sums=sums)
+
+    def _on_forward_engine(self, call):
+        """One index-based inference call on the forward engine, at the model's precision; counted in wn_stats()."""
+        eng = self._forward_engine()
+        self._apply_precision(eng)
+        out = self._index_call(lambda: call(eng))
+        self._wn_forward_calls += 1
+        return out
 
     @staticmethod
     def _index_call(fn):
@@ -415,10 +395,8 @@ class WaveNetModel(nn.Module):
     def _engine(self, n_streams):
         """The MI355X engine holding this module's current parameters (rebuilt when they change)."""
         from mi355_wavenet import engine
-        plist = list(self.parameters())
-        dev = plist[0].device
-        index = dev.index if dev.type == "cuda" and dev.index is not None else int(os.environ.get("WN_DEVICE", "0"))
-        key = (n_streams, index, tuple((v.data_ptr(), v._version) for v in plist))  # (every state_dict entry of this module is a parameter)
+        key = (n_streams,) + self._parameters_key()
+        index = key[1]
         if self._wn_engine is None or self._wn_engine_key != key:
             params = list(self.state_dict().items())
             if self._wn_engine is not None and self._wn_engine_key[:2] == key[:2]:
@@ -531,7 +509,7 @@ class WaveNetModel(nn.Module):
         same numpy expressions and looked up (10 ms -> 0.3 ms per 128 k samples); the table is checked once against the
         elementwise evaluation on a probe that puts every class at shifted array positions."""
         classes = self.classes
-        tab = getattr(self, "_wn_expansion", None)
+        tab = self._wn_expansion
         if tab is None or tab[0] != classes:
             every = np.arange(classes, dtype=np.int64)
             table = mu_law_expansion((every / classes) * 2. - 1, classes)
@@ -605,13 +583,8 @@ class WaveNetModel(nn.Module):
         checkpoint format): their __dict__ has no end_channels / bias / engine fields (wavenet_model.py:42-56)."""
         super().__setstate__(state)   # nn.Module back-fills the hook / buffer attributes that a snapshot of an older torch lacks
         d = self.__dict__
-        d.setdefault("_wn_engine", None)
-        d.setdefault("_wn_engine_key", None)
-        d.setdefault("_wn_forward_calls", 0)
-        d.setdefault("_wn_train_runner", None)
-        d.setdefault("_wn_train_calls", 0)
-        d.setdefault("matrix_precision", "fp32")
-        d.setdefault("deterministic_gradients", None)
+        for k, v in _wn_defaults().items():
+            d.setdefault(k, v)
         if "end_channels" not in d:
             d["end_channels"] = self.end_conv_1.out_channels
         if "bias" not in d:

@@ -1,5 +1,5 @@
 """CPU: layout and packing of the GEMM-ready weight banks (csrc/wn_banks.h, plain C++) compiled with g++ and checked through a small
-harness against the torch restatement of the same layout (mi355_wavenet/training.py: StackRunner.sizes / StackRunner.pack):
+harness against the torch restatement of the same layout (mi355_wavenet/training.py: StackLayout.sizes / StackLayout.pack):
 the offsets are the running sum of the section sizes, the fp32 bank equals the Python pack bit for bit (both are pure copies; bskip_total,
 the one computed section, is the fp32 sum of the skip biases taken in layer order), the bf16 bank equals torch's round-to-nearest-even
 bfloat16 of the transposed / block-grouped fp32 sections bit for bit."""
@@ -90,12 +90,9 @@ def weights(shape, bias, seed):
 
 
 def runner(shape, bias, total, off):
-    """A StackRunner without an engine: pack() and sizes() only need the shape, the layout and a device."""
+    """The engine-free half of a StackRunner: pack() and sizes() only need the shape, the layout and a device."""
     layers, blocks, R, D, S, E, C = shape
-    r = object.__new__(training.StackRunner)
-    r.NL, r.R, r.D, r.S, r.E, r.C, r.bias = layers * blocks, R, D, S, E, C, bool(bias)
-    r.total, r.off, r.device = total, off, torch.device("cpu")
-    return r
+    return training.StackLayout(layers * blocks, R, D, S, E, C, bias, total, off, torch.device("cpu"))
 
 
 def bits(t):

@@ -138,21 +138,16 @@ def test_native_gradients_match_the_reference_golden(golden, case):
 
 def test_packed_layout_matches_the_c_side():
     """pack(parameters) in Python == what wn_load_weights built in C (wn_train_export_params), element for element."""
-    from mi355_wavenet import engine, training
+    from mi355_wavenet import engine, params, training
     for bias in (False, True):
         m = _model(bias)
         eng = engine.Engine(m._config(), dict(m.state_dict()), n_streams=1, device_index=0, pad_channels=False)  # (a training handle keeps the model's own shape)
         r = training.StackRunner(eng)
-        sd = m.state_dict()
         NL = m.layers * m.blocks
-        p = {"start_w": sd["start_conv.weight"], "end1_w": sd["end_conv_1.weight"], "end1_b": sd["end_conv_1.bias"],
-             "end2_w": sd["end_conv_2.weight"], "end2_b": sd["end_conv_2.bias"]}
-        for key, name in (("filter", "filter_convs"), ("gate", "gate_convs"), ("res", "residual_convs"), ("skip", "skip_convs")):
-            p[key + "_w"] = torch.stack([sd["%s.%d.weight" % (name, l)] for l in range(NL)])
-            if bias:
-                p[key + "_b"] = torch.stack([sd["%s.%d.bias" % (name, l)] for l in range(NL)])
-        if bias:
-            p["start_b"] = sd["start_conv.bias"]
+        # (the module's own parameters by attribute, against the engine's copy gathered by state_dict name: both maps are params' table, which
+        #  tests/test_params_host.py holds to a real state_dict)
+        p = {k: (ts[0].detach() if k in training.SINGLE_KEYS else torch.stack([t.detach() for t in ts])) for k, ts in params.from_module(m).items()}
+        assert tuple(p) == params.order(bias)
         flat = r.pack(p)
         ref = r.export_params()
         torch.cuda.synchronize()
