@@ -273,9 +273,10 @@ int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_
  * fp32 DEVICE array in the packed layout described by wn_train_layout (each reference parameter appears exactly once, so
  * any element-wise optimiser can step on the flat array directly), plus a same-shaped gradient array.  The loss (and its
  * gradient w.r.t. the logits) stays with the caller -- the reference computes it with F.cross_entropy (wavenet_training.py:83).
- * Offsets are in floats.  Packed layouts (NL layers, R/D/S/E/C channel counts, k = 2 taps; the inference bank of a kernel_size 3 or 4 handle has
- * fg [NL][kR][2D], tap 0 = x[t-(k-1)d] the oldest, and is not reachable through wn_train_*, which stay kernel_size 2):
- *   fg    [NL][2R][2D]  row = tap*R + r (tap 0 = x[t-d], tap 1 = x[t]); column = 64*(ch/32) + 32*gate + ch%32, gate 0 = filter
+ * Offsets are in floats.  Packed layouts (NL layers, R/D/S/E/C channel counts, k = kernel_size taps).  wn_train_* serve kernel_size 2, and -- fp32
+ * operands only, channel counts and classes multiples of 32, no zero padding, clips of at least receptive_field + output_length - 1 samples
+ * (shorter ones: WN_E_UNSUPPORTED from wn_train_forward, nothing written) -- kernel_size 3 and 4; above 4: WN_E_UNSUPPORTED.
+ *   fg    [NL][kR][2D]  row = tap*R + r (tap 0 = x[t-(k-1)d] the oldest .. tap k-1 = x[t]; k = 2: x[t-d], x[t]); column = 64*(ch/32) + 32*gate + ch%32, gate 0 = filter
  *                       (filter_convs.l.weight[ch][r][tap], gate_convs.l.weight[ch][r][tap])       bfg [NL][2D] same columns
  *   res   [NL][D][R]    residual_convs.l.weight[r][d][0] transposed                                 bres [NL][R]
  *   skip  [NL][D][S]    skip_convs.l.weight[s][d][0] transposed                                     bskip [NL][S]
@@ -299,8 +300,8 @@ int wn_train_export_params(wn_handle* h, float* params, void* hip_stream);
 typedef struct wn_train_tensors {
     int32_t n_layers;          /* layers * blocks */
     int32_t reserved;          /* 0 */
-    void* const* filter_w;     /* [n_layers] (D, R, 2) */
-    void* const* gate_w;       /* [n_layers] (D, R, 2) */
+    void* const* filter_w;     /* [n_layers] (D, R, k)   k = kernel_size */
+    void* const* gate_w;       /* [n_layers] (D, R, k) */
     void* const* res_w;        /* [n_layers] (R, D, 1) */
     void* const* skip_w;       /* [n_layers] (S, D, 1) */
     void* const* filter_b;     /* [n_layers] (D) or NULL */
@@ -330,7 +331,8 @@ int wn_train_unpack_grads(wn_handle* h, const float* grads, const wn_train_tenso
 int wn_train_set_deterministic(wn_handle* h, int32_t on);
 
 /* model(x) for training: like wn_forward (fp32) but reads the parameters from `params` and keeps every layer's input, gate
- * activations and the head's intermediates in a workspace owned by the handle for the following wn_train_backward. */
+ * activations and the head's intermediates in a workspace owned by the handle for the following wn_train_backward.  kernel_size 3 and 4:
+ * as wn_forward, no zero-padded taps -- a clip shorter than receptive_field + output_length - 1 is WN_E_UNSUPPORTED with wn_forward's message. */
 int wn_train_forward(wn_handle* h, const float* params, const int32_t* indices, int64_t N, int64_t L, int64_t output_length,
                      float* logits, void* hip_stream);
 

@@ -14,12 +14,15 @@
 #include "../../include/wn_abi.h"
 #include "wn_plan.h"
 
-// the training step (and the bf16 forward) needs kernel_size 2 and channel counts that are multiples of 32
+// the bf16 forms of the forward and the training step need kernel_size 2 and channel counts that are multiples of 32
 static inline bool wn_bank_ok(const WnPlan& s) { return s.k == 2 && s.R % 32 == 0 && s.D % 32 == 0 && s.S % 32 == 0 && s.E % 32 == 0 && s.C % 32 == 0; }
 // inference (wn_forward / wn_score / wn_prime, fp32 operands) also takes kernel_size 3 and 4: only the filter/gate product reads the taps (wn_fwd_gemm_taps)
 static inline bool wn_bank_fwd_ok(const WnPlan& s) {
     return s.k >= 2 && s.k <= 4 && s.R % 32 == 0 && s.D % 32 == 0 && s.S % 32 == 0 && s.E % 32 == 0 && s.C % 32 == 0;
 }
+
+// the fp32 training step takes the same shapes (kernel_size 3 and 4: wn_fwd_gemm_taps / wn_bwd_gemm_taps; bf16 operands stay kernel_size 2)
+static inline bool wn_bank_train_ok(const WnPlan& s) { return wn_bank_fwd_ok(s); }
 
 static inline wn_train_layout wn_bank_layout(const WnPlan& s) {   // offsets in floats
     const int64_t NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C, k = s.k;

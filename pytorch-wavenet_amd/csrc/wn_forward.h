@@ -16,7 +16,8 @@
 // result matches the reference's fp32 forward to rounding (tests: 1e-4).  wn_set_forward_precision selects the bf16 forms
 // (v_mfma_f32_32x32x16_bf16, fp32 accumulation): operands rounded while they are staged, and in the training step the activations
 // that only ever feed such operands stored as bf16 -- the products are HBM streams (K = 128-512), so the bytes are what they cost.
-// The same file holds the backward products of the training step (wn_train.inl is their host side).
+// The same file holds the backward products of the training step (wn_train.inl is their host side).  kernel_size 3 and 4 (fp32 operands) take the
+// filter/gate product and its input gradient over k row-shifted views of one matrix: wn_fwd_gemm_taps, wn_bwd_gemm_taps.
 //
 // Valid when every returned position has a full receptive field: L >= receptive_field + output_length - 1 (the
 // reference's own training shape, train_script.py:39).  Shorter inputs hit the reference's zero-padding quirk
@@ -538,6 +539,112 @@ __global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm_taps(WnTapsArgs
     }
 
     wn_gemm_epilogue<WN_EPI_GATE>(g, acc, m0 + 32 * wv, n0, lane, smem_f + wv * WN_EPI_TILE_FLOATS);   // (the loop's last barrier: nobody reads the operand buffers any more)
+}
+
+// ---- The input gradient of that product (training step, kernel_size TAPS = 3 or 4, fp32 operands): with dfg = [dF|dG] of the layer on the rows
+// [t_lo, t_hi) of every batch entry,
+//     dx(t) = dx'(t) [row >= cin_skip_lo]  +  sum_j dfg(t + (TAPS-1-j) d) . W_j^T,   K = TAPS * 2D,
+// in one launch, every output row written exactly once (nothing is cleared first, no read-modify-write).  The sibling of wn_fwd_gemm_taps: same tile,
+// K loop and LDS image, the plain epilogue.  The A operand is TAPS views of ONE matrix shifted FORWARD in time: g.a1 is the view of dfg(t), view j
+// lies (TAPS-1-j) * tap_rows rows behind it in memory order (later in time), g.k_split = 2D is the K extent of a view (a chunk never straddles
+// two views: 2D % 64 == 0), g.K = TAPS * 2D.  A view's row is formed from (batch entry, row in the entry); it reads as zero WITHOUT BEING LOADED
+// where its time falls before t_lo or at / after t_hi (the units of g.a1.t0), so no view crosses into the next entry.  The B operand is the TAPS
+// transposed tap blocks [2D][N], block j at g.bt + j * bt_tap_stride (N = R output columns).
+struct WnTapsBwdArgs {
+    WnGemmArgs g;             // a0, bt1, a_skip_*, a_bf16, relu_*, mask, gate_*, c2: unused
+    long long tap_rows;       // d: rows between two neighbouring views
+    long long t_lo, t_hi;     // the rows of a batch entry of dfg that exist: [t_lo, t_hi)
+    long long bt_tap_stride;  // floats between the transposed blocks of two neighbouring taps
+};
+template <int TAPS>
+__global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_bwd_gemm_taps(WnTapsBwdArgs ta) {
+    static_assert(TAPS == 3 || TAPS == 4, "kernel_size 3 and 4 (2 is wn_fwd_gemm's two-view form)");
+    const WnGemmArgs& g = ta.g;
+    constexpr int TM = 128, TN = 128, KC = WN_GEMM_KC, AP = TM + 1;
+    constexpr int NQ = KC / 8;
+    constexpr int BT = 256 / KC;
+    __shared__ __attribute__((aligned(16))) float smem_f[2 * KC * AP + 2 * KC * TN + (2 * KC * AP) % 4];
+    static_assert(2 * KC * AP + 2 * KC * TN >= 4 * WN_EPI_TILE_FLOATS, "the operand buffers hold the four waves' staging tiles");
+    float (*a_t)[KC * AP] = reinterpret_cast<float (*)[KC * AP]>(smem_f);                                        // [2][k][row]
+    float (*b_s)[KC * TN] = reinterpret_cast<float (*)[KC * TN]>(smem_f + ((2 * KC * AP + 3) & ~3));               // [2][k][col]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const unsigned mtiles = (unsigned)((g.M + TM - 1) / TM), tm_i = blockIdx.x % mtiles, tn_i = blockIdx.x / mtiles;  // row tiles fastest
+    const long long m0 = (long long)tm_i * TM;
+    const int n0 = (int)tn_i * TN;
+    wn_f16v acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+
+    // loader roles as in wn_fwd_gemm_taps: A chunk = 128 rows x KC floats, two threads per row; B chunk = KC x 128
+    const int arow = tid >> 1, ahalf = tid & 1;
+    const long long am = m0 + arow;
+    const bool arow_ok = am < g.M;
+    const unsigned aq = arow_ok ? (unsigned)am / (unsigned)g.rows_per_batch : 0u, arem = arow_ok ? (unsigned)am - aq * (unsigned)g.rows_per_batch : 0u;
+    const float* a1p = wn_row_at(g.a1, aq, arem) + ahalf * (KC / 2);   // the row of dfg(t) (formed, not loaded, where it does not exist)
+    const long long tap_fl = ta.tap_rows * g.a1.row_stride;              // floats between two neighbouring views
+    const long long t_row = g.a1.t0 + (long long)arem;                    // the row's time inside its batch entry
+    unsigned okmask = 0;                                                 // bit j: view j of this row exists
+#pragma unroll
+    for (int j = 0; j < TAPS; ++j) {
+        const long long tj = t_row + (TAPS - 1 - j) * ta.tap_rows;
+        okmask |= (arow_ok && tj >= ta.t_lo && tj < ta.t_hi) ? (1u << j) : 0u;
+    }
+    const int brow = tid / BT, bcol = (tid % BT) * (KC / 2);
+    const float* bp = g.bt + (size_t)brow * g.N + n0 + bcol;
+    const bool okb = n0 + bcol < g.N;   // (one predicate for the thread's NQ loads: see wn_fwd_gemm)
+
+    float4 va[NQ], vb[NQ];
+    int f_tap = 0, f_off = 0;   // the view and the column inside it of the next chunk to fetch
+    auto fetch = [&]() {
+        const bool ok = (okmask >> f_tap) & 1u;
+        const float* src = a1p + (long long)(TAPS - 1 - f_tap) * tap_fl + f_off;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) va[q] = ok ? *reinterpret_cast<const float4*>(src + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const float* bsrc = bp + (long long)f_tap * ta.bt_tap_stride + (size_t)f_off * g.N;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) vb[q] = okb ? *reinterpret_cast<const float4*>(bsrc + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        f_off += KC;
+        if (f_off == g.k_split) { f_off = 0; ++f_tap; }
+    };
+    auto stash = [&](int buf) {  // registers -> LDS (A transposed to [k][row])
+        float* at = a_t[buf];
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) {
+            const float4 x = va[q];
+            const int k = ahalf * (KC / 2) + q * 4;
+            at[(k + 0) * AP + arow] = x.x; at[(k + 1) * AP + arow] = x.y; at[(k + 2) * AP + arow] = x.z; at[(k + 3) * AP + arow] = x.w;
+        }
+        float* bs = b_s[buf] + brow * TN + bcol;
+#pragma unroll
+        for (int q = 0; q < NQ; ++q) *reinterpret_cast<float4*>(bs + q * 4) = vb[q];
+    };
+
+    const int nchunks = TAPS * (g.k_split / KC);
+    fetch();
+    stash(0);
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; ++kc) {
+        const int buf = kc & 1;
+        if (kc + 1 < nchunks) fetch();  // lands while this chunk is multiplied
+        const float* at = a_t[buf] + 32 * wv + (lane & 31);
+        const float* bs = b_s[buf] + (lane & 31);
+        const int kh = lane >> 5;
+#pragma unroll
+        for (int ks = 0; ks < KC / 2; ++ks) {
+            const float a = at[(2 * ks + kh) * AP];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const float b = bs[(2 * ks + kh) * TN + 32 * j];
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
+            }
+        }
+        if (kc + 1 < nchunks) stash(buf ^ 1);
+        __syncthreads();
+    }
+
+    wn_gemm_epilogue<WN_EPI_PLAIN>(g, acc, m0 + 32 * wv, n0, lane, smem_f + wv * WN_EPI_TILE_FLOATS);   // (the loop's last barrier: nobody reads the operand buffers any more)
 }
 
 

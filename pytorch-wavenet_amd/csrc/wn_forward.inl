@@ -35,6 +35,13 @@ static void wn_launch_taps(hipStream_t st, int taps, const WnTapsArgs& a) {
     else hipLaunchKernelGGL(wn_fwd_gemm_taps<4>, grid, dim3(256), 0, st, a);
 }
 
+// The input gradient of that product in the training step (wn_bwd_gemm_taps: one launch, dx written exactly once)
+static void wn_launch_taps_bwd(hipStream_t st, int taps, const WnTapsBwdArgs& a) {
+    const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)((a.g.N + 127) / 128));
+    if (taps == 3) hipLaunchKernelGGL(wn_bwd_gemm_taps<3>, grid, dim3(256), 0, st, a);
+    else hipLaunchKernelGGL(wn_bwd_gemm_taps<4>, grid, dim3(256), 0, st, a);
+}
+
 // One forward layer in one launch (wn_fwd_layer_bf16): `a` = the filter/gate product's arguments (bf16 operands, c_bf16 = 1; a.c.base may be
 // NULL: z is not stored), `r` = the residual product's (its bias, cin, c, c_h are used).  Returns false when the shape is not the fused
 // kernel's (the caller launches the two products).  WN_NO_FUSED_LAYER=1 (with WN_TESTING=1) switches it off for A/B runs.
@@ -110,6 +117,19 @@ static WnTapsArgs wn_layer_fg_taps(const WnPlan& pl, const wn_train_layout& o, c
     WnTapsArgs a;
     a.g = wn_nn2(x, x, pl.R, pl.k * pl.R, fw + o.fg + (size_t)l * pl.k * pl.R * 2 * pl.D, 2 * pl.D, pl.has_bias ? fw + o.bfg + (size_t)l * 2 * pl.D : nullptr, z, n * rows, rows);
     a.tap_rows = d; a.t_min = t_min;
+    return a;
+}
+// dx_l = (dx') + sum_j dfg(t + (k-1-j) d) . W_j^T of a layer with kernel_size k = 3 or 4, on the `rows_out` trailing rows of every batch entry.  dfg holds
+// `rows_dfg` dense rows of 2D floats per entry, the trailing ones (wn_taps_bwd_shift, wn_plan.h: output row i is dfg's row i - shift where that exists);
+// btT = the transposed tap blocks [2D][R] of the layer, tap_stride floats apart; dx / dxin (base NULL: no addend) are views at the first output row.
+static WnTapsBwdArgs wn_layer_dx_taps(const WnPlan& pl, const float* dfg, long long rows_dfg, long long rows_out, long long d, const float* btT, long long tap_stride,
+                                      const WnRowMap& dxin, const WnRowMap& dx, long long n) {
+    const long long sh = wn_taps_bwd_shift(rows_out, rows_dfg);
+    WnTapsBwdArgs a;
+    const WnRowMap v = wn_rows(dfg, rows_dfg, 2 * pl.D, -sh);
+    a.g = wn_nn2(v, v, 2 * pl.D, pl.k * 2 * pl.D, btT, pl.R, nullptr, dx, n * rows_out, rows_out);
+    a.g.cin = dxin; a.g.cin_skip_lo = (int)sh;   // (dx' exists on the rows dfg does)
+    a.tap_rows = d; a.t_lo = 0; a.t_hi = rows_dfg; a.bt_tap_stride = tap_stride;
     return a;
 }
 // x' = z . Wres^T + bres + x(t) of layer l

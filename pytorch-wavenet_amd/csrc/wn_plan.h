@@ -483,4 +483,12 @@ static inline std::string wn_forward_geometry_host(const int32_t* dil, int NL, l
     }
     return std::string();
 }
+// ---- row windows of the k-tap backward's input-gradient product (wn_bwd_gemm_taps, wn_forward.h).  dx_l lives on the rows_out = g.rows[l] trailing rows of a
+// clip, [dF|dG] of the layer on the rows_dfg = g.rows[l + 1] trailing ones: output row i (time L - rows_out + i) is row i - shift of dfg.
+static inline long long wn_taps_bwd_shift(long long rows_out, long long rows_dfg) { return rows_out - rows_dfg; }
+// The row of dfg that view j (tap j, 0 = the oldest) of output row i reads -- dfg(t + (k-1-j) d) --, or -1 where that row does not exist: the view reads as zero there.
+static inline long long wn_taps_bwd_src(long long i, long long shift, long long d, int k, int j, long long rows_dfg) {
+    const long long r = i - shift + (long long)(k - 1 - j) * d;
+    return (r >= 0 && r < rows_dfg) ? r : -1;
+}
 #endif  // WN_PLAN_H

@@ -317,7 +317,8 @@ struct WnDetWs { float* buf = nullptr; size_t floats = 0; };
 struct WnWeights {
     float *d_blobs = nullptr, *d_start_t = nullptr, *d_start_b = nullptr;
     // batched forward (wn_forward) and training: the fp32 bank, and its bf16 copy [N][K] row-major
-    float* d_fw = nullptr; size_t fw_floats = 0; bool fw_ok = false; wn_train_layout fw = {};   // fw_ok: the training step's shapes (kernel_size 2)
+    float* d_fw = nullptr; size_t fw_floats = 0; bool fw_ok = false; wn_train_layout fw = {};   // fw_ok: kernel_size 2 shapes (the bf16 banks)
+    bool train_ok = false;   // the training step's shapes: kernel_size 2, 3 and 4 (wn_banks.h: wn_bank_train_ok)
     bool fwd_ok = false;   // inference (wn_forward / wn_score / wn_prime): also kernel_size 3 and 4 (wn_banks.h: wn_bank_fwd_ok)
     unsigned short* d_fwb = nullptr; size_t fwb_elems = 0; bool fwb_ok = false; WnBf16Layout fwb;
 };
@@ -810,6 +811,7 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
     // GEMM-ready banks for wn_forward and the training step (wn_banks.h)
     wt.fw_ok = wn_bank_ok(pl);
     wt.fwd_ok = wn_bank_fwd_ok(pl);
+    wt.train_ok = wn_bank_train_ok(pl);
     wt.fwb_ok = false;
     if (wt.fwd_ok) {
         wt.fw = wn_bank_layout(pl);

@@ -15,6 +15,11 @@
 //           dF   = dz * G * (1 - T^2),  dG = dz * T * G * (1 - G)           dWfg^T  = [x_l(t-d) | x_l(t)]^T . [dF|dG]
 //           dx_l(t) = dx'(t) + [dF|dG](t) . Wfg(tap 1) + [dF|dG](t+d) . Wfg(tap 0)
 //       dstart^T = onehot(indices)^T . dx_0
+//   kernel_size k = 3, 4 (fp32 operands; clips of at least receptive_field + output_length - 1 samples, so that every tap of every row exists):
+//       [F|G] = [x_l(t-(k-1)d) | ... | x_l(t)] . Wfg^T + b      wn_fwd_gemm_taps<k>, the same gate epilogue (T, G saved, z into Z_b)
+//       dWfg^T rows jR.. = x_l(t-(k-1-j)d)^T . [dF|dG]          k single-view launches of wn_bwd_gemm_tn (atomics or deterministic, as every TN product)
+//       dx_l(t) = dx'(t) + sum_j [dF|dG](t+(k-1-j)d) . Wfg(tap j)    ONE launch of wn_bwd_gemm_taps<k>, dx_l written exactly once
+//   everything else -- residual, grouped skip, head, gate derivative, column sums, start_conv, the two streams and their events -- is the k = 2 code.
 //   "NN" products reuse wn_fwd_gemm with re-laid-out banks (rebuilt from `params` by wn_transpose_batched on every forward);
 //   "TN" products (weight gradients) use wn_bwd_gemm_tn; bias gradients are column sums.
 
@@ -29,6 +34,10 @@ static int wn_train_layout_ws(const wn_handle* h, long long N, long long L, long
         if (rc) return rc;
         t.need = geo.rows; t.zlo = geo.zlo;
     }
+    if (pl.k != 2)   // (the k-tap products have no row windows for pad zeros: wn_forward's refusal)
+        for (int l = 0; l < NL; ++l)
+            if (t.zlo[l] != 0 || L - t.need[l + 1] - (long long)(pl.k - 1) * h->dil[l] < 0)
+                return wn_fail(WN_E_UNSUPPORTED, "wn_train_forward: kernel_size %d does not serve zero-padded taps", pl.k);
     t.G = pl.layers < NL ? pl.layers : NL;
     { const char* gb = wn_dev_env("WN_TRAIN_SKIP_BLOCK"); if (gb && atoi(gb) > 0) t.G = atoi(gb) < NL ? atoi(gb) : NL; }   // (A/B runs, with WN_TESTING=1: layers per grouped skip product)
     size_t o = 0;
@@ -67,6 +76,7 @@ static int wn_train_layout_ws(const wn_handle* h, long long N, long long L, long
     t.skip = take(Mo * S); t.ev = take(Mo * E); t.dzg = take((size_t)t.nblk * Mo * t.G * D); t.bskip_total = take(S);
     t.res_o = take((size_t)NL * R * D); t.skip_o = take((size_t)NL * S * D); t.w1_o = take((size_t)E * S); t.w2_o = take((size_t)C * E);
     t.fgb0 = take((size_t)NL * 2 * D * R); t.fgb1 = take((size_t)NL * 2 * D * R);
+    if (pl.k > 2) take((size_t)(pl.k - 2) * NL * 2 * D * R);   // kernel_size 3, 4: the further taps' blocks behind them, tap j at fgb0 + j * (fgb1 - fgb0)
     t.dskip = take(Mo * S); t.de = take(Mo * E); t.dz = take(zmax); t.dfg = take(2 * zmax); t.dfg2 = take(2 * zmax);
     t.dskip_h = (h->fw_bf16 && h->w.fwb_ok) ? take((Mo * S + 1) / 2) : 0;   // (written by the dskip product next to the fp32 matrix: WnGemmArgs::c_h)
     t.dxa = take((size_t)N * L * R); t.dxb = take((size_t)N * L * R);
@@ -95,7 +105,7 @@ static WnRowMap wn_zg_map(const WnTrainLay& t, float* ws, int D, int b) {       
 
 static int wn_train_usable(wn_handle* h, const char* who) {   // a handle whose packed parameter layout is the caller's model
     if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
-    if (!h->w.fw_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_train: needs kernel_size 2 and channel counts that are multiples of 32");
+    if (!h->w.train_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_train: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32");
     if (h->padded) return wn_fail(WN_E_UNSUPPORTED, "wn_train: this handle runs a zero-padded channel shape (its parameter layout is not the caller's)");
     return WN_OK;
 }
@@ -134,7 +144,7 @@ extern "C" int wn_train_export_params(wn_handle* h, float* params, void* hip_str
 static int wn_relayout_run(wn_handle* h, const wn_train_tensors* t, float* flat, bool unpack, hipStream_t st, const char* who) {
     const WnPlan& pl = h->plan;
     const wn_train_layout& o = h->w.fw;
-    const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
+    const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL, k = pl.k;
     if (t->n_layers != NL) return wn_fail(WN_E_BADARG, "%s: n_layers = %d, the model has %d", who, t->n_layers, NL);
     if (!t->filter_w || !t->gate_w || !t->res_w || !t->skip_w) return wn_fail(WN_E_BADARG, "%s: a per-layer pointer array is NULL", who);
     if (pl.has_bias && (!t->filter_b || !t->gate_b || !t->res_b || !t->skip_b)) return wn_fail(WN_E_BADARG, "%s: cfg.bias = 1 but a per-layer bias array is NULL", who);
@@ -152,10 +162,10 @@ static int wn_relayout_run(wn_handle* h, const wn_train_tensors* t, float* flat,
         b.tiles += ((rows + 31) / 32) * ((cols + 31) / 32);
     };
     for (int l = 0; l < NL; ++l) {
-        for (int tap = 0; tap < 2; ++tap) {   // (D, R, 2) -> rows tap * R .. of [2R][2D], columns [F(32) | G(32)] per 32 channels
-            const size_t off = o.fg + ((size_t)l * 2 * R + (size_t)tap * R) * 2 * D;
-            piece(t->filter_w[l] ? static_cast<float*>(t->filter_w[l]) + tap : nullptr, off, D, R, 2 * R, 2, 2 * D, 64, 0);
-            piece(t->gate_w[l] ? static_cast<float*>(t->gate_w[l]) + tap : nullptr, off, D, R, 2 * R, 2, 2 * D, 64, 32);
+        for (int tap = 0; tap < k; ++tap) {   // (D, R, k) -> rows tap * R .. of [kR][2D], columns [F(32) | G(32)] per 32 channels
+            const size_t off = o.fg + ((size_t)l * k * R + (size_t)tap * R) * 2 * D;
+            piece(t->filter_w[l] ? static_cast<float*>(t->filter_w[l]) + tap : nullptr, off, D, R, k * R, k, 2 * D, 64, 0);
+            piece(t->gate_w[l] ? static_cast<float*>(t->gate_w[l]) + tap : nullptr, off, D, R, k * R, k, 2 * D, 64, 32);
         }
         piece(t->res_w[l], o.res + (size_t)l * D * R, R, D, D, 1, R, 32, 0);       // (R, D, 1) -> [D][R]
         piece(t->skip_w[l], o.skip + (size_t)l * D * S, S, D, D, 1, S, 32, 0);     // (S, D, 1) -> [D][S]
@@ -366,7 +376,7 @@ extern "C" int wn_train_forward(wn_handle* h, const float* params, const int32_t
     if (N < 1 || out_len < 1) return wn_fail(WN_E_BADARG, "wn_train_forward: N and output_length must be >= 1");
     const WnPlan& pl = h->plan;
     const int R = pl.R, D = pl.D, S = pl.S, E = pl.E, C = pl.C, NL = pl.NL;
-    if (!h->w.fw_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_train_forward: needs kernel_size 2 and channel counts that are multiples of 32");
+    if (!h->w.train_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_train_forward: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32");
     if (h->padded) return wn_fail(WN_E_UNSUPPORTED, "wn_train_forward: this handle runs a zero-padded channel shape (its parameter layout is not the caller's)");
     if ((long long)N * L >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "wn_train_forward: N*L must stay below 2^31 rows");
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
@@ -392,8 +402,8 @@ extern "C" int wn_train_forward(wn_handle* h, const float* params, const int32_t
     }
     wn_launch_transpose(st, fw + o.w1, 0, ws + t.w1_o, S, E, 1);                         // [S][E] -> [E][S]
     wn_launch_transpose(st, fw + o.w2, 0, ws + t.w2_o, E, C, 1);                         // [E][C] -> [C][E]
-    wn_launch_transpose(st, fw + o.fg, (long long)2 * R * 2 * D, ws + t.fgb0, R, 2 * D, NL);               // tap 0 rows -> [2D][R]
-    wn_launch_transpose(st, fw + o.fg + (size_t)R * 2 * D, (long long)2 * R * 2 * D, ws + t.fgb1, R, 2 * D, NL);
+    for (int tap = 0; tap < pl.k; ++tap)   // tap j's rows of every layer -> [2D][R], block j of the workspace (fgb0, fgb1, ...)
+        wn_launch_transpose(st, fw + o.fg + (size_t)tap * R * 2 * D, (long long)pl.k * R * 2 * D, ws + t.fgb0 + (size_t)tap * (t.fgb1 - t.fgb0), R, 2 * D, NL);
     const int G = t.G;
     const bool bf16 = h->fw_bf16 && h->w.fwb_ok;
     t.bf16 = bf16;
@@ -451,7 +461,12 @@ extern "C" int wn_train_forward(wn_handle* h, const float* params, const int32_t
         }
         // (bf16 step, the 128/128 shape: both products of the layer in one launch, z handed over in LDS -- wn_fwd_layer_bf16)
         const bool fused = bf16 && l < NL - 1 && wn_launch_layer(st, a, bt_fg + (size_t)l * 2 * D * 2 * R, ar, bt_res + (size_t)l * R * D);
-        if (!fused) {
+        if (pl.k != 2) {   // kernel_size 3, 4 (fp32 operands): the k views of x are formed in the kernel; the same epilogue, gates saved, z into Z_b
+            WnTapsArgs at = wn_layer_fg_taps(pl, o, fw, l, wn_rows(xin, L, R, t0), d, zmap, N, rows, 0);
+            at.g.gate_t = a.gate_t; at.g.gate_g = a.gate_g;
+            wn_launch_taps(st, pl.k, at);
+            if (l < NL - 1) wn_launch_nn(st, WN_EPI_PLAIN, ar);
+        } else if (!fused) {
             wn_launch_nn(st, WN_EPI_GATE, a, bf16 ? bt_fg + (size_t)l * 2 * D * 2 * R : nullptr);
             if (l < NL - 1) wn_launch_nn(st, WN_EPI_PLAIN, ar, bf16 ? bt_res + (size_t)l * R * D : nullptr);
         }
@@ -644,7 +659,13 @@ extern "C" int wn_train_backward(wn_handle* h, const float* params, const float*
         g.a1 = wn_rows(xop, L, R, t0); g.ka_split = R;
         g.a_bf16 = shadow ? 1 : 0; g.b_bf16 = t.bf16 ? 1 : 0;
         g.a_skip_lo = (int)t.zlo[l];   // tap 0 on the rows where the forward read a pad zero: no contribution
-        if (R % 128 == 0) {
+        if (pl.k != 2) {   // kernel_size 3, 4: one single-view product per tap -- view x_l(t - (k-1-j) d), rows j R .. of the gradient (every tap exists: wn_train_layout_ws)
+            for (int tap = 0; tap < pl.k; ++tap) {
+                WnGemmTnArgs g1 = wn_tn(wn_rows(xin, L, R, t0 - (long long)(pl.k - 1 - tap) * d), R, dfg_map, 2 * D,
+                                        grads + o.fg + ((size_t)l * pl.k + tap) * R * 2 * D, 2 * D, M, rows);
+                wn_launch_tn(sd, g1, false);
+            }
+        } else if (R % 128 == 0) {
             wn_launch_tn(sd, g, t.bf16);
         } else
         for (int tap = 0; tap < 2; ++tap) {
@@ -670,7 +691,11 @@ extern "C" int wn_train_backward(wn_handle* h, const float* params, const float*
         a.a_skip_lo[0] = (int)sh; a.a_skip_hi[1] = (int)d; a.a_bf16 = t.bf16 ? 1 : 0;
         a.bt1 = ws + t.fgb0 + (size_t)l * 2 * D * R;
         if (has_res) { a.cin = wn_rows(dxn, L, R, t0 - sh); a.cin_skip_lo = (int)sh; }
-        {
+        if (pl.k != 2) {   // kernel_size 3, 4: the k forward-shifted views of dfg against the k transposed tap blocks, one launch (wn_bwd_gemm_taps)
+            wn_launch_taps_bwd(st, pl.k, wn_layer_dx_taps(pl, dfg, rows, rows_l, d, ws + t.fgb0 + (size_t)l * 2 * D * R, (long long)(t.fgb1 - t.fgb0),
+                                                          has_res ? wn_rows(dxn, L, R, t0 - sh) : WnRowMap{nullptr, 0, 0, 0}, wn_rows(dxc, L, R, t0 - sh), N));
+            have_dfg = false;
+        } else {
             const unsigned short* w = bw ? bw + o.fg + (size_t)l * 2 * R * 2 * D : nullptr;  // native [2R][2D]: rows 0..R-1 tap 0, R.. tap 1
             // bf16 step, the 128 / 128 shape: this product and layer l - 1's gate-derivative product (same rows, dx_l as its A operand) are
             // ONE launch -- dx_l is handed over in LDS (wn_bwd_layer_bf16).  Layer l - 1's waits move in front of it.

@@ -21,18 +21,19 @@ from .params import PARAM_ORDER, SINGLE_KEYS  # noqa: F401  (read by the tests a
 class StackLayout:
     """The flat GEMM layout of wn_train_layout for one channel shape, and the reference Conv1d layouts <-> it in torch ops: needs no engine."""
 
-    def __init__(self, NL, R, D, S, E, C, bias, total, off, device):
+    def __init__(self, NL, R, D, S, E, C, bias, total, off, device, k=2):
+        """k: kernel_size -- the filter / gate section is [NL][k R][2D], tap j (0 = the oldest) in rows j R .. (j+1) R - 1 of a layer."""
         self.NL, self.R, self.D, self.S, self.E, self.C, self.bias = NL, R, D, S, E, C, bool(bias)
-        self.total, self.off, self.device = total, off, device
+        self.total, self.off, self.device, self.k = total, off, device, int(k)
 
     def sizes(self):
         NL, R, D, S, E, C = self.NL, self.R, self.D, self.S, self.E, self.C
-        return {"fg": NL * 2 * R * 2 * D, "bfg": NL * 2 * D, "res": NL * D * R, "bres": NL * R, "skip": NL * D * S,
+        return {"fg": NL * self.k * R * 2 * D, "bfg": NL * 2 * D, "res": NL * D * R, "bres": NL * R, "skip": NL * D * S,
                 "bskip": NL * S, "bskip_total": S, "w1": S * E, "b1": E, "w2": E * C, "b2": C, "start_t": C * R, "start_b": R}
 
     def pack(self, p):
         """p: {key: tensor} of the keys of params.order(bias), the per-layer ones stacked over the layers (params.stacked)."""
-        NL, R, D, S, E, C = self.NL, self.R, self.D, self.S, self.E, self.C
+        NL, R, D, S, E, C, k = self.NL, self.R, self.D, self.S, self.E, self.C, self.k
         flat = torch.zeros(self.total, dtype=torch.float32, device=self.device)
         sz, off = self.sizes(), self.off
 
@@ -40,7 +41,7 @@ class StackLayout:
             flat[off[name]:off[name] + sz[name]] = t.reshape(-1)
 
         fg = torch.stack([p["filter_w"], p["gate_w"]], dim=1)                       # (NL, gate, D, R, tap)
-        fg = fg.reshape(NL, 2, D // 32, 32, R, 2).permute(0, 5, 4, 2, 1, 3)         # (NL, tap, R, grp, gate, c32)
+        fg = fg.reshape(NL, 2, D // 32, 32, R, k).permute(0, 5, 4, 2, 1, 3)         # (NL, tap, R, grp, gate, c32)
         put("fg", fg)
         put("res", p["res_w"].reshape(NL, R, D).transpose(1, 2))
         put("skip", p["skip_w"].reshape(NL, S, D).transpose(1, 2))
@@ -59,13 +60,13 @@ class StackLayout:
 
     def unpack(self, flat):
         """Inverse of pack() (used for gradients): flat -> dict of tensors in the reference layouts."""
-        NL, R, D, S, E, C = self.NL, self.R, self.D, self.S, self.E, self.C
+        NL, R, D, S, E, C, k = self.NL, self.R, self.D, self.S, self.E, self.C, self.k
         sz, off = self.sizes(), self.off
 
         def get(name):
             return flat[off[name]:off[name] + sz[name]]
 
-        fg = get("fg").reshape(NL, 2, R, D // 32, 2, 32).permute(0, 4, 3, 5, 2, 1).reshape(NL, 2, D, R, 2)  # (NL, gate, D, R, tap)
+        fg = get("fg").reshape(NL, k, R, D // 32, 2, 32).permute(0, 4, 3, 5, 2, 1).reshape(NL, 2, D, R, k)  # (NL, gate, D, R, tap)
         out = {"filter_w": fg[:, 0].contiguous(), "gate_w": fg[:, 1].contiguous(),
                "res_w": get("res").reshape(NL, D, R).transpose(1, 2).reshape(NL, R, D, 1).contiguous(),
                "skip_w": get("skip").reshape(NL, D, S).transpose(1, 2).reshape(NL, S, D, 1).contiguous(),
@@ -91,7 +92,8 @@ class StackRunner(StackLayout):
         engine.lib.check(engine.lib.dll.wn_train_get_layout(engine._h, ctypes.byref(lay)))
         c = engine.cfg
         super().__init__(c["layers"] * c["blocks"], c["residual_channels"], c["dilation_channels"], c["skip_channels"], c["end_channels"],
-                         c["classes"], c.get("bias", False), int(lay.total), {n: int(getattr(lay, n)) for n in _abi.TRAIN_SECTIONS}, engine.mem.device)
+                         c["classes"], c.get("bias", False), int(lay.total), {n: int(getattr(lay, n)) for n in _abi.TRAIN_SECTIONS}, engine.mem.device,
+                         k=c.get("kernel_size", 2))
         self.ticket = 0
         self._flat = None        # the packed parameters of the step in flight (one buffer per model: stable addresses)
         self._gflat = None       # the flat gradient wn_train_backward writes

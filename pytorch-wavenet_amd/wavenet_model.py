@@ -17,7 +17,7 @@ What is different underneath:
     behind a torch.autograd.Function when gradients are wanted) -- including clips shorter than receptive_field +
     output_length - 1, where the reference left-pads the layers' activations with zeros (wavenet_modules.py:24-27: per-layer row
     windows in the kernels).  The reference's algorithm with torch ops remains for: CPU tensors, inputs that are not one-hot,
-    gradients w.r.t. the input, kernel_size != 2, a class count that is not a multiple of 32 under autograd (channel counts that are not
+    gradients w.r.t. the input, kernel_size != 2 (kernel_size 3 and 4 run natively where ``native_taps_training`` is switched on: see the class), a class count that is not a multiple of 32 under autograd (channel counts that are not
     multiples of 32 run natively, zero-padded: with and, since round 6, under autograd), and the input lengths for which the reference itself has no defined result (its error, or its shapes, are reproduced).
 """
 import collections
@@ -72,6 +72,12 @@ class WaveNetModel(nn.Module):
         dtype:                      Parameter type of this model (legacy tensor type object or torch.dtype)
         bias (Bool):                Whether the stack convolutions carry a bias
     """
+
+    # Extension, opt-in: True = forward() on a one-hot CUDA tensor and train_forward_indices() of a kernel_size 3 or 4 model whose channel counts and
+    # class count are multiples of 32 run on the matrix cores too (fp32: wn_forward without autograd, wn_train_forward / wn_train_backward with it)
+    # instead of the torch path.  A CLASS attribute, so that reference pickles and snapshots written before it existed load unchanged; set it on the
+    # class or on an instance (an instance's value travels with its pickle).  False: every path, message and warning is as before.
+    native_taps_training = False
 
     def __init__(self, layers=10, blocks=4, dilation_channels=32, residual_channels=32, skip_channels=256,
                  end_channels=256, classes=256, output_length=32, kernel_size=2, dtype=torch.FloatTensor, bias=False):
@@ -154,20 +160,25 @@ class WaveNetModel(nn.Module):
 
     def _native_indices_supported(self):
         """Shapes the index-based inference extensions cover (forward_indices / score_indices: wn_forward / wn_score): kernel_size 2, 3 or 4,
-        channel counts multiples of 32.  forward() on a one-hot tensor and training stay on torch ops for kernel_size != 2."""
+        channel counts multiples of 32.  forward() on a one-hot tensor and training stay on torch ops for kernel_size != 2 unless native_taps_training is on."""
         return self.kernel_size in (2, 3, 4) and not any(c % 32 for c in (self.residual_channels, self.dilation_channels, self.skip_channels,
                                                                             self.end_channels, self.classes))
 
     def _native_trainable(self):
-        """Shapes the native training step covers: kernel_size 2 and a class count that is a multiple of 32 -- channel counts that are not multiples
+        """Shapes the native training step covers by default (kernel_size 3 and 4 are opt-in: _native_taps_trainable): kernel_size 2 and a class count that is a multiple of 32 -- channel counts that are not multiples
         of 32 are zero-padded up to multiples of 64 for it (round 6: mi355_wavenet/training.py StackRunner.pad_tensors, shapes from mi355_wavenet/params.py; same logits, same gradients)."""
         return self.kernel_size == 2 and self.classes % 32 == 0
+
+    def _native_taps_trainable(self):
+        """Opted in (native_taps_training) and a shape the k-tap training step covers: kernel_size 3 or 4, channel counts and classes multiples of 32
+        (no zero padding for kernel_size != 2)."""
+        return bool(self.native_taps_training) and self.kernel_size in (3, 4) and self._native_indices_supported()
 
     def _padded_train_config(self):
         """(config, model shape) of the training engine: the model's own when its channel counts are multiples of 32, else padded to multiples of 64
         (so that the bf16 step's kernels apply as well)."""
         cfg = self._config()
-        if self._native_supported():
+        if self._native_supported() or self._native_taps_trainable():
             return cfg, None
         shape = (self.residual_channels, self.dilation_channels, self.skip_channels, self.end_channels)
         up = lambda c: (c + 63) // 64 * 64  # noqa: E731
@@ -204,15 +215,19 @@ class WaveNetModel(nn.Module):
             return None   # the reference's own path: nothing to report
         if input.dim() != 3 or input.size(1) != self.classes:
             return self._fallback("input is not (N, classes, L)")
-        if self.kernel_size != 2:
+        taps = self._native_taps_trainable()
+        if self.kernel_size != 2 and not taps:
+            if self.native_taps_training and self.kernel_size in (3, 4):
+                return self._fallback("kernel_size %d with channel counts or classes that are not multiples of 32 (no zero padding for kernel_size != 2)"
+                                      % self.kernel_size)
             return self._fallback("kernel_size %d (the matrix-core kernels are written for 2)" % self.kernel_size)
         want_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
         # Without autograd the engine decides: a channel shape that is not a multiple of 32 may still run natively, zero-padded into a
         # compiled shape (include/wn_abi.h: wn_create); with autograd the handle keeps the model's own shape and needs the multiples.
         no_native = self._wn_forward_unsupported == self._forward_shape_key(input.device)
-        if want_grad and not self._native_trainable():
+        if want_grad and not taps and not self._native_trainable():
             return self._fallback("a class count that is not a multiple of 32 under autograd")
-        if not want_grad and no_native and not self._native_supported():
+        if not want_grad and no_native and not taps and not self._native_supported():
             return self._fallback("channel counts that are not multiples of 32 and fit no compiled shape")
         if torch.is_grad_enabled() and input.requires_grad:
             return self._fallback("a gradient with respect to the one-hot input is wanted")
@@ -295,8 +310,8 @@ class WaveNetModel(nn.Module):
         idx = torch.as_tensor(indices)
         if idx.dim() != 2:
             raise ValueError("indices must be (N, L) class indices")
-        if training and self._native_trainable():
-            pass   # (the training engine pads odd channel counts itself)
+        if training and (self._native_trainable() or self._native_taps_trainable()):
+            pass   # (kernel_size 2: the training engine pads odd channel counts itself; 3, 4: opted in, multiples of 32)
         elif training and self.kernel_size != 2:
             raise ValueError("the index-based training forward needs kernel_size 2 (kernel_size %d: inference only, forward_indices / "
                              "score_indices)" % self.kernel_size)
