@@ -97,13 +97,20 @@ static __device__ __forceinline__ float wn_exp(float x) {
 #define WN_STAMPS 8
 // Stamps are parked in LDS (one ds_write, no vector-memory traffic on the critical path) and flushed to HBM by
 // wn_stamp_flush at the end of the step.
+// DIAG is a compile-time property of the kernel (the host launches the DIAG instantiation for a job with stamps or a logits dump, wn_chain_launch): in the
+// product instantiation the stamps do not exist -- as run-time tests of r.prof each was an exec-mask save + branch pair on the token's path, the
+// stamp body laid out inline (profiles/r12_lean_item_loops.txt).
+template <bool DIAG>
 static __device__ __forceinline__ void wn_stamp(const WnRun& r, long long* park, long long item, int k, bool cx_single = false) {
+    if constexpr (!DIAG) return;
     if (r.prof && item < r.prof_items && threadIdx.x == 0) {
         park[k] = (long long)wall_clock64();
         if (k == 0 && cx_single) park[6] = (long long)clock64();  // shader clock, to read the effective MHz off the stamps
     }
 }
+template <bool DIAG>
 static __device__ __forceinline__ void wn_stamp_flush(const WnRun& r, const long long* park, int w, long long item) {
+    if constexpr (!DIAG) return;
     if (r.prof && item < r.prof_items && threadIdx.x == 0) {
         long long* dst = r.prof + ((size_t)w * r.prof_items + item) * WN_STAMPS;
 #pragma unroll

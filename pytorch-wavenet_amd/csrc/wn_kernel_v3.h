@@ -439,7 +439,17 @@ static __device__ __forceinline__ void wn_dot_lds_gp(const float (&w)[K], const 
     }
 }
 
-template <class SH, int P, int G, int SK = 0>
+// Weights resident before the item loop.  The register-resident weights and biases of a group are loaded once, in front of its loop; the compiler's
+// wait-count pass nonetheless carried them into the loop body as "possibly still in flight" (the loop header merges the entry state with the back
+// edge), and every first use of a weight register in an item got an s_waitcnt vmcnt(n) -- which in steady state waits for the item's own younger
+// polls and for earlier stores' acknowledgements, not for weights.  One full wait the pass can see (the builtin is a real S_WAITCNT, unlike a wait
+// inside inline assembly) in front of the loop clears its scoreboard: profiles/r12_lean_item_loops.txt.  In the critical and the queue group, whose item
+// loops issue vector-memory loads only from hand-scheduled blocks; the skip group, the head and the sampler load through the compiler in every item.
+static __device__ __forceinline__ void wn_weights_resident() { __builtin_amdgcn_s_waitcnt(0); }
+// compile-time bool as a function argument (the store flavour of a publication, the host's choice of the DIAG instantiation)
+template <bool B> struct WnBool { static constexpr bool value = B; };
+
+template <class SH, int P, int G, int SK = 0, bool DIAG = false>
 static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds, int l, int c) {
     constexpr int R = SH::R, DC = SH::DC, S = SH::S, T1 = SH::T1, K1 = SH::K1, T2 = SH::T2, K2 = SH::K2, RS = SH::RS;
     using L = WnV3Lds<SH, G>;
@@ -481,7 +491,12 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
         locflags[0] = lx; locflags[1] = lsk; locflags[2] = lup; locflags[3] = lcons;
     }
     __syncthreads();
-    const bool local_x = locflags[0] != 0, local_s = locflags[1] != 0;
+    // The store flavours are workgroup-uniform and fixed at start-up, but they come out of LDS: read as they are the compiler takes them for lane-dependent,
+    // and every publication carried an exec-mask ladder (v_cndmask, v_cmp_ne, s_andn2, branch, s_mov, s_andn2, taken branch, s_and, branch) BETWEEN its two
+    // 16-byte stores -- stream b's x' left ~9 instructions and 1-2 taken branches after stream a's.  Through v_readfirstlane they are scalars: one s_cmp +
+    // s_cbranch per store pair.  (A copy of the item loop per flavour and layer position -- no test at all -- was tried first: the second copy of the
+    // critical loop alone made the allocator spill in the skip group of the cfg3 kernels, which sits at 152 registers: profiles/r12_lean_item_loops.txt.)
+    const bool local_x = __builtin_amdgcn_readfirstlane(locflags[0]) != 0, local_s = __builtin_amdgcn_readfirstlane(locflags[1]) != 0;
     const int n_prime = (int)(r.n_given - 1);
 
     // ---- fetching the layer's input (lanes t < G*R of the critical group): request (set A), first look, spin with two sets in flight, stage.
@@ -533,7 +548,9 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             look(tag2, sum, ok);  // (set A was re-requested at the end of the spin)
         }
         xb2[tg * L::XR + SH::xpad(tr)] = sum;
-        if (r.prof && item2 < r.prof_items && (tid & 255) == 0) park4[item2 & 1] = (long long)wall_clock64();
+        if constexpr (DIAG) {
+            if (r.prof && item2 < r.prof_items && (tid & 255) == 0) park4[item2 & 1] = (long long)wall_clock64();
+        }
     };
     // the first evaluation's input of layer 0 is a given sample: start_conv row gather (wavenet_model.py:127, 256-257)
     auto given_input = [&](int s2, float* xb2) {
@@ -587,6 +604,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
         const float res_m = (c == 0 && kq2 == 0) ? 1.f : 0.f;   // (the lane that adds x[t] to its row of the residual partial: wavenet_model.py:165)
         long long* park = reinterpret_cast<long long*>(lds + L::park);
         const __amdgpu_buffer_rsrc_t rs_gx = wn_rsrc(p.gx);
+        wn_weights_resident();
         if (poller) request(0);
         int buf = 0;
         for (long long e = 0; e < r.n_eval; ++e) {
@@ -594,7 +612,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             for (int s = 0; s < ns; s += G, buf ^= 1) {
                 float* xb = xs + buf * (G * L::XR);  // [G][XR]
                 const long long item = e * nI + s / G;
-                wn_stamp(r, park, item, 0);
+                wn_stamp<DIAG>(r, park, item, 0);
                 // ---- 1. layer input x[t] of the item's G streams
                 if (l == 0 && e == 0) { if (poller) given_input(s, xb); }
                 else if (poller) {  // (set A was requested at the end of the previous item)
@@ -604,7 +622,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                     finish_input(e, s, xb, sum, ok, item);
                 }
                 const int fail_a = wn_barrier_flag(cx, failflag);  // ---- A(i): x staged
-                wn_stamp(r, park, item, 1);
+                wn_stamp<DIAG>(r, park, item, 1);
                 // ---- 2. filter/gate: tap 1 on x[t] + parked tap 0, tanh * sigmoid   (wavenet_model.py:147-151)
                 // (the G streams' chains are kept in ONE basic block -- unconditional LDS reads, selects instead of lane-predicated
                 //  branches, the z stores after both chains -- so that the scheduler can interleave them: a predicated store between
@@ -671,7 +689,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                 }
                 if (fail_a) return;
                 const int fail_b = wn_barrier_flag(cx, failflag);  // ---- B(i): z staged
-                wn_stamp(r, park, item, 5);
+                wn_stamp<DIAG>(r, park, item, 5);
                 // ---- 3. residual 1x1 partial, published at once                      (wavenet_model.py:164-165)
                 if (l < NL - 1) {
                     float a2[G], zero[G], xn[G];
@@ -686,23 +704,32 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                         float xn1[G];
 #pragma unroll
                         for (int g = 0; g < G; ++g) xn1[g] = wn_dpp<0x4E>(xn[g]);  // quad_perm [2,3,0,1]
-                        if ((t & 3) == 0) {
+                        // (the uniform test of the flavour OUTSIDE the lane predicate: inside it the structurizer turns it into exec-mask arithmetic between the stores)
+                        auto publish = [&](auto lx_c) __attribute__((always_inline)) {
+                            if ((t & 3) == 0) {
 #pragma unroll
-                            for (int g = 0; g < G; ++g) wn_st_pair(rs_gx, (unsigned)((((size_t)cx.w * ns + s + g) * R + row2) * 8), tag, xn[g], xn1[g], local_x);
-                        }
+                                for (int g = 0; g < G; ++g) wn_st_pair(rs_gx, (unsigned)((((size_t)cx.w * ns + s + g) * R + row2) * 8), tag, xn[g], xn1[g], decltype(lx_c)::value);
+                            }
+                        };
+                        if (local_x) publish(WnBool<true>{}); else publish(WnBool<false>{});
                     } else {
-                        if (kq2 == 0) {
+                        auto publish = [&](auto lx_c) __attribute__((always_inline)) {
+                            if (kq2 == 0) {
 #pragma unroll
-                            for (int g = 0; g < G; ++g) wn_publish_at(p.gx + ((size_t)cx.w * ns + s + g) * R + row2, tag, xn[g], local_x);
-                        }
+                                for (int g = 0; g < G; ++g) wn_publish_at(p.gx + ((size_t)cx.w * ns + s + g) * R + row2, tag, xn[g], decltype(lx_c)::value);
+                            }
+                        };
+                        if (local_x) publish(WnBool<true>{}); else publish(WnBool<false>{});
                     }
                 }
-                wn_stamp(r, park, item, 2);
-                wn_stamp(r, park, item, 3);
-                if (r.prof && item < r.prof_items && tid == 0) {  // slots 0-5 (6 and 7 belong to the skip and queue groups)
-                    long long* dst = r.prof + ((size_t)cx.w * r.prof_items + item) * WN_STAMPS;
+                wn_stamp<DIAG>(r, park, item, 2);
+                wn_stamp<DIAG>(r, park, item, 3);
+                if constexpr (DIAG) {
+                    if (r.prof && item < r.prof_items && tid == 0) {  // slots 0-5 (6 and 7 belong to the skip and queue groups)
+                        long long* dst = r.prof + ((size_t)cx.w * r.prof_items + item) * WN_STAMPS;
 #pragma unroll
-                    for (int k = 0; k < 6; ++k) dst[k] = k == 4 ? park4[item & 1] : park[k];
+                        for (int k = 0; k < 6; ++k) dst[k] = k == 4 ? park4[item & 1] : park[k];
+                    }
                 }
                 if (poller) request(s + G < ns ? s + G : 0);  // set A of the coming item
                 if (fail_b) return;
@@ -800,7 +827,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             const uint32_t tag = (uint32_t)(e + 1);
             for (int s = 0; s < ns; s += G, ++item) {
                 if (wn_barrier_failed(cx, failflag)) return;  // ---- B(i): z of this item staged
-                const bool stamp = r.prof && item < r.prof_items && tid == 256;
+                const bool stamp = DIAG && r.prof && item < r.prof_items && tid == 256;
                 const long long t0 = stamp ? (long long)wall_clock64() : 0;
                 const int s2 = s + G < ns ? s + G : 0;  // the coming item's first stream
                 const int slot2 = NSLOT > 0 && slot + 1 < NSLOT ? slot + 1 : 0;
@@ -896,15 +923,20 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                             }
                         }
                     }
+                    float nb[G];
 #pragma unroll
-                    for (int g = 0; g < G; ++g) {
+                    for (int g = 0; g < G; ++g) nb[g] = ODD ? wn_dpp<0xB1>(a3[g][RS - 1]) : 0.f;  // quad_perm [1,0,3,2]: the odd neighbour's row
+                    auto publish = [&](auto ls_c) __attribute__((always_inline)) {   // (one test of the flavour for all the lane's stores of the item)
 #pragma unroll
-                        for (int h2 = 0; h2 < NPL; ++h2) wn_st_pair(rs_gs, base_me + g * SB + h2 * 4096 + lane16, tag_out, a3[g][2 * h2], a3[g][2 * h2 + 1], local_s);
-                        if constexpr (ODD) {
-                            const float nb = wn_dpp<0xB1>(a3[g][RS - 1]);  // quad_perm [1,0,3,2]: the odd neighbour's row
-                            if ((t & 1) == 0) wn_st_pair(rs_gs, base_me + g * SB + odd_st, tag_out, a3[g][RS - 1], nb, local_s);
+                        for (int g = 0; g < G; ++g) {
+#pragma unroll
+                            for (int h2 = 0; h2 < NPL; ++h2) wn_st_pair(rs_gs, base_me + g * SB + h2 * 4096 + lane16, tag_out, a3[g][2 * h2], a3[g][2 * h2 + 1], decltype(ls_c)::value);
+                            if constexpr (ODD) {
+                                if ((t & 1) == 0) wn_st_pair(rs_gs, base_me + g * SB + odd_st, tag_out, a3[g][RS - 1], nb[g], decltype(ls_c)::value);
+                            }
                         }
-                    }
+                    };
+                    if (local_s) publish(WnBool<true>{}); else publish(WnBool<false>{});
                 }
                 if (stamp)  // slot 6: the skip group's B(i) | its chunk length << 40 (10 ns ticks)
                     r.prof[((size_t)cx.w * r.prof_items + item) * WN_STAMPS + 6] = (t0 & 0xffffffffffll) | (((long long)wall_clock64() - t0) << 40);
@@ -993,6 +1025,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
         for (int k = 0; k < K1; ++k) acc += img[(size_t)(K1 + k) * 256] * ring[(size_t)pos * R + kq1 * K1 + k];  // (once per job: the weights straight from the image)
         pre[s * 256 + t] = acc;
     }
+    wn_weights_resident();
     float* rings_l = p.rings + p.ring_off[l] + (size_t)c * ns * (size_t)ML * R;  // stream s: + s * ML * R
     int tmod = (int)(r.t_base % ML);  // queue slot of x[t] of the current item, kept incrementally
     // ---- Few streams: the layer's dilation queues live in LDS (round 3; wavenet_modules.py:42-77).  One stream leaves the workgroup's
@@ -1013,7 +1046,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             for (int s = 0; s < ns; ++s, bufq ^= 1, ++itemq) {
                 float* ring_s = lring + (size_t)s * ML * L::XR;
                 if (wn_barrier_failed(cx, failflag)) return;  // ---- A(i): x of this item staged
-                const bool stamp = r.prof && itemq < r.prof_items && tid == 512;
+                const bool stamp = DIAG && r.prof && itemq < r.prof_items && tid == 512;
                 const long long t0 = stamp ? (long long)wall_clock64() : 0;
                 if (t < R) ring_s[tmod * L::XR + xq1] = xs[bufq * L::XR + xq1];  // the push (wavenet_modules.py:55-57)
                 if (wn_barrier_failed(cx, failflag)) return;  // ---- B(i)
@@ -1085,7 +1118,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             float* xo_cur = (late_wg && (item & 1)) ? xol1 : xol;
             float* xo_nxt = (item & 1) ? xol : xol1;
             if (wn_barrier_failed(cx, failflag)) return;  // ---- A(i): x of this item staged
-            const bool stamp = r.prof && item < r.prof_items && tid == 512;
+            const bool stamp = DIAG && r.prof && item < r.prof_items && tid == 512;
             const long long t0 = stamp ? (long long)wall_clock64() : 0;
             if (TAP_A && late) wn_q_issue_slot(slot, q_next);  // the tap of item i + D goes into the entry item i gave up at the end of item i - 1
             // ---- queue push (wavenet_modules.py:55-57); stage the tap x[t+1-d] (d = 1: it is x[t] itself)
@@ -1168,7 +1201,7 @@ static __device__ __forceinline__ float wn_dot_lds_chunked(const float (&w)[K], 
 // p.HR replicas of the PA head workgroups share the streams (replica j serves the streams s = j mod HR): a head workgroup's cycle
 // per stream (compute 0.53 us + the round trip of its publication) is the slowest stage once the layer workgroups process two
 // streams per item -- and the chain leaves 44 of the 256 CUs unused.
-template <class SH, int P>
+template <class SH, int P, bool DIAG = false>
 static __device__ void wn_v3_head(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds, int hw) {
     constexpr int S = SH::S, EC = SH::EC, T3 = SH::T3, K3 = SH::K3, QS = S / 256;
     constexpr int CH3 = (K3 / 4) % 4 == 0 ? 4 : (K3 / 4) % 2 == 0 ? 2 : 1;  // (float4 reads of the long dot in flight together)
@@ -1214,7 +1247,7 @@ static __device__ void wn_v3_head(const WnPlan& p, const WnRun& r, WnCtx& cx, fl
         locflags[0] = p.allow_plain ? (int)wn_same_xcd(cx, mine, p.n_lw + p.PA * p.HR, p.n_smp) : 0;  // logits feed the samplers
     }
     wn_lds_barrier();
-    const bool local_l = locflags[0] != 0;
+    const bool local_l = __builtin_amdgcn_readfirstlane(locflags[0]) != 0;   // (a scalar: see wn_v3_layer)
     const __amdgpu_buffer_rsrc_t rs_gs = wn_rsrc(p.gs);
     // The P lanes of the running skip sum (published by the last layer's skip groups; layout: see the skip group) of the NEXT item are
     // requested early (after this item's long dot): with tokens queued in front of it the head's cycle would otherwise be compute PLUS a
@@ -1241,7 +1274,7 @@ static __device__ void wn_v3_head(const WnPlan& p, const WnRun& r, WnCtx& cx, fl
         const uint32_t tag = (uint32_t)(e + 1);
         for (int s = rep; s < ns; s += HR) {
             const long long item = e * n_mine + (s - rep) / HR;
-            wn_stamp(r, park, item, 0);
+            wn_stamp<DIAG>(r, park, item, 0);
             // (this item's stream: requested for it one item ago.)  Stale lanes are re-requested TOGETHER until all carry the tag: polled
             // one by one, every late lane cost a round trip of its own -- with nothing queued in front of the head (latency-bound runs)
             // that was 4 x ~0.5 us between the last layer's publication and the head's first instruction (profiles/archive/r03_ring_tail.txt)
@@ -1281,7 +1314,7 @@ static __device__ void wn_v3_head(const WnPlan& p, const WnRun& r, WnCtx& cx, fl
                 sk[SH::skpad(256 * (QS - 1) + tid)] = sum > 0.f ? sum : 0.f;
             }
             if (wn_barrier_failed(cx, failflag)) return;
-            wn_stamp(r, park, item, 1);
+            wn_stamp<DIAG>(r, park, item, 1);
             const unsigned gl_off = (unsigned)((((size_t)h * ns + s) * 256) * 8);  // (wave-uniform: the scalar offset of the store)
             auto publish_logit = [&](float v) {
                 const wn_v2i d = {__float_as_int(v), (int)tag};
@@ -1337,10 +1370,10 @@ static __device__ void wn_v3_head(const WnPlan& p, const WnRun& r, WnCtx& cx, fl
                 request(s + HR < ns ? s + HR : rep);
                 publish_logit(0.f);
             }
-            wn_stamp(r, park, item, 2);
+            wn_stamp<DIAG>(r, park, item, 2);
             wn_lds_barrier();
-            wn_stamp(r, park, item, 3);
-            wn_stamp_flush(r, park, cx.w, item);
+            wn_stamp<DIAG>(r, park, item, 3);
+            wn_stamp_flush<DIAG>(r, park, cx.w, item);
         }
     }
 }
@@ -1492,7 +1525,7 @@ static __device__ __forceinline__ void wn_poll_class(WnCtx& cx, __amdgpu_buffer_
 // the caller lets the workgroup's first FOUR waves in, thread c collects class c from every slice (8-byte loads, 16 in flight), the
 // sums meet in LDS (lds_lg, 256 floats) and wave 0 draws as in the one-wave form -- same sums in the same order, two LDS barriers more.
 // (Variant 4 takes WIDE from eight head slices up, wn_kernel_v4.h; in variant 3 it was level and is not used: profiles/r04_sampler_prefetch_and_wide_sampler.txt.)
-template <class SH, bool WIDE = false>
+template <class SH, bool WIDE = false, bool DIAG = false>
 static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds_smp, float* lds_tab, int j, float* lds_lg = nullptr) {
     constexpr int R = SH::R, NP = (R / 2 + 63) / 64;  // pairs of row elements per lane
     constexpr int NT = WIDE ? 256 : 64;
@@ -1502,7 +1535,7 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
     if (WIDE && threadIdx.x == 0) *failflag = 0;
     const int mine = wn_xcc_id();
     if (lane == 0) __hip_atomic_store(p.xcc_tab + cx.w, (unsigned)(mine + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const bool local_i = p.allow_plain && wn_same_xcd(cx, mine, 0, p.P);  // the row feeds every slice of layer 0  (wave-uniform)
+    const bool local_i = __builtin_amdgcn_readfirstlane((int)(p.allow_plain && wn_same_xcd(cx, mine, 0, p.P))) != 0;  // the row feeds every slice of layer 0  (wave-uniform)
     const __amdgpu_buffer_rsrc_t rs_g0 = wn_rsrc(p.g0), rs_gl = wn_rsrc(p.gl);
     const float* tab = p.start_t;
     if (p.start_in_lds) {
@@ -1525,7 +1558,7 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
     for (long long e = 1; e <= r.n_eval; ++e) {
         for (int s = j; s < ns; s += p.n_smp) {
             const long long item = (e - 1) * ns + s;  // stamps (diagnostics): 0 start of the wait, 1 logits complete, 2 row published
-            wn_stamp(r, park, item, 0);
+            wn_stamp<DIAG>(r, park, item, 0);
             // The item's uniform (streamed from HBM, eight bytes per item) is requested BEFORE the wait for the logits: a global load behind
             // their arrival sat on the ring (a single stream's timestep is 8 - 20 us, an HBM miss is half a microsecond of it).  The
             // temperature and the given sample (kernel argument / L2 hits) stay behind the wait -- asking for them early as well raised
@@ -1561,7 +1594,7 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
                 if (p.PA - h >= 1) wn_poll_logits<1>(cx, rs_gl, lane32, h, s, ns, (uint32_t)e, e, logit);
                 if (cx.fail) return;
             }
-            wn_stamp(r, park, item, 1);
+            wn_stamp<DIAG>(r, park, item, 1);
             const float temp = r.stream_temps ? r.stream_temps[s + lane0] : r.temperature;
             const bool greedy = r.greedy != 0 || !(temp > 0.f);
             const int given = g < 0 ? r.first[(size_t)s * r.n_given + e + lane0] : 0;
@@ -1569,25 +1602,30 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
             if (g < 0) {
                 idx = given;
             } else {
-                if (r.dbg_logits) {
+                if constexpr (DIAG) {   // (a job that dumps its logits runs the DIAG instantiation: wn_chain_launch)
+                    if (r.dbg_logits) {
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) r.dbg_logits[((size_t)s * r.num_samples + g) * 256 + 4 * lane + k] = logit[k];
+                        for (int k = 0; k < 4; ++k) r.dbg_logits[((size_t)s * r.num_samples + g) * 256 + 4 * lane + k] = logit[k];
+                    }
                 }
                 idx = wn_sample_1w(r, logit, lane, u, greedy, temp);
                 if (lane == 0) r.out_idx[(size_t)s * r.num_samples + g] = idx;
             }
             if (e < r.n_eval) {
+                auto publish = [&](auto li_c) __attribute__((always_inline)) {   // (the uniform test of the flavour outside the lane predicate)
 #pragma unroll
-                for (int m = 0; m < NP; ++m) {
-                    const int pi = lane + 64 * m;
-                    if (2 * pi < R) {
-                        const float2 v = *reinterpret_cast<const float2*>(tab + (size_t)idx * R + 2 * pi);
-                        wn_st_pair(rs_g0, (unsigned)(((size_t)s * R + 2 * pi) * 8), (uint32_t)(e + 1), v.x + bias0[m][0], v.y + bias0[m][1], local_i);
+                    for (int m = 0; m < NP; ++m) {
+                        const int pi = lane + 64 * m;
+                        if (2 * pi < R) {
+                            const float2 v = *reinterpret_cast<const float2*>(tab + (size_t)idx * R + 2 * pi);
+                            wn_st_pair(rs_g0, (unsigned)(((size_t)s * R + 2 * pi) * 8), (uint32_t)(e + 1), v.x + bias0[m][0], v.y + bias0[m][1], decltype(li_c)::value);
+                        }
                     }
-                }
+                };
+                if (local_i) publish(WnBool<true>{}); else publish(WnBool<false>{});
             }
-            wn_stamp(r, park, item, 2);
-            wn_stamp_flush(r, park, cx.w, item);
+            wn_stamp<DIAG>(r, park, item, 2);
+            wn_stamp_flush<DIAG>(r, park, cx.w, item);
         }
     }
 }
@@ -1599,7 +1637,8 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
 // by construction, not by the luck of the allocator; the launch bound still gives every lane the 168 the blocks address).  On gfx90a and
 // later the backend DOUBLES the attribute's value (unified VGPR + AGPR file) before it compares it with the occupancy limit -- a value above
 // 84 is silently dropped at 3 waves per SIMD -- hence WN_V3_COMPILER_VGPRS / 2; build.py disassembles the library and checks the result.
-template <int R, int DC, int S, int EC, int P, int G = 1, int SK = 0>
+// DIAG: the instantiation with the wall-clock stamps (wn_profile_next) and the sampler's logits dump; the product instantiation has neither.
+template <int R, int DC, int S, int EC, int P, int G = 1, int SK = 0, bool DIAG = false>
 __global__ __launch_bounds__(WN_THREADS_V3) __attribute__((amdgpu_num_vgpr(WN_V3_COMPILER_VGPRS / 2)))
 void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
     using SH = WnV2Shape<R, DC, S, EC>;
@@ -1612,12 +1651,12 @@ void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
     if (wn_not_resident(cx, wn_lds3m)) return;   // (every workgroup of the job is resident from here on)
     const int n_layer_wg = p.NL * p.P;
     if (w < n_layer_wg) {
-        wn_v3_layer<SH, P, G, SK>(p, r, cx, wn_lds3m, w / P, w % P);
+        wn_v3_layer<SH, P, G, SK, DIAG>(p, r, cx, wn_lds3m, w / P, w % P);
         return;
     }
     if (threadIdx.x >= WN_THREADS) return;  // the head role is a 256-thread role, the sampler role a one-wave role
-    if (w < n_layer_wg + p.PA * p.HR) wn_v3_head<SH, P>(p, r, cx, wn_lds3m, w - n_layer_wg);
-    else if (threadIdx.x < 64) wn_v3_sampler<SH>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
+    if (w < n_layer_wg + p.PA * p.HR) wn_v3_head<SH, P, DIAG>(p, r, cx, wn_lds3m, w - n_layer_wg);
+    else if (threadIdx.x < 64) wn_v3_sampler<SH, false, DIAG>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
 }
 
 #endif  // WN_KERNEL_V3_H

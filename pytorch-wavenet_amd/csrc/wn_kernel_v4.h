@@ -79,7 +79,7 @@ static __device__ __forceinline__ float wn_ld_sc1(const float* p) {   // served 
     return __uint_as_float(__hip_atomic_load(reinterpret_cast<const unsigned*>(p), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
-template <class V, int LPW>
+template <class V, int LPW, bool DIAG = false>
 static __device__ void wn_v4_stack(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds, int w) {
     constexpr int R = V::R, D = V::D, S = V::S, KF = V::KF, KR = V::KR, KS = V::KS, RS = V::RS, XP = V::XP, ZP = V::ZP;
     constexpr int NPL = RS / 2, ODD = RS % 2, NPR = NPL + ODD, NWS = RS * KS / 2;
@@ -105,7 +105,9 @@ static __device__ void wn_v4_stack(const WnPlan& p, const WnRun& r, WnCtx& cx, f
     // diagnostics (wn_profile_next): stamps of an item -- 0 start of the wait, 1 input staged, 2 first layer done, 3 x' published (layers
     // done), 4 skip lane published, 5 item done (tap-0 sums of the next timestep parked)
     auto stamp = [&](long long item, int k) {
-        if (r.prof && item < r.prof_items && t == 0) park[k] = (long long)wall_clock64();
+        if constexpr (DIAG) {   // (the stamps exist in the DIAG instantiation only: wn_chain_regs.h, wn_stamp)
+            if (r.prof && item < r.prof_items && t == 0) park[k] = (long long)wall_clock64();
+        }
     };
     float4* w0l = reinterpret_cast<float4*>(lds + L::w0) + t;   // [(li * KF / 2 + k4) * 512]
 
@@ -399,10 +401,12 @@ static __device__ void wn_v4_stack(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             tap0_dots(s);   // the tap-0 half of the dilated convs of timestep t + 1
             wn_lds_barrier();
             stamp(item, 5);
-            if (r.prof && item < r.prof_items && t == 0) {
-                long long* dst = r.prof + ((size_t)cx.w * r.prof_items + item) * WN_STAMPS;
+            if constexpr (DIAG) {
+                if (r.prof && item < r.prof_items && t == 0) {
+                    long long* dst = r.prof + ((size_t)cx.w * r.prof_items + item) * WN_STAMPS;
 #pragma unroll
-                for (int k = 0; k < 6; ++k) dst[k] = park[k];
+                    for (int k = 0; k < 6; ++k) dst[k] = park[k];
+                }
             }
         }
 #pragma unroll
@@ -410,7 +414,7 @@ static __device__ void wn_v4_stack(const WnPlan& p, const WnRun& r, WnCtx& cx, f
     }
 }
 
-template <int R, int D, int S, int EC, int LPW>
+template <int R, int D, int S, int EC, int LPW, bool DIAG = false>
 __global__ __launch_bounds__(WN_THREADS_V4) void wn_generate_kernel_v4(WnPlan p, WnRun r) {
     using V = WnV4Shape<R, D, S>;
     using SH = WnV2Shape<R, D, S, EC>;   // head / sampler roles: variant 3's, on an unsplit stack
@@ -422,14 +426,14 @@ __global__ __launch_bounds__(WN_THREADS_V4) void wn_generate_kernel_v4(WnPlan p,
     cx.t_start = (long long)wall_clock64();
     if (wn_not_resident(cx, wn_lds4)) return;   // (every workgroup of the job is resident from here on)
     if (w < p.n_lw) {
-        wn_v4_stack<V, LPW>(p, r, cx, wn_lds4, w);
+        wn_v4_stack<V, LPW, DIAG>(p, r, cx, wn_lds4, w);
         return;
     }
     if (threadIdx.x >= WN_THREADS) return;  // the head role is a 256-thread role, the sampler role a one-wave (or, collecting many head slices, four-wave) role
-    if (w < p.n_lw + p.PA * p.HR) wn_v3_head<SH, 1>(p, r, cx, wn_lds4, w - p.n_lw);
+    if (w < p.n_lw + p.PA * p.HR) wn_v3_head<SH, 1, DIAG>(p, r, cx, wn_lds4, w - p.n_lw);
     else if (p.PA >= 8)   // many head slices: the sampler collects them with four waves (the head's staging area is free in this workgroup)
-        wn_v3_sampler<SH, true>(p, r, cx, wn_lds4 + WnV3Lds<SH, 1>::smp, wn_lds4 + WnV3Lds<SH, 1>::pre, w - p.n_lw - p.PA * p.HR, wn_lds4 + WnV3Lds<SH, 1>::sk);
-    else if (threadIdx.x < 64) wn_v3_sampler<SH>(p, r, cx, wn_lds4 + WnV3Lds<SH, 1>::smp, wn_lds4 + WnV3Lds<SH, 1>::pre, w - p.n_lw - p.PA * p.HR);
+        wn_v3_sampler<SH, true, DIAG>(p, r, cx, wn_lds4 + WnV3Lds<SH, 1>::smp, wn_lds4 + WnV3Lds<SH, 1>::pre, w - p.n_lw - p.PA * p.HR, wn_lds4 + WnV3Lds<SH, 1>::sk);
+    else if (threadIdx.x < 64) wn_v3_sampler<SH, false, DIAG>(p, r, cx, wn_lds4 + WnV3Lds<SH, 1>::smp, wn_lds4 + WnV3Lds<SH, 1>::pre, w - p.n_lw - p.PA * p.HR);
 }
 
 #endif  // WN_KERNEL_V4_H

@@ -115,9 +115,10 @@ struct WnV2Entry {
     // [form]: 0 = one stream per pipeline item of a layer workgroup, 1 = two (wn_v3_mode), 2 = two + skip-lane slot re-use (wn_v3_slots_for); NULL where
     // the shape has no such form
     const void* fn_v3[3];
+    const void* fn_v3_diag[3];   // the same forms with the stamps and the logits dump compiled in (DIAG: a job with wn_profile_next or dbg_logits)
     int (*lds_floats_v3)(int ns, int g2);
     int lds_pre_v3;  // float offset of the per-stream area = what head / sampler workgroups use in front of their own tables
-    void (*launch_v3)(int form, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
+    void (*launch_v3)(int form, bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
 };
 
 template <class SH>
@@ -173,12 +174,20 @@ static WnV2Entry wn_v2_entry() {
     WnV2Entry e;
     e.R = R; e.DC = DC; e.S = S; e.EC = EC; e.nwl = SH::NWL; e.nwh = SH::NWH; e.Pm = PM;
     e.pack = wn_pack_v2<SH>;
-    e.fn_v3[0] = e.fn_v3[1] = e.fn_v3[2] = nullptr; e.lds_floats_v3 = nullptr; e.launch_v3 = nullptr; e.lds_pre_v3 = 0;
+    e.fn_v3[0] = e.fn_v3[1] = e.fn_v3[2] = nullptr; e.fn_v3_diag[0] = e.fn_v3_diag[1] = e.fn_v3_diag[2] = nullptr; e.lds_floats_v3 = nullptr; e.launch_v3 = nullptr; e.lds_pre_v3 = 0;
     static_assert(wn_v3_fits<SH, PM>(), "every table entry runs the wave-specialised kernel");
     {
-        e.fn_v3[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1>;
-        if constexpr (wn_v3_g2_fits<SH>()) e.fn_v3[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2>;
-        if constexpr (wn_v3_g2_fits<SH>() && SK > 0) e.fn_v3[2] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK>;
+        e.fn_v3[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, false>;
+        e.fn_v3_diag[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, true>;
+        if constexpr (wn_v3_g2_fits<SH>()) {
+            e.fn_v3[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, false>;
+            e.fn_v3_diag[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, true>;
+        }
+        // The slot re-use form exists in ONE instantiation, the one that tests r.prof at run time: its product instantiation measured 7 % SLOWER than the
+        // parent's kernel on the jobs the form is for (cfg3 x 128: 1.45 M against 1.57 M; x 96: 1.37 against 1.43), this one 3 % faster (1.61 / 1.47 M) --
+        // the form is throughput bound, what the stamps cost is not on its path, and the compiler's schedule of the kernel without them is the worse one
+        // (profiles/r12_lean_item_loops.txt).
+        if constexpr (wn_v3_g2_fits<SH>() && SK > 0) e.fn_v3[2] = e.fn_v3_diag[2] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>;
         e.lds_pre_v3 = WnV3Lds<SH, 1>::pre;
         e.lds_floats_v3 = [](int ns, int g2) {
             int lay = WnV3Lds<SH, 1>::floats(ns);
@@ -189,14 +198,18 @@ static WnV2Entry wn_v2_entry() {
             if (smp * 4 <= WN_LDS_MAX_BYTES && smp > need) need = smp;
             return need;
         };
-        e.launch_v3 = [](int form, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
-            if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
-                if (form == 2) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
-            }
-            if constexpr (wn_v3_g2_fits<SH>()) {
-                if (form >= 1) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
-            }
-            hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 1>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r);
+        e.launch_v3 = [](int form, bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
+            auto go = [&](auto diag_c) {
+                constexpr bool DG = decltype(diag_c)::value;
+                if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
+                    if (form == 2) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
+                }
+                if constexpr (wn_v3_g2_fits<SH>()) {
+                    if (form >= 1) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, DG>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
+                }
+                hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, DG>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r);
+            };
+            if (diag) go(WnBool<true>{}); else go(WnBool<false>{});
         };
     }
     return e;
@@ -390,17 +403,23 @@ static void wn_free_weights(wn_handle* h) {   // (members i > 0 of a rounds fron
 }
 
 // The chain kernel a handle runs: its function (for the attribute and occupancy queries of wn_create), its workgroup size, its launch
+// (variants 3 and 4 exist twice: the product instantiation and the DIAG one -- wall-clock stamps, logits dump -- that a job with wn_profile_next or
+//  dbg_logits runs; the generic kernel tests at run time)
 struct WnChainKernel { const void* fn; int threads; };
-static WnChainKernel wn_chain_kernel(const wn_handle* h) {
-    if (h->variant == 4) return WnChainKernel{wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
-    if (h->variant == 3) return WnChainKernel{wn_v2_table()[h->v2_index].fn_v3[h->v3_slots ? 2 : (h->v3_mode & 1)], WN_THREADS_V3};
+static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
+    if (h->variant == 4) return WnChainKernel{diag ? wn_v4_table()[h->v2_index].fn_diag : wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
+    if (h->variant == 3) {
+        const WnV2Entry& e = wn_v2_table()[h->v2_index];
+        return WnChainKernel{(diag ? e.fn_v3_diag : e.fn_v3)[h->v3_slots ? 2 : (h->v3_mode & 1)], WN_THREADS_V3};
+    }
     return WnChainKernel{(const void*)wn_generate_kernel, WN_THREADS};
 }
 static void wn_chain_launch(const wn_handle* h, hipStream_t st, const WnRun& r) {
+    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr;
     if (h->variant == 4)
-        wn_v4_table()[h->v2_index].launch(h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
+        wn_v4_table()[h->v2_index].launch(diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
     else if (h->variant == 3)
-        wn_v2_table()[h->v2_index].launch_v3(h->v3_slots ? 2 : (h->v3_mode & 1), h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
+        wn_v2_table()[h->v2_index].launch_v3(h->v3_slots ? 2 : (h->v3_mode & 1), diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
     else
         hipLaunchKernelGGL(wn_generate_kernel, dim3(h->plan.n_blocks), dim3(WN_THREADS), (size_t)h->lds_bytes, st, h->plan, r);
 }
@@ -699,12 +718,19 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     pl.g0 = pl.gi + pl.n_streams;
     pl.status = h->d_status;
     pl.xcc_tab = h->d_status + 8;
-    const WnChainKernel ck = wn_chain_kernel(h);
+    const WnChainKernel ck = wn_chain_kernel(h, false), ck_diag = wn_chain_kernel(h, true);
     rc = rt_hip(hipFuncSetAttribute(ck.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+    if (!rc && ck_diag.fn != ck.fn)
+        rc = rt_hip(hipFuncSetAttribute(ck_diag.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     if (rc) { wn_destroy(h); return rc; }
     {   // residency is a requirement, not a hope: what the hardware can keep resident of THIS kernel with THIS much LDS, against what the plan needs per XCD
-        int per_cu = 0;
+        int per_cu = 0;   // (of either instantiation: the smaller figure)
         rc = rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ck.fn, ck.threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+        if (!rc && ck_diag.fn != ck.fn) {
+            int per_cu_diag = 0;
+            rc = rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_diag, ck_diag.fn, ck_diag.threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+            if (per_cu_diag < per_cu) per_cu = per_cu_diag;
+        }
         if (rc) { wn_destroy(h); return rc; }
         int need = 0, cap = 0;
         wn_gate_numbers(h, &need, &cap);

@@ -76,7 +76,8 @@ static WnV4Entry wn_v4_entry() {
     WnV4Entry e;
     e.R = R; e.D = D; e.S = S; e.EC = EC; e.LPW = LPW; e.nwpl = V::NWPL; e.nwh = SH::NWH;
     e.pack = wn_pack_v4<R, D, S, EC, LPW>;
-    e.fn = (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW>;
+    e.fn = (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW, false>;
+    e.fn_diag = (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW, true>;
     e.lds_pre_head = WnV3Lds<SH, 1>::pre;
     e.lds_floats = [](int ns) {
         int need = WnV4Lds<V, LPW>::floats(ns);
@@ -86,8 +87,9 @@ static WnV4Entry wn_v4_entry() {
         if (smp * 4 <= WN_LDS_MAX_BYTES && smp > need) need = smp;
         return need;
     };
-    e.launch = [](int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
-        hipLaunchKernelGGL((wn_generate_kernel_v4<R, D, S, EC, LPW>), dim3(grid), dim3(WN_THREADS_V4), lds, st, p, r);
+    e.launch = [](bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
+        if (diag) hipLaunchKernelGGL((wn_generate_kernel_v4<R, D, S, EC, LPW, true>), dim3(grid), dim3(WN_THREADS_V4), lds, st, p, r);
+        else hipLaunchKernelGGL((wn_generate_kernel_v4<R, D, S, EC, LPW, false>), dim3(grid), dim3(WN_THREADS_V4), lds, st, p, r);
     };
     return e;
 }

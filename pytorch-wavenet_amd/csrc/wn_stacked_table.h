@@ -22,10 +22,11 @@
 struct WnV4Entry {
     int R, D, S, EC, LPW, nwpl, nwh;
     void (*pack)(const WnPlan& pl, const WnHostWeights& w, std::vector<float>& out);
-    const void* fn;
+    const void* fn;        // the product instantiation
+    const void* fn_diag;   // ... and the one with the stamps and the logits dump (a job with wn_profile_next or dbg_logits)
     int (*lds_floats)(int ns);
     int lds_pre_head;   // float offset of the head / sampler workgroups' own tables (WnV3Lds<SH>::pre)
-    void (*launch)(int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
+    void (*launch)(bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
 };
 
 const std::vector<WnV4Entry>& wn_v4_table();
