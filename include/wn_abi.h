@@ -227,7 +227,9 @@ int wn_export_queue(wn_handle* h, int32_t layer, int32_t stream, float* host_dat
  * the layer --, for kernel_size above 4 and for channel counts that are not multiples of 32 (after zero padding): callers use the
  * torch path for those, which reproduces what the reference does there.  kernel_size 3 and 4 (fp32 operands; the filter/gate product of a
  * layer reads its k taps as k row-shifted views of the activation matrix, csrc/wn_forward.h: wn_fwd_gemm_taps) are served from
- * L >= receptive_field + output_length - 1 on: shorter clips -- the zero-padding regime above -- are WN_E_UNSUPPORTED for them. */
+ * L >= receptive_field + output_length - 1 on: shorter clips -- the zero-padding regime above -- are WN_E_UNSUPPORTED for them.  Under
+ * wn_set_forward_precision(h, WN_PRECISION_BF16_TAPS) such a handle runs the stack and the head on bf16 operands (wn_fwd_gemm_taps_bf16 and
+ * the bf16 products of kernel_size 2); the clip lengths served are the same. */
 int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t output_length, float* logits, void* hip_stream);
 
 /* Teacher-forced scoring -- what WavenetTrainer.validate() computes per batch (wavenet_training.py:89-112: output = model(x);
@@ -243,7 +245,7 @@ int wn_forward(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64
  * kernel that keeps the head's hidden activations and the logits on the compute unit (csrc/wn_score.h; 256 classes, end channels a multiple
  * of 64, fp32 operands), else -- other shapes, and bf16 operands, where it measured faster -- as wn_forward's two head products into the
  * handle's workspace and a row kernel over them.  WN_NO_FUSED_SCORE=1 / =0 with WN_TESTING=1 pins the second / the first form (A/B runs;
- * wn_info.dev_overrides says so).  Honours wn_set_forward_precision.  Asynchronous on hip_stream.  (Added without a new WN_ABI_VERSION: no existing call or struct changed; a caller
+ * wn_info.dev_overrides says so).  Honours wn_set_forward_precision (kernel_size 3 and 4: WN_PRECISION_BF16_TAPS).  Asynchronous on hip_stream.  (Added without a new WN_ABI_VERSION: no existing call or struct changed; a caller
  * that must run against an older library of version 5 looks the symbol up.) */
 int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64_t N, int64_t L, int64_t output_length,
              float* row_nll, int32_t* row_pred, double* sums, void* hip_stream);
@@ -256,7 +258,14 @@ int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64
  * since round 5 the skip convs' share of dz (one product per block of layers, added to the residual conv's share by the gate
  * derivative) as well: one more rounding point, carried by the step's oracle, oracle/bf16_step.py;
  * logits differ from the fp32 path at the 1e-2 level of their scale, gradients by a few per cent in norm -- mostly sign
- * flips of ReLU masks).  WN_E_UNSUPPORTED unless R, D, S and E are multiples of 64 and kernel_size is 2 (kernel_size 3 and 4 run fp32). */
+ * flips of ReLU masks).  WN_E_UNSUPPORTED unless R, D, S and E are multiples of 64 and kernel_size is 2 (kernel_size 3 and 4 run fp32).
+ * WN_PRECISION_BF16_TAPS (2) = opt-in bf16 operands for kernel_size 3 and 4 INFERENCE: on a kernel_size 2 handle it is the same as 1; on a
+ * kernel_size 3 or 4 handle whose R, D, S and E are multiples of 64 it puts wn_forward and wn_score -- and nothing else -- on bf16 operands
+ * (the filter/gate product over the k tap views, then the residual, skip and head products or score kernels of kernel_size 2).  wn_prime stays
+ * fp32 as always, wn_train_forward / wn_train_backward of such a handle stay fp32 whatever the mode, clips shorter than receptive_field +
+ * output_length - 1 stay WN_E_UNSUPPORTED.  WN_E_UNSUPPORTED for other channel shapes and for kernel_size above 4; WN_E_STATE before the
+ * weights are loaded.  1 on such a handle is refused as before; 0 returns to fp32; every other non-zero value means 1. */
+#define WN_PRECISION_BF16_TAPS 2
 int wn_set_forward_precision(wn_handle* h, int32_t bf16);
 
 /* The priming loop of generate_fast (wavenet_model.py:259-269) for ALL given samples at once: `first_samples` is a DEVICE

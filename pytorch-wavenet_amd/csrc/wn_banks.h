@@ -2,7 +2,7 @@
 //
 // The fp32 bank IS the packed parameter array of the training step (include/wn_abi.h: wn_train_layout, where the layouts of its sections are
 // written down); wn_forward / wn_prime read the same sections.  The bf16 bank holds the matrices of the forward once more as [N][K] row-major
-// bf16 (K contiguous: the weights' natural (out, in) layout), for wn_set_forward_precision(1).
+// bf16 (K contiguous: the weights' natural (out, in) layout), for wn_set_forward_precision; the filter/gate matrix of a layer is [2D][k*R], column tap*R + r, tap 0 the oldest.
 #ifndef WN_BANKS_H
 #define WN_BANKS_H
 
@@ -19,6 +19,10 @@ static inline bool wn_bank_ok(const WnPlan& s) { return s.k == 2 && s.R % 32 == 
 // inference (wn_forward / wn_score / wn_prime, fp32 operands) also takes kernel_size 3 and 4: only the filter/gate product reads the taps (wn_fwd_gemm_taps)
 static inline bool wn_bank_fwd_ok(const WnPlan& s) {
     return s.k >= 2 && s.k <= 4 && s.R % 32 == 0 && s.D % 32 == 0 && s.S % 32 == 0 && s.E % 32 == 0 && s.C % 32 == 0;
+}
+// bf16 operands for inference (wn_set_forward_precision): kernel_size 2, and 3 and 4 (wn_fwd_gemm_taps_bf16; wn_forward / wn_score only)
+static inline bool wn_bank_fwd_bf16_ok(const WnPlan& s) {
+    return s.k >= 2 && s.k <= 4 && s.R % 64 == 0 && s.D % 64 == 0 && s.S % 64 == 0 && s.E % 64 == 0 && s.C % 32 == 0;
 }
 
 // the fp32 training step takes the same shapes (kernel_size 3 and 4: wn_fwd_gemm_taps / wn_bwd_gemm_taps; bf16 operands stay kernel_size 2)
@@ -52,12 +56,12 @@ struct WnBf16Layout {
     bool ok = false;   // R, D, S, E multiples of 64 and G divides NL
 };
 static inline WnBf16Layout wn_bank_layout_bf16(const WnPlan& s) {
-    const size_t NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C;
+    const size_t NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C, k = s.k;
     WnBf16Layout t;
     t.G = s.layers < s.NL ? s.layers : s.NL;
     t.ok = s.R % 64 == 0 && s.D % 64 == 0 && s.S % 64 == 0 && s.E % 64 == 0 && s.NL % t.G == 0;
     size_t o = 0;
-    t.fg = o; o += NL * 2 * D * 2 * R;
+    t.fg = o; o += NL * 2 * D * k * R;   // (k taps: [NL][2D][k*R])
     t.res = o; o += NL * R * D;
     t.skip = o; o += NL * D * S;
     t.w1 = o; o += E * S;
@@ -123,12 +127,12 @@ static inline unsigned short wn_bf16_rne(float x) {   // round to nearest even (
 // `fw`: the packed fp32 bank (its filter/gate section is transposed here; the others come from the caller's arrays, which are [N][K] already)
 static inline std::vector<unsigned short> wn_pack_bank_bf16(const WnBf16Layout& ob, const wn_train_layout& o, const WnPlan& s, const std::vector<float>& fw,
                                                             const wn_weight_ptrs* w) {
-    const int NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C, G = ob.G;
+    const int NL = s.NL, R = s.R, D = s.D, S = s.S, E = s.E, C = s.C, G = ob.G, KR = s.k * s.R;
     std::vector<unsigned short> wb(ob.total, 0);
     for (int l = 0; l < NL; ++l) {
         for (int n = 0; n < 2 * D; ++n)  // packed column n of layer l = row n here; k = tap*R + ch
-            for (int k = 0; k < 2 * R; ++k)
-                wb[ob.fg + ((size_t)l * 2 * D + n) * 2 * R + k] = wn_bf16_rne(fw[o.fg + (size_t)l * 2 * R * 2 * D + (size_t)k * 2 * D + n]);
+            for (int k = 0; k < KR; ++k)
+                wb[ob.fg + ((size_t)l * 2 * D + n) * KR + k] = wn_bf16_rne(fw[o.fg + (size_t)l * KR * 2 * D + (size_t)k * 2 * D + n]);
         for (int r = 0; r < R; ++r)
             for (int dch = 0; dch < D; ++dch) wb[ob.res + ((size_t)l * R + r) * D + dch] = wn_bf16_rne(w->res_w[((size_t)l * R + r) * D + dch]);
         const int blk = l / G, li = l % G;  // skip banks are grouped per block: [block][S][G*D]

@@ -17,7 +17,8 @@
 // (v_mfma_f32_32x32x16_bf16, fp32 accumulation): operands rounded while they are staged, and in the training step the activations
 // that only ever feed such operands stored as bf16 -- the products are HBM streams (K = 128-512), so the bytes are what they cost.
 // The same file holds the backward products of the training step (wn_train.inl is their host side).  kernel_size 3 and 4 (fp32 operands) take the
-// filter/gate product and its input gradient over k row-shifted views of one matrix: wn_fwd_gemm_taps, wn_bwd_gemm_taps.
+// filter/gate product and its input gradient over k row-shifted views of one matrix: wn_fwd_gemm_taps, wn_bwd_gemm_taps; inference also has the
+// product on bf16 operands, opt-in: wn_fwd_gemm_taps_bf16.
 //
 // Valid when every returned position has a full receptive field: L >= receptive_field + output_length - 1 (the
 // reference's own training shape, train_script.py:39).  Shorter inputs hit the reference's zero-padding quirk
@@ -789,6 +790,109 @@ __global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? (A16 ? WN_GEMM_BF16_MINB :
     asm volatile("" : "+v"(te));
     const int lane_e = te & 63, wv_e = te >> 6, wr_e = wv_e & 3, wc_e = wv_e >> 2;
     wn_gemm_epilogue<EPI, 4, true>(g, acc, m0 + 32 * wr_e, n0 + 128 * wc_e, lane_e, reinterpret_cast<float*>(smem_h) + wv_e * WN_EPI_TILE_FLOATS);   // (after the loop's last barrier)
+}
+
+// ---- The filter/gate product of a layer with kernel_size TAPS = 3 or 4 on bf16 operands (inference: wn_forward / wn_score under
+// wn_set_forward_precision(h, WN_PRECISION_BF16_TAPS)): wn_fwd_gemm_bf16<WN_EPI_GATE, WAVES>'s tile, LDS image, K loop and epilogue with
+// wn_fwd_gemm_taps's A operand -- TAPS row-shifted views of the ONE fp32 activation matrix, rounded to bf16 (RNE) while they are staged:
+// g.a1 is the view of x(t), view j lies (TAPS-1-j) * tap_rows rows before it, g.k_split = R is the K extent of a view (a chunk never
+// straddles two views: R % 64 == 0), g.K = TAPS * R; a view's row whose time falls before t_min reads as zero without being loaded.
+// B is the layer's block of the bf16 bank, [2D][TAPS * R] row-major (column tap * R + r, tap 0 the oldest).  The chunks run view 0 first,
+// one accumulator per output element, added in K order: with zero weights on the oldest TAPS - 2 taps the result is the two-view
+// product's bit for bit.  (No bf16-stored A form: the one-launch layer kernel and its x shadow are kernel_size 2.)
+template <int TAPS, int WAVES>
+__global__ __launch_bounds__(64 * WAVES, WAVES == 4 ? 3 : 4) void wn_fwd_gemm_taps_bf16(WnTapsArgs ta, const unsigned short* bn) {
+    static_assert(TAPS == 3 || TAPS == 4, "kernel_size 3 and 4 (2 is wn_fwd_gemm_bf16's two-view form)");
+    const WnGemmArgs& g = ta.g;
+    constexpr int NT = 64 * WAVES, TM = 128, TN = 32 * WAVES, KC = WN_GEMM_BF16_KC, LD = KC + 8;  // LD: padded row length (bf16): 80-byte rows, conflict-free b128 reads
+    constexpr int TPR = NT / TM;   // loader threads per A row (2 / 4)
+    constexpr int HK = KC / TPR;   // k values per A loader thread and chunk (16 / 8)
+    constexpr int HB = KC / 2;     // B: two loader threads per column, KC/2 bf16 each (NT == 2 TN)
+    static_assert(HK % 8 == 0 && HB % 8 == 0, "loader pieces are 16-byte LDS stores");
+    // (ONE block: the epilogue re-uses it as the waves' staging tiles once the K loop is done)
+    __shared__ __attribute__((aligned(16))) unsigned short smem_h[2 * TM * LD + 2 * TN * LD];
+    static_assert((2 * TM * LD + 2 * TN * LD) * 2 >= WAVES * WN_EPI_TILE_FLOATS * 4, "the operand buffers hold the waves' staging tiles");
+    unsigned short (*a_s)[TM * LD] = reinterpret_cast<unsigned short (*)[TM * LD]>(smem_h);
+    unsigned short (*b_s)[TN * LD] = reinterpret_cast<unsigned short (*)[TN * LD]>(smem_h + 2 * TM * LD);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, wr = wv & 3, wc = wv >> 2;
+    const unsigned ntiles = (unsigned)((g.N + TN - 1) / TN), tm_i = blockIdx.x / ntiles, tn_i = blockIdx.x % ntiles;   // column tiles of a row tile next to each other (wn_fwd_gemm_bf16)
+    const long long m0 = (long long)tm_i * TM;
+    const int n0 = (int)tn_i * TN;
+    wn_f16v acc[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
+    const int lrow = tid / TPR, lpart = tid % TPR;
+    const long long am = m0 + lrow;
+    const bool arow_ok = am < g.M;
+    const unsigned aq = arow_ok ? (unsigned)am / (unsigned)g.rows_per_batch : 0u, arem = arow_ok ? (unsigned)am - aq * (unsigned)g.rows_per_batch : 0u;
+    const float* a1p = wn_row_at(g.a1, aq, arem) + lpart * HK;          // the row of x(t)
+    const long long tap_fl = ta.tap_rows * g.a1.row_stride;              // floats between two neighbouring taps
+    const long long t_row = g.a1.t0 + (long long)arem;                    // the row's time inside its batch entry
+    unsigned okmask = 0;                                                 // bit j: view j of this row exists
+#pragma unroll
+    for (int j = 0; j < TAPS; ++j) okmask |= (arow_ok && t_row - (TAPS - 1 - j) * ta.tap_rows >= ta.t_min) ? (1u << j) : 0u;
+    const int bcol = tid >> 1, bhalf = tid & 1;
+    const bool bcol_ok = n0 + bcol < g.N;
+    const unsigned short* bp = bn + (size_t)(n0 + bcol) * g.K + bhalf * HB;   // (the row of the bank: K = TAPS * R contiguous, the views' columns one after the other)
+
+    float4 va[HK / 4];
+    uint4 vb[HB / 8];
+    int f_tap = 0, f_off = 0;   // the view and the column inside it of the next chunk to fetch
+    auto fetch = [&]() {
+        const bool ok = (okmask >> f_tap) & 1u;
+        const float* src = a1p - (long long)(TAPS - 1 - f_tap) * tap_fl + f_off;
+#pragma unroll
+        for (int q = 0; q < HK / 4; ++q) va[q] = ok ? *reinterpret_cast<const float4*>(src + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
+        const uint4* bsrc = reinterpret_cast<const uint4*>(bp);
+#pragma unroll
+        for (int q = 0; q < HB / 8; ++q) vb[q] = bcol_ok ? bsrc[q] : make_uint4(0u, 0u, 0u, 0u);
+        bp += KC;
+        f_off += KC;
+        if (f_off == g.k_split) { f_off = 0; ++f_tap; }
+    };
+    auto stash = [&](int buf) {
+        uint4* ad = reinterpret_cast<uint4*>(a_s[buf] + lrow * LD + lpart * HK);
+#pragma unroll
+        for (int q = 0; q < HK / 8; ++q) {
+            const float4 x = va[2 * q], y = va[2 * q + 1];
+            ad[q] = make_uint4(wn_pack_bf16(x.x, x.y), wn_pack_bf16(x.z, x.w), wn_pack_bf16(y.x, y.y), wn_pack_bf16(y.z, y.w));
+        }
+        uint4* bd = reinterpret_cast<uint4*>(b_s[buf] + bcol * LD + bhalf * HB);
+#pragma unroll
+        for (int q = 0; q < HB / 8; ++q) bd[q] = vb[q];
+    };
+    auto multiply = [&](int buf) {
+        const unsigned short* ar = a_s[buf] + (32 * wr + (lane & 31)) * LD + 8 * (lane >> 5);
+        const unsigned short* br = b_s[buf] + (128 * wc + (lane & 31)) * LD + 8 * (lane >> 5);
+#pragma unroll
+        for (int ks = 0; ks < KC / 16; ++ks) {
+            const wn_bf16x8 a = *reinterpret_cast<const wn_bf16x8*>(ar + 16 * ks);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const wn_bf16x8 b = *reinterpret_cast<const wn_bf16x8*>(br + 32 * j * LD + 16 * ks);
+                acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, acc[j], 0, 0, 0);
+            }
+        }
+    };
+
+    const int nchunks = TAPS * (g.k_split / KC);
+    fetch();
+    stash(0);
+    __syncthreads();
+    for (int kc = 0; kc < nchunks; ++kc) {
+        const int buf = kc & 1;
+        if (kc + 1 < nchunks) fetch();  // lands while this chunk is multiplied
+        multiply(buf);
+        if (kc + 1 < nchunks) stash(buf ^ 1);
+        __syncthreads();
+    }
+    // (the epilogue's lane roles from an opaque copy of the thread index: see wn_fwd_gemm_bf16)
+    int te = threadIdx.x;
+    asm volatile("" : "+v"(te));
+    const int lane_e = te & 63, wv_e = te >> 6, wr_e = wv_e & 3, wc_e = wv_e >> 2;
+    wn_gemm_epilogue<WN_EPI_GATE, 4, true>(g, acc, m0 + 32 * wr_e, n0 + 128 * wc_e, lane_e, reinterpret_cast<float*>(smem_h) + wv_e * WN_EPI_TILE_FLOATS);   // (after the loop's last barrier)
 }
 
 // ---- One layer of the forward in ONE kernel (bf16 operands; the shape whose filter/gate product is ONE 256-column tile: D = 128, and

@@ -35,6 +35,20 @@ static void wn_launch_taps(hipStream_t st, int taps, const WnTapsArgs& a) {
     else hipLaunchKernelGGL(wn_fwd_gemm_taps<4>, grid, dim3(256), 0, st, a);
 }
 
+// The same product on bf16 operands (wn_fwd_gemm_taps_bf16): bn = the layer's block of the bf16 bank, [N][taps * R]; N % 256 == 0 takes the
+// 128 x 256 tile (wn_launch_nn's rule)
+static void wn_launch_taps_bf16(hipStream_t st, int taps, const WnTapsArgs& a, const unsigned short* bn) {
+    const bool wide = a.g.N % 256 == 0;
+    const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)(wide ? a.g.N / 256 : (a.g.N + 127) / 128));
+    if (wide) {
+        if (taps == 3) hipLaunchKernelGGL((wn_fwd_gemm_taps_bf16<3, 8>), grid, dim3(512), 0, st, a, bn);
+        else hipLaunchKernelGGL((wn_fwd_gemm_taps_bf16<4, 8>), grid, dim3(512), 0, st, a, bn);
+    } else {
+        if (taps == 3) hipLaunchKernelGGL((wn_fwd_gemm_taps_bf16<3, 4>), grid, dim3(256), 0, st, a, bn);
+        else hipLaunchKernelGGL((wn_fwd_gemm_taps_bf16<4, 4>), grid, dim3(256), 0, st, a, bn);
+    }
+}
+
 // The input gradient of that product in the training step (wn_bwd_gemm_taps: one launch, dx written exactly once)
 static void wn_launch_taps_bwd(hipStream_t st, int taps, const WnTapsBwdArgs& a) {
     const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)((a.g.N + 127) / 128));
@@ -190,6 +204,9 @@ static bool wn_fused_score_enabled(wn_handle* h, bool bf16) {
     return !bf16;
 }
 
+// wn_forward / wn_score run on bf16 operands: kernel_size 2 under mode 1 (fwb_ok), kernel_size 3 and 4 under WN_PRECISION_BF16_TAPS (fwb_taps_ok; inference only)
+static bool wn_forward_bf16(const wn_handle* h) { return (h->fw_bf16 && h->w.fwb_ok) || (h->fw_bf16_taps && h->w.fwb_taps_ok); }
+
 static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64_t L, int64_t out_len, float* logits, const WnScoreOut* score, void* hip_stream,
                           const char* who) {
     if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
@@ -203,7 +220,7 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
     WnFwdGeom geo;
     { int rc = wn_forward_geometry(h, L, out_len, geo, who); if (rc) return rc; }
     const long long Mrows = (long long)N * out_len;
-    const bool score_fused = score && C == 256 && S % 32 == 0 && E % WN_SCORE_EC == 0 && wn_fused_score_enabled(h, h->fw_bf16 && h->w.fwb_ok);
+    const bool score_fused = score && C == 256 && S % 32 == 0 && E % WN_SCORE_EC == 0 && wn_fused_score_enabled(h, wn_forward_bf16(h));
     size_t n_part = 0;
     if (score) {   // one fp64 triple per workgroup of the kernel that scores
         n_part = (size_t)(score_fused ? (Mrows + WN_SCORE_TM - 1) / WN_SCORE_TM : (Mrows + WN_SCORE_ROWS_PER_WG - 1) / WN_SCORE_ROWS_PER_WG);
@@ -214,7 +231,7 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
         }
     }
     const std::vector<long long>& need = geo.rows;
-    const int taps = pl.k;   // 2: the two-view product of wn_fwd_gemm; 3, 4: wn_fwd_gemm_taps (fp32 operands: fwb_ok is false for them)
+    const int taps = pl.k;   // 2: the two-view product of wn_fwd_gemm; 3, 4: wn_fwd_gemm_taps, or wn_fwd_gemm_taps_bf16 under WN_PRECISION_BF16_TAPS
     if (taps != 2)
         for (int l = 0; l < NL; ++l)
             if (geo.zlo[l] != 0 || L - need[l + 1] - (long long)(taps - 1) * h->dil[l] < 0) return wn_fail(WN_E_UNSUPPORTED, "%s: kernel_size %d does not serve zero-padded taps", who, taps);
@@ -227,7 +244,7 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
     // bf16 operands at the 128 / 128 shape: a layer is ONE launch (wn_fwd_layer_bf16: z goes from the gate epilogue to the residual product
     // through LDS and is never stored), its matrix operand reads of x take a bf16 shadow written next to x (WnGemmArgs::c_h), z on the skip
     // rows (zg) is stored as bf16.  Same roundings as the two-launch form (every value is rounded to bf16 once, where it becomes an operand).
-    const bool fuse = h->fw_bf16 && h->w.fwb_ok && R == 128 && D == 128 && wn_fused_layer_enabled();
+    const bool fuse = taps == 2 && h->fw_bf16 && h->w.fwb_ok && R == 128 && D == 128 && wn_fused_layer_enabled();
     const size_t xh_fl = fuse ? ((x_fl + 1) / 2 + 63) / 64 * 64 : 0;
     const size_t lg_fl = (score && !score_fused) ? (size_t)Mrows * C : 0;   // (unfused scoring: the logits live in the workspace)
     const size_t total = 2 * x_fl + z_fl + skip_fl + e_fl + zg_fl + 2 * xh_fl + lg_fl;
@@ -247,7 +264,7 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
         hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, indices, h->w.d_start_t,
                            pl.has_bias ? h->w.d_start_b : nullptr, xa, rows, R, xha);
     }
-    const bool bf16 = h->fw_bf16 && wt.fwb_ok;
+    const bool bf16 = wn_forward_bf16(h);
     const unsigned short* fwb = wt.d_fwb;
     auto launch = [&](int epi, const WnGemmArgs& a, size_t bank) { wn_launch_nn(st, epi, a, bf16 ? fwb + bank : nullptr); };   // bank: the product's B in the bf16 bank
     const float* fw = wt.d_fw;
@@ -281,8 +298,9 @@ static int wn_forward_run(wn_handle* h, const int32_t* indices, int64_t N, int64
         if (taps != 2) {   // (a's epilogue fields -- c, c2: z and its copy on the skip rows -- carried over)
             WnTapsArgs at = wn_layer_fg_taps(pl, o, fw, l, wn_rows(xin, L, R, t0), d, wn_rows(z, rows, D), N, rows, 0);
             at.g.c2 = a.c2; at.g.c2_first_row = a.c2_first_row;
-            wn_launch_taps(st, taps, at);
-            if (l < NL - 1) launch(WN_EPI_PLAIN, ar, 0);
+            if (bf16) wn_launch_taps_bf16(st, taps, at, fwb + ob.fg + (size_t)l * 2 * D * taps * R);
+            else wn_launch_taps(st, taps, at);
+            if (l < NL - 1) launch(WN_EPI_PLAIN, ar, ob.res + (size_t)l * R * D);
         } else if (!fused) {
             launch(WN_EPI_GATE, a, ob.fg + (size_t)l * 2 * D * 2 * R);
             if (l < NL - 1) launch(WN_EPI_PLAIN, ar, ob.res + (size_t)l * R * D);
@@ -414,15 +432,24 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
     return WN_OK;
 }
 
-// Operand precision of wn_forward's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),
-// 1 = bf16 operands with fp32 accumulation (the residual stream and all sums stay fp32).  wn_prime always runs fp32.
+// Operand precision of wn_forward's / wn_score's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),
+// 1 = bf16 operands with fp32 accumulation (the residual stream and all sums stay fp32; kernel_size 2, the training step included),
+// WN_PRECISION_BF16_TAPS = the same, and on a kernel_size 3 or 4 handle bf16 operands for wn_forward and wn_score alone (the training
+// step of such a handle stays fp32 whatever the mode).  wn_prime always runs fp32.
 extern "C" int wn_set_forward_precision(wn_handle* h, int32_t bf16) {
     g_err[0] = 0;
     if (!h) return wn_fail(WN_E_BADARG, "wn_set_forward_precision: NULL handle");
     if (!h->chains.empty()) return wn_set_forward_precision(h->chains[0], bf16);
     if (bf16 && !h->have_weights) return wn_fail(WN_E_STATE, "wn_set_forward_precision: load the weights first");
+    if (bf16 == WN_PRECISION_BF16_TAPS && h->plan.k != 2) {
+        if (h->plan.k > 4 || h->plan.k < 2) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 operands need kernel_size 2, 3 or 4 (kernel_size %d runs fp32)", h->plan.k);
+        if (!h->w.fwb_taps_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 needs R, D, S, E to be multiples of 64");
+        h->fw_bf16_taps = 1;
+        return WN_OK;
+    }
     if (bf16 && h->plan.k != 2) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 operands need kernel_size 2 (kernel_size %d runs fp32)", h->plan.k);
     if (bf16 && !h->w.fwb_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_set_forward_precision: bf16 needs R, D, S, E to be multiples of 64");
     h->fw_bf16 = bf16 ? 1 : 0;
+    h->fw_bf16_taps = 0;
     return WN_OK;
 }

@@ -333,7 +333,8 @@ struct WnWeights {
     float* d_fw = nullptr; size_t fw_floats = 0; bool fw_ok = false; wn_train_layout fw = {};   // fw_ok: kernel_size 2 shapes (the bf16 banks)
     bool train_ok = false;   // the training step's shapes: kernel_size 2, 3 and 4 (wn_banks.h: wn_bank_train_ok)
     bool fwd_ok = false;   // inference (wn_forward / wn_score / wn_prime): also kernel_size 3 and 4 (wn_banks.h: wn_bank_fwd_ok)
-    unsigned short* d_fwb = nullptr; size_t fwb_elems = 0; bool fwb_ok = false; WnBf16Layout fwb;
+    unsigned short* d_fwb = nullptr; size_t fwb_elems = 0; bool fwb_ok = false; WnBf16Layout fwb;   // fwb_ok: the bf16 bank of a kernel_size 2 model (forward AND training forms)
+    bool fwb_taps_ok = false;   // the bf16 bank of a kernel_size 3 or 4 model: wn_forward / wn_score only (WN_PRECISION_BF16_TAPS)
 };
 struct wn_handle {
     wn_config cfg = {};
@@ -373,7 +374,8 @@ struct wn_handle {
     size_t blob_floats = 0, ring_floats = 0, gran_count = 0;
     long long* d_prof = nullptr;
     float* d_ws = nullptr; size_t ws_floats = 0;   // batched forward (wn_forward): a workspace that grows on demand
-    int fw_bf16 = 0;                               //   and its operand precision (wn_set_forward_precision)
+    int fw_bf16 = 0;                               //   and its operand precision (wn_set_forward_precision); kernel_size 2, shared with the training step
+    int fw_bf16_taps = 0;                          //   kernel_size 3 and 4: bf16 operands for wn_forward / wn_score alone (WN_PRECISION_BF16_TAPS)
     int prof_items = 0;      // stamps requested for the next job (0 = off)
     int prof_recorded = 0;   // stamps held in d_prof
     std::vector<int64_t> ring_off;
@@ -839,6 +841,7 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
     wt.fwd_ok = wn_bank_fwd_ok(pl);
     wt.train_ok = wn_bank_train_ok(pl);
     wt.fwb_ok = false;
+    wt.fwb_taps_ok = false;
     if (wt.fwd_ok) {
         wt.fw = wn_bank_layout(pl);
         const std::vector<float> fw = wn_pack_bank(wt.fw, pl, w);
@@ -847,10 +850,12 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
         if (!wt.d_fw) return wn_fail(WN_E_NOMEM, "wn_load_weights: forward weight banks (%.1f MB)", o * 4e-6);
         rc = rt_h2d(wt.d_fw, fw.data(), o * 4);
         if (rc) return rc;
-        // bf16 copies for wn_set_forward_precision(1)
+        // bf16 copies for wn_set_forward_precision
         const WnBf16Layout fwb = wn_bank_layout_bf16(pl);
-        wt.fwb_ok = wt.fw_ok && fwb.ok;   // (bf16 operands: kernel_size 2 only)
-        if (wt.fwb_ok) {
+        const bool bank = wn_bank_fwd_bf16_ok(pl) && fwb.ok;
+        wt.fwb_ok = bank && pl.k == 2;        // (the bf16 forms of the forward and the training step: kernel_size 2 only)
+        wt.fwb_taps_ok = bank && pl.k != 2;   // (kernel_size 3 and 4: the forward alone)
+        if (bank) {
             wt.fwb = fwb;
             const std::vector<unsigned short> wb = wn_pack_bank_bf16(fwb, wt.fw, pl, fw, w);
             const size_t ob = wb.size();

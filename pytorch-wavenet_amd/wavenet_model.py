@@ -79,6 +79,12 @@ class WaveNetModel(nn.Module):
     # class or on an instance (an instance's value travels with its pickle).  False: every path, message and warning is as before.
     native_taps_training = False
 
+    # Extension, opt-in: True = with matrix_precision "bf16", forward_indices() / score_indices() (and so the trainer's native validation) of a
+    # kernel_size 3 or 4 model whose channel counts are multiples of 64 run on bf16 matrix operands (C ABI wn_set_forward_precision,
+    # WN_PRECISION_BF16_TAPS).  Inference only: priming, generate_fast() and the native_taps_training step stay fp32.  A class attribute like
+    # native_taps_training.  False: matrix_precision is ignored for such a model, as before.
+    native_taps_bf16 = False
+
     def __init__(self, layers=10, blocks=4, dilation_channels=32, residual_channels=32, skip_channels=256,
                  end_channels=256, classes=256, output_length=32, kernel_size=2, dtype=torch.FloatTensor, bias=False):
         super(WaveNetModel, self).__init__()
@@ -281,9 +287,12 @@ class WaveNetModel(nn.Module):
         c = eng.cfg   # (the ENGINE's channel shape: the training engine of a model with odd channel counts is zero-padded to multiples of 64)
         if want and any(c[k] % 64 for k in ("residual_channels", "dilation_channels", "skip_channels", "end_channels")):
             want = False
+        taps = False
         if c.get("kernel_size", 2) != 2:
-            want = False   # (kernel_size 3 and 4: the matrix-core inference path is fp32 only)
-        eng.set_forward_precision(want)
+            # (kernel_size 3 and 4: fp32 unless opted in, and then on the forward engine alone -- the training step of such a model is fp32)
+            runner = self._wn_train_runner
+            taps = want = (want and bool(self.native_taps_bf16) and c["kernel_size"] in (3, 4) and not (runner is not None and eng is runner.eng))
+        eng.set_forward_precision(want, taps=taps)
 
     def _native_train_forward(self, idx):
         """model(x) with a native backward: see mi355_wavenet/training.py."""
