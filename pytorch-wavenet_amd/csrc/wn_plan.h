@@ -111,6 +111,7 @@ static inline int wn_pow2floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; re
 static inline int wn_pow2ceil(int v) { int p = 1; while (p < v) p *= 2; return p; }
 static inline int wn_cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int wn_round4(int v) { return (v + 3) & ~3; }
+static inline int wn_smp_floats(int C) { return 5 * wn_round4(C) + 8 * WN_SAMPLER_GROUPS + 16; }  // floats of the sampler scratch (wn_kernel.h WnSmp)
 
 static inline WnMatvec wn_make_matvec(int Nr, int K, int off4) {
     WnMatvec m;
@@ -184,7 +185,7 @@ static inline int64_t wn_plan_geometry(WnPlan& pl, int P, int PA) {
     pl.l_xt = o; o += wn_round4(pl.R);
     // skin + red double as the sampler scratch of the L0 workgroups (never live at the same time)
     // sampler scratch: lgt,xsm,pp floats (3*C4) + pd doubles (2*C4) + per-group partials (see wn_kernel.h WnSmp)
-    const int smp_floats = 5 * wn_round4(pl.C) + 8 * WN_SAMPLER_GROUPS + 16;
+    const int smp_floats = wn_smp_floats(pl.C);
     pl.l_skin = o;
     pl.l_smp = o;
     int region = wn_round4(pl.S) + pl.red_floats;
