@@ -268,6 +268,28 @@ int wn_score(wn_handle* h, const int32_t* indices, const int64_t* targets, int64
 #define WN_PRECISION_BF16_TAPS 2
 int wn_set_forward_precision(wn_handle* h, int32_t bf16);
 
+/* Sampling filters: top-k and nucleus (top-p) truncation of every SAMPLED draw of every later wn_generate on the handle, inside the sampler
+ * kernels.  Handle state like the forward precision; (0, 0) restores the unfiltered draw; valid before or after wn_load_weights.  A greedy stream
+ * (temperature <= 0, or a job without uniforms) ignores the filters: the maximum is always kept.
+ *   Let x be the float32 row the samplers form -- fl32(logit - regularizer), then fl32(x / temperature) -- and C the class count.
+ *   top_k (int32; 0 and >= C: off; negative: WN_E_BADARG): tau = the k-th largest value of x, counted with multiplicity; class i is kept iff
+ *     x_i >= tau.  Ties at the threshold are all kept, so more than k classes may survive.  A comparison of float32 values that are the same bits
+ *     on host and device: membership is exact.
+ *   top_p (float; 0 and 1: off; negative, NaN or above 1: WN_E_BADARG), applied to the survivors of top_k: m_i = expf(x_i - max x) for a survivor,
+ *     0 for the others; T = sum of m; G_i = sum of the m_j with x_j > x_i STRICTLY (so that tied classes share one verdict); class i is kept iff
+ *     G_i < top_p * T, the product formed in double from the float given here.  That is the smallest set of most probable classes whose mass
+ *     reaches top_p, with the ties at its edge all kept; the maximum is always kept.  G and T are float64 sums of the float32 masses: G_i / T
+ *     differs from the exact value by the rounding of expf alone (a few 1e-7).
+ *   The draw: a dropped class has the mass exactly 0.0; everything behind is the unfiltered pipeline -- p = m * (1 / sum m) in float32, the
+ *     float64 inclusive sum, the number of classes with cdf / cdf[C-1] <= u, clamped to C - 1.  One uniform per generated sample, as without
+ *     filters.  For u in [0, 1) the returned class is a kept class; u >= 1 (never drawn by a random generator: an input of the kernel tests
+ *     only) clamps to C - 1 whatever was kept.
+ * On the wave-specialised and the stacked kernels a job with a filter in effect runs an instantiation of its own -- the diagnostic one that
+ * wn_profile_next and dbg_logits select, or, in the slot re-use form, a filter kernel beside it -- and a job without one runs, instruction for
+ * instruction, the kernel it ran before this function existed.  The generic kernel (one instantiation) tests the two values per draw.  (Added without a new WN_ABI_VERSION: no existing call or struct
+ * changed; a caller that must run against an older library of version 5 looks the symbol up.) */
+int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p);
+
 /* The priming loop of generate_fast (wavenet_model.py:259-269) for ALL given samples at once: `first_samples` is a DEVICE
  * pointer to int32 [n_streams][row_stride]; the first n_prime (= n_given - 1) samples of every stream are evaluated teacher
  * forced with the forward GEMM kernels (no skip / head work: the reference discards those outputs) and the queues are left

@@ -281,6 +281,42 @@ WN_DEV void wn_sample(WnCtx& cx, const WnSmp& sm, double u, bool greedy, float t
         for (int i = tid; i < C; i += WN_THREADS) sm.pp[i] = expf(sm.xsm[i] - m);
     }
     WN_SYNC();
+    // Sampling filters (wn_set_sampling; the contract is in include/wn_abi.h): a dropped class gets the mass 0.0 and everything behind is the code above
+    // and below.  One thread per class, O(C) each over the LDS rows (every thread reads the same element: a broadcast).
+    //   top_k: x_i >= the k-th largest x  <=>  fewer than k classes are strictly greater than x_i
+    //   top_p: G_i = the mass strictly above x_i, T = the survivors' mass, both float64 sums of the fp32 masses in class order; keep iff G_i < top_p T.
+    //          The new masses go through the (still unused) pd area: pp is what the other threads are reading.
+    if (r.top_k > 0) {
+        WN_PHASE {
+            for (int i = tid; i < C; i += WN_THREADS) {
+                const float xi = sm.xsm[i];
+                int above = 0;
+                for (int j = 0; j < C; ++j) above += sm.xsm[j] > xi ? 1 : 0;
+                if (above >= r.top_k) sm.pp[i] = 0.f;   // (own element only)
+            }
+        }
+        WN_SYNC();
+    }
+    if (r.top_p > 0.f) {
+        float* kept = reinterpret_cast<float*>(sm.pd);
+        WN_PHASE {
+            for (int i = tid; i < C; i += WN_THREADS) {
+                const float xi = sm.xsm[i];
+                double g = 0., t = 0.;
+                for (int j = 0; j < C; ++j) {
+                    const double mj = (double)sm.pp[j];
+                    t += mj;
+                    g += sm.xsm[j] > xi ? mj : 0.;
+                }
+                kept[i] = g < (double)r.top_p * t ? sm.pp[i] : 0.f;
+            }
+        }
+        WN_SYNC();
+        WN_PHASE {
+            for (int i = tid; i < C; i += WN_THREADS) sm.pp[i] = kept[i];
+        }
+        WN_SYNC();
+    }
     WN_PHASE {
         if (tid < G) {
             const int lo = tid * chunk, hi = lo + chunk < C ? lo + chunk : C;

@@ -1393,6 +1393,65 @@ static __device__ __forceinline__ double wn_dpp_rows_f64(double v) {
     const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(v), CTRL, ROWS, 0xf, false);
     return __hiloint2double(hi, lo);
 }
+// ---- the sampling filters of the one-wave sampler (FILTER: wn_set_sampling, include/wn_abi.h has the contract).  Both thresholds are found by a
+// selection over the ORDER-PRESERVING integer keys of x (sign bit flipped for x >= 0, all bits for x < 0; -0.0 counted as +0.0, as the float
+// comparison of the contract does): a 32-step binary search, most significant bit first, for the largest key that still has the wanted property.
+//   top_k: the largest key K with #{key >= K} >= k is the k-th largest key, counted with multiplicity -- four ballots and popcounts per step,
+//          everything in SGPRs; the survivors are the classes with key >= K (ties at the threshold all stay).
+//   top_p: the largest key K whose strictly-greater mass G(K) = sum of m_j over key_j > K is still >= top_p * T -- class i stays iff G(key_i) <
+//          top_p * T, and G falls with the key, so the survivors are the classes with key > K.  m are the fp32 masses expf(x - max) of top_k's
+//          survivors, summed in float64 (a lane's four, then DPP inside the 16-lane rows, then the rows' totals): G / T differs from the float64
+//          statement by the ulp of expf alone, and on equal masses by nothing.
+// Nothing leaves the registers.  A filter that is off costs one scalar branch.
+static __device__ __forceinline__ double wn_wave_sum_f64(double v) {
+    v += wn_row_shr_f64<1>(v);
+    v += wn_row_shr_f64<2>(v);
+    v += wn_row_shr_f64<4>(v);
+    v += wn_row_shr_f64<8>(v);   // lane 15 of every row holds the row's total
+    return (wn_lane_d(v, 15) + wn_lane_d(v, 31)) + (wn_lane_d(v, 47) + wn_lane_d(v, 63));
+}
+static __device__ __forceinline__ uint32_t wn_order_key(float x) {
+    const uint32_t b = __float_as_uint(x == 0.f ? 0.f : x);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, const float (&x)[4], float gm, float (&pk)[4]) {
+    uint32_t key[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) key[k] = wn_order_key(x[k]);
+    uint32_t kth = 0;   // every key is >= 0: top_k off keeps all
+    if (top_k > 0) {
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = kth | (1u << bit);
+            int n = 0;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) n += __popcll(__builtin_amdgcn_ballot_w64(key[k] >= cand));
+            if (n >= top_k) kth = cand;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) pk[k] = key[k] >= kth ? expf(x[k] - gm) : 0.f;
+    if (top_p > 0.f) {
+        double md[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) md[k] = (double)pk[k];
+        const double want = (double)top_p * wn_wave_sum_f64(((md[0] + md[1]) + md[2]) + md[3]);
+        uint32_t edge = 0;   // G(0) = T >= top_p T: the search starts on a key that has the property
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t cand = edge | (1u << bit);
+            double g = 0.;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) g += key[k] > cand ? md[k] : 0.;
+            if (wn_wave_sum_f64(g) >= want) edge = cand;
+        }
+#pragma unroll
+        for (int k = 0; k < 4; ++k) pk[k] = key[k] > edge ? pk[k] : 0.f;
+    }
+}
+
+// FILTER = false is the product's sampler, instruction for instruction what it was before the filters existed; FILTER = true (the DIAG kernels, which a
+// job with a filter runs: wn_chain_launch) reads r.top_k / r.top_p HERE -- behind the logits' poll, like the temperature -- and with both off computes
+// the same pk[] as the other form.  u >= 1 clamps to class 255 whatever the filter kept (a harness-only input).
+template <bool FILTER = false>
 static __device__ __forceinline__ int wn_sample_1w(const WnRun& r, const float (&logit)[4], int lane, double u, bool greedy, float temperature) {
     float x[4];
 #pragma unroll
@@ -1407,8 +1466,12 @@ static __device__ __forceinline__ int wn_sample_1w(const WnRun& r, const float (
         return wn_wave_min_i(mine);
     }
     float pk[4];
+    if constexpr (FILTER) {
+        wn_filter_1w(r.top_k, r.top_p, x, gm, pk);   // (dropped classes: mass 0.0; the rest of the draw is the same code)
+    } else {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) pk[k] = expf(x[k] - gm);
+        for (int k = 0; k < 4; ++k) pk[k] = expf(x[k] - gm);
+    }
     const float tot = wn_wave_sum(((pk[0] + pk[1]) + pk[2]) + pk[3]);
     const float inv = 1.0f / tot;
     // inclusive float64 scan (np.cumsum): inside the lane, then over the lanes' totals
@@ -1525,7 +1588,9 @@ static __device__ __forceinline__ void wn_poll_class(WnCtx& cx, __amdgpu_buffer_
 // the caller lets the workgroup's first FOUR waves in, thread c collects class c from every slice (8-byte loads, 16 in flight), the
 // sums meet in LDS (lds_lg, 256 floats) and wave 0 draws as in the one-wave form -- same sums in the same order, two LDS barriers more.
 // (Variant 4 takes WIDE from eight head slices up, wn_kernel_v4.h; in variant 3 it was level and is not used: profiles/r04_sampler_prefetch_and_wide_sampler.txt.)
-template <class SH, bool WIDE = false, bool DIAG = false>
+// FILTER: the draw is wn_sample_1w<FILTER> (by default what DIAG says; the slot re-use form, whose ONE instantiation is DIAG = true and serves unfiltered
+// product jobs, keeps the unfiltered draw there and has the filter in a kernel of its own: wn_generate_kernel_v3m_filter).
+template <class SH, bool WIDE = false, bool DIAG = false, bool FILTER = DIAG>
 static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds_smp, float* lds_tab, int j, float* lds_lg = nullptr) {
     constexpr int R = SH::R, NP = (R / 2 + 63) / 64;  // pairs of row elements per lane
     constexpr int NT = WIDE ? 256 : 64;
@@ -1608,7 +1673,7 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
                         for (int k = 0; k < 4; ++k) r.dbg_logits[((size_t)s * r.num_samples + g) * 256 + 4 * lane + k] = logit[k];
                     }
                 }
-                idx = wn_sample_1w(r, logit, lane, u, greedy, temp);
+                idx = wn_sample_1w<FILTER>(r, logit, lane, u, greedy, temp);   // (a job with a sampling filter runs a DIAG instantiation as well)
                 if (lane == 0) r.out_idx[(size_t)s * r.num_samples + g] = idx;
             }
             if (e < r.n_eval) {
@@ -1637,7 +1702,10 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
 // by construction, not by the luck of the allocator; the launch bound still gives every lane the 168 the blocks address).  On gfx90a and
 // later the backend DOUBLES the attribute's value (unified VGPR + AGPR file) before it compares it with the occupancy limit -- a value above
 // 84 is silently dropped at 3 waves per SIMD -- hence WN_V3_COMPILER_VGPRS / 2; build.py disassembles the library and checks the result.
-// DIAG: the instantiation with the wall-clock stamps (wn_profile_next) and the sampler's logits dump; the product instantiation has neither.
+// DIAG: the instantiation with the wall-clock stamps (wn_profile_next), the sampler's logits dump and the sampling filters (wn_set_sampling); the
+// product instantiation has none of them.
+// SK > 0 (the slot re-use form) exists in the DIAG = true instantiation ALONE and is what an unfiltered job of 96 streams and more runs
+// (wn_runtime.hip: wn_v2_entry): its sampler keeps the unfiltered draw, so that its instruction stream is what it was before the filters existed.
 template <int R, int DC, int S, int EC, int P, int G = 1, int SK = 0, bool DIAG = false>
 __global__ __launch_bounds__(WN_THREADS_V3) __attribute__((amdgpu_num_vgpr(WN_V3_COMPILER_VGPRS / 2)))
 void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
@@ -1656,7 +1724,31 @@ void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
     }
     if (threadIdx.x >= WN_THREADS) return;  // the head role is a 256-thread role, the sampler role a one-wave role
     if (w < n_layer_wg + p.PA * p.HR) wn_v3_head<SH, P, DIAG>(p, r, cx, wn_lds3m, w - n_layer_wg);
-    else if (threadIdx.x < 64) wn_v3_sampler<SH, false, DIAG>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
+    else if (threadIdx.x < 64) wn_v3_sampler<SH, false, DIAG, DIAG && SK == 0>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
+}
+
+// ... and the slot re-use form WITH the sampling filters, what a job of that form runs while a filter is set (wn_chain_launch): the kernel above with
+// DIAG = true and the filtering sampler.  (Its body is written out a second time on purpose: as a function shared by both kernels, plan and run reach the
+// roles by reference instead of as kernel arguments, and every existing kernel's instruction stream moved.)
+template <int R, int DC, int S, int EC, int P, int G, int SK>
+__global__ __launch_bounds__(WN_THREADS_V3) __attribute__((amdgpu_num_vgpr(WN_V3_COMPILER_VGPRS / 2)))
+void wn_generate_kernel_v3m_filter(WnPlan p, WnRun r) {
+    using SH = WnV2Shape<R, DC, S, EC>;
+    extern __shared__ __attribute__((aligned(16))) float wn_lds3m_f[];
+    const int w = p.wg_map[blockIdx.x];
+    if (w < 0) return;
+    WnCtx cx;
+    cx.p = &p; cx.r = &r; cx.lds = wn_lds3m_f; cx.w = w; cx.fail = 0;
+    cx.t_start = (long long)wall_clock64();
+    if (wn_not_resident(cx, wn_lds3m_f)) return;   // (every workgroup of the job is resident from here on)
+    const int n_layer_wg = p.NL * p.P;
+    if (w < n_layer_wg) {
+        wn_v3_layer<SH, P, G, SK, true>(p, r, cx, wn_lds3m_f, w / P, w % P);
+        return;
+    }
+    if (threadIdx.x >= WN_THREADS) return;  // the head role is a 256-thread role, the sampler role a one-wave role
+    if (w < n_layer_wg + p.PA * p.HR) wn_v3_head<SH, P, true>(p, r, cx, wn_lds3m_f, w - n_layer_wg);
+    else if (threadIdx.x < 64) wn_v3_sampler<SH, false, true, true>(p, r, cx, wn_lds3m_f + WnV3Lds<SH, 1>::smp, wn_lds3m_f + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
 }
 
 #endif  // WN_KERNEL_V3_H

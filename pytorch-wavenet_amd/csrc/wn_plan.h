@@ -100,6 +100,10 @@ struct WnRun {
     int32_t pad;
     const float* stream_temps;  // optional [n_streams]: per-stream temperature (<= 0: that stream is greedy); NULL = `temperature` for all
     int64_t resident_ticks;     // bound of the start-up residency barrier (wn_resident_barrier), wall_clock64 ticks
+    // sampling filters (wn_set_sampling, include/wn_abi.h), normalised by the host: 0 = off.  APPENDED: WnRun is the kernels' last argument, so no offset
+    // of an existing argument moves, and a zero-filled run means "no filter"
+    int32_t top_k;              // 1 .. C-1: keep the classes x_i >= the k-th largest x (ties at the threshold all stay)
+    float top_p;                // (0, 1): of those, keep class i iff the mass of the classes with x_j > x_i is < top_p * the survivors' mass
 };
 
 // ---- host-side planner / packer (plain C++; also parsed, unused, in the device pass) ----

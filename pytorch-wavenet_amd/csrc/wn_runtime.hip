@@ -116,6 +116,7 @@ struct WnV2Entry {
     // the shape has no such form
     const void* fn_v3[3];
     const void* fn_v3_diag[3];   // the same forms with the stamps and the logits dump compiled in (DIAG: a job with wn_profile_next or dbg_logits)
+    const void* fn_v3_filter;    // form 2 with the sampling filters (the forms 0 and 1 have them in fn_v3_diag); NULL where the shape has no form 2
     int (*lds_floats_v3)(int ns, int g2);
     int lds_pre_v3;  // float offset of the per-stream area = what head / sampler workgroups use in front of their own tables
     void (*launch_v3)(int form, bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
@@ -174,7 +175,7 @@ static WnV2Entry wn_v2_entry() {
     WnV2Entry e;
     e.R = R; e.DC = DC; e.S = S; e.EC = EC; e.nwl = SH::NWL; e.nwh = SH::NWH; e.Pm = PM;
     e.pack = wn_pack_v2<SH>;
-    e.fn_v3[0] = e.fn_v3[1] = e.fn_v3[2] = nullptr; e.fn_v3_diag[0] = e.fn_v3_diag[1] = e.fn_v3_diag[2] = nullptr; e.lds_floats_v3 = nullptr; e.launch_v3 = nullptr; e.lds_pre_v3 = 0;
+    e.fn_v3[0] = e.fn_v3[1] = e.fn_v3[2] = nullptr; e.fn_v3_diag[0] = e.fn_v3_diag[1] = e.fn_v3_diag[2] = nullptr; e.fn_v3_filter = nullptr; e.lds_floats_v3 = nullptr; e.launch_v3 = nullptr; e.lds_pre_v3 = 0;
     static_assert(wn_v3_fits<SH, PM>(), "every table entry runs the wave-specialised kernel");
     {
         e.fn_v3[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, false>;
@@ -187,7 +188,13 @@ static WnV2Entry wn_v2_entry() {
         // parent's kernel on the jobs the form is for (cfg3 x 128: 1.45 M against 1.57 M; x 96: 1.37 against 1.43), this one 3 % faster (1.61 / 1.47 M) --
         // the form is throughput bound, what the stamps cost is not on its path, and the compiler's schedule of the kernel without them is the worse one
         // (profiles/r12_lean_item_loops.txt).
-        if constexpr (wn_v3_g2_fits<SH>() && SK > 0) e.fn_v3[2] = e.fn_v3_diag[2] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>;
+        // Because unfiltered product jobs run it, its sampler does NOT carry the sampling filters (wn_kernel_v3.h: the kernel is, instruction for instruction,
+        // what it was before they existed): a job of this form with a filter set runs wn_generate_kernel_v3m_filter, compiled in the other unit (wn_stacked_table.h).
+        if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
+            e.fn_v3[2] = e.fn_v3_diag[2] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>;
+            static_assert(R == 128 && DC == 32 && S == 512 && EC == 32 && PM == 4 && SK == 4, "the slot form's filter kernel is instantiated for this shape (wn_stacked.hip)");
+            e.fn_v3_filter = wn_v3_cfg3_slots_filter_fn();
+        }
         e.lds_pre_v3 = WnV3Lds<SH, 1>::pre;
         e.lds_floats_v3 = [](int ns, int g2) {
             int lay = WnV3Lds<SH, 1>::floats(ns);
@@ -202,6 +209,7 @@ static WnV2Entry wn_v2_entry() {
             auto go = [&](auto diag_c) {
                 constexpr bool DG = decltype(diag_c)::value;
                 if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
+                    if (form == 2 && (r.top_k != 0 || r.top_p != 0.f)) { wn_v3_cfg3_slots_filter_launch(grid, lds, st, p, r); return; }
                     if (form == 2) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
                 }
                 if constexpr (wn_v3_g2_fits<SH>()) {
@@ -377,6 +385,7 @@ struct wn_handle {
     int fw_bf16 = 0;                               //   and its operand precision (wn_set_forward_precision); kernel_size 2, shared with the training step
     int fw_bf16_taps = 0;                          //   kernel_size 3 and 4: bf16 operands for wn_forward / wn_score alone (WN_PRECISION_BF16_TAPS)
     int prof_items = 0;      // stamps requested for the next job (0 = off)
+    int32_t smp_top_k = 0; float smp_top_p = 0.f;   // sampling filters of every later job (wn_set_sampling; as given: wn_generate normalises the off values)
     int prof_recorded = 0;   // stamps held in d_prof
     std::vector<int64_t> ring_off;
     std::vector<int32_t> dil;
@@ -406,7 +415,7 @@ static void wn_free_weights(wn_handle* h) {   // (members i > 0 of a rounds fron
 
 // The chain kernel a handle runs: its function (for the attribute and occupancy queries of wn_create), its workgroup size, its launch
 // (variants 3 and 4 exist twice: the product instantiation and the DIAG one -- wall-clock stamps, logits dump -- that a job with wn_profile_next or
-//  dbg_logits runs; the generic kernel tests at run time)
+//  dbg_logits or a sampling filter runs; the generic kernel tests at run time)
 struct WnChainKernel { const void* fn; int threads; };
 static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
     if (h->variant == 4) return WnChainKernel{diag ? wn_v4_table()[h->v2_index].fn_diag : wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
@@ -417,7 +426,7 @@ static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
     return WnChainKernel{(const void*)wn_generate_kernel, WN_THREADS};
 }
 static void wn_chain_launch(const wn_handle* h, hipStream_t st, const WnRun& r) {
-    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr;
+    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr || r.top_k != 0 || r.top_p != 0.f;   // (the sampling filters live in the DIAG samplers)
     if (h->variant == 4)
         wn_v4_table()[h->v2_index].launch(diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
     else if (h->variant == 3)
@@ -720,7 +729,10 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     pl.g0 = pl.gi + pl.n_streams;
     pl.status = h->d_status;
     pl.xcc_tab = h->d_status + 8;
-    const WnChainKernel ck = wn_chain_kernel(h, false), ck_diag = wn_chain_kernel(h, true);
+    WnChainKernel ck = wn_chain_kernel(h, false), ck_diag = wn_chain_kernel(h, true);
+    if (h->variant == 3 && h->v3_slots) {   // the slot re-use form has ONE kernel for plain and diagnostic jobs and a second one for jobs with a sampling filter
+        ck_diag.fn = wn_v2_table()[h->v2_index].fn_v3_filter;
+    }
     rc = rt_hip(hipFuncSetAttribute(ck.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     if (!rc && ck_diag.fn != ck.fn)
         rc = rt_hip(hipFuncSetAttribute(ck_diag.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
@@ -940,6 +952,10 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     r.first = a->first_samples; r.n_given = a->n_given; r.num_samples = a->num_samples; r.n_eval = n_eval;
     r.t_base = h->t_base; r.temperature = a->temperature; r.greedy = greedy ? 1 : 0; r.reg = a->regularizer;
     r.uniforms = a->uniforms; r.out_idx = a->out_idx; r.dbg_logits = a->dbg_logits; r.stream_temps = a->stream_temperatures;
+    if (!greedy) {   // (nothing is drawn in a greedy job: it runs the kernel it always ran)
+        r.top_k = h->smp_top_k < h->plan.C ? h->smp_top_k : 0;
+        r.top_p = h->smp_top_p < 1.f ? h->smp_top_p : 0.f;
+    }
     const long long ms = a->timeout_ms > 0 ? a->timeout_ms : 10000;
     r.timeout_ticks = ms * (long long)h->wall_khz;
     {   // the start-up residency barrier has a bound of its own: a job that finds CUs taken by another kernel starts when they free up
@@ -1126,6 +1142,17 @@ extern "C" int wn_export_queue(wn_handle* h, int32_t layer, int32_t stream, floa
         for (int m = 0; m < ML; ++m) host_data[(size_t)r * ML + m] = tmp[(size_t)m * pl.R + r];  // (slot, R) -> (R, max_length)
     if (in_pos) *in_pos = (int32_t)(h->t_base % ML);  // one enqueue + one dequeue per evaluation
     if (out_pos) *out_pos = (int32_t)(h->t_base % ML);
+    return WN_OK;
+}
+
+// Sampling filters of every later job on the handle (include/wn_abi.h has the contract; the kernels read them from WnRun)
+extern "C" int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p) {
+    g_err[0] = 0;
+    if (!h) return wn_fail(WN_E_BADARG, "wn_set_sampling: NULL handle");
+    if (top_k < 0) return wn_fail(WN_E_BADARG, "wn_set_sampling: top_k must be >= 0 (0 and >= classes: off), got %d", (int)top_k);
+    if (!(top_p >= 0.f && top_p <= 1.f)) return wn_fail(WN_E_BADARG, "wn_set_sampling: top_p must lie in [0, 1] (0 and 1: off), got %g", (double)top_p);
+    for (wn_handle* c : h->chains) { int rc = wn_set_sampling(c, top_k, top_p); if (rc) return rc; }   // (rounds: every member draws with the same filter)
+    h->smp_top_k = top_k; h->smp_top_p = top_p;
     return WN_OK;
 }
 

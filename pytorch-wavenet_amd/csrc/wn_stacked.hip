@@ -103,3 +103,8 @@ const std::vector<WnV4Entry>& wn_v4_table() {
     return t;
 }
 
+// the slot re-use form of cfg3 with the sampling filters (wn_stacked_table.h: why it is compiled in this unit)
+const void* wn_v3_cfg3_slots_filter_fn() { return (const void*)wn_generate_kernel_v3m_filter<128, 32, 512, 32, 4, 2, 4>; }
+void wn_v3_cfg3_slots_filter_launch(int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
+    hipLaunchKernelGGL((wn_generate_kernel_v3m_filter<128, 32, 512, 32, 4, 2, 4>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r);
+}

@@ -31,4 +31,11 @@ struct WnV4Entry {
 
 const std::vector<WnV4Entry>& wn_v4_table();
 
+// One kernel of the wave-specialised family lives in wn_stacked.hip too: the slot re-use form of cfg3 WITH the sampling filters
+// (wn_kernel_v3.h: wn_generate_kernel_v3m_filter<128, 32, 512, 32, 4, 2, 4>).  In wn_runtime.hip it would be a second caller of the layer role that form's
+// own kernel instantiates, and that alone moves the instruction stream of that kernel -- the one unfiltered jobs of 96 streams and more run, whose
+// schedule is sensitive (wn_runtime.hip: wn_v2_entry).  Here it is the role's only caller, and the other unit compiles as if it did not exist.
+const void* wn_v3_cfg3_slots_filter_fn();
+void wn_v3_cfg3_slots_filter_launch(int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
+
 #endif  // WN_STACKED_TABLE_H

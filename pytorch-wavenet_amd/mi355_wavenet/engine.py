@@ -73,6 +73,7 @@ class Engine:
                            int(bool(cfg.get("bias", False))), self.n_streams, device_index, layer_split, head_split)
         if not pad_channels:  # WN_CFG_NO_PADDING: plan the model's own channel shape (a handle that serves wn_train_* must)
             c.reserved[0] = 1
+        self._sampling = (0, 0.0)   # what set_sampling last put on the handle
         self._h = ctypes.c_void_p()
         self.lib.check(self.lib.dll.wn_create(ctypes.byref(c), ctypes.byref(self._h)))
         self.load_weights(weights)
@@ -118,6 +119,25 @@ class Engine:
         """bf16 operands (fp32 accumulation) for forward_indices / score; fp32 is the parity default.  taps=True asks for WN_PRECISION_BF16_TAPS: the same
         on a kernel_size 2 engine, and the only bf16 mode a kernel_size 3 or 4 engine takes (wn_forward / wn_score alone; include/wn_abi.h)."""
         self.lib.check(self.lib.dll.wn_set_forward_precision(self._h, (2 if taps else 1) if bf16 else 0))
+
+    def set_sampling(self, top_k=0, top_p=0.0):
+        """top-k / nucleus (top-p) truncation of every sampled draw of every later job, inside the sampler kernels (C ABI wn_set_sampling; the
+        contract is in include/wn_abi.h).  top_k: 0 or >= classes is off; top_p: 0 or 1 is off; (0, 0) restores the unfiltered draw.  Greedy streams
+        ignore both.  With both off a library that lacks the symbol is left alone; asking it for a filter raises."""
+        if isinstance(top_k, bool) or int(top_k) != top_k:
+            raise ValueError("top_k must be an integer, got %r" % (top_k,))
+        top_k, top_p = int(top_k), float(top_p)
+        if top_k < 0 or top_k > 0x7fffffff:
+            raise ValueError("top_k must be >= 0 (0 and >= classes: off), got %d" % top_k)
+        if not (0.0 <= top_p <= 1.0):
+            raise ValueError("top_p must lie in [0, 1] (0 and 1: off), got %r" % top_p)
+        if not self.lib.has("wn_set_sampling"):
+            if top_k == 0 and top_p == 0.0:
+                return   # nothing was ever set on such a library
+            raise RuntimeError("mi355_wavenet: %s does not export wn_set_sampling (a library built before the sampling filters were added): "
+                               "rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
+        self.lib.check(self.lib.dll.wn_set_sampling(self._h, top_k, top_p))
+        self._sampling = (top_k, top_p)
 
     def forward_indices(self, indices, output_length):
         """WaveNetModel.forward() on class indices: int tensor/array (N, L) -> float32 (N*output_length, classes) on the
@@ -202,15 +222,18 @@ class Engine:
     PRIME_BATCH_MIN = 64  # given samples from which the GEMM priming path beats the per-sample chain passes
 
     def generate(self, num_samples, first_samples=None, temperature=1.0, regularize=0.0, uniforms=None,
-                 want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None):
+                 want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None, top_k=None, top_p=None):
         """first_samples: (n_streams, n_given) or (n_given,) ints (broadcast to every stream) or None -> classes//2.
         uniforms: float64 (n_streams, num_samples) (np.random.random_sample draws) or None -> greedy.
         temperature: a number, or one per stream (a stream with temperature <= 0 is greedy and ignores its uniforms row).
         uniforms may also be what ``upload_uniforms`` returned (already resident: drawn and uploaded while an earlier job ran).
         while_running: optional callable, invoked after the job has been enqueued and before this call waits for it -- host work
         that overlaps the kernel (the facade draws and uploads the NEXT piece's uniforms there).
+        top_k / top_p: ``set_sampling`` before the job -- the values STAY on the handle for later jobs; None leaves what the handle has.
         Returns indices int32 (n_streams, num_samples) [, logits float32 (n_streams, num_samples, classes)]."""
         ns, C = self.n_streams, self.classes
+        if top_k is not None or top_p is not None:
+            self.set_sampling(self._sampling[0] if top_k is None else top_k, self._sampling[1] if top_p is None else top_p)
         if first_samples is None:
             first_samples = np.full((ns, 1), C // 2, dtype=np.int32)  # wavenet_model.py:245-247
         fs = np.asarray(first_samples)

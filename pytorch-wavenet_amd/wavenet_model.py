@@ -434,8 +434,17 @@ class WaveNetModel(nn.Module):
         return self._wn_engine
 
     def generate_fast(self, num_samples, first_samples=None, temperature=1., regularize=0.,
-                      progress_callback=None, progress_interval=100):
-        """Same contract as wavenet_model.py:237-315; returns float64 ndarray (num_samples,)."""
+                      progress_callback=None, progress_interval=100, *, top_k=0, top_p=0.):
+        """Same contract as wavenet_model.py:237-315; returns float64 ndarray (num_samples,).
+        Extension (keyword only): top_k / top_p truncate every sampled draw inside the sampler kernels (include/wn_abi.h: wn_set_sampling); one
+        uniform per sample is drawn from the global numpy RNG as without them, and the engine's filter is off again when the call returns or raises."""
+        try:
+            return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p)
+        finally:   # (also when a callback raised between two pieces)
+            if (top_k or top_p) and self._wn_engine is not None:
+                self._wn_engine.set_sampling(0, 0.)
+
+    def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p):
         self.eval()
         if first_samples is None:
             first_samples = torch.LongTensor(1).zero_() + (self.classes // 2)
@@ -448,6 +457,8 @@ class WaveNetModel(nn.Module):
             queue.reset()
         eng = self._engine(n_streams)
         eng.reset()
+        if top_k or top_p:
+            eng.set_sampling(top_k, top_p)   # (handle state: every piece below carries it)
         sampled = temperature > 0
 
         # The job is evaluations ev = 0 .. n_eval-1 (num_given-1 priming + num_samples generating).
@@ -557,12 +568,12 @@ class WaveNetModel(nn.Module):
             if getattr(queue, "_lazy", None) is not None:
                 queue._sync()
 
-    def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0.):
+    def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0.):
         """Extension: one generate_fast() per entry of ``temperatures`` -- the reference's generate_audio loop
         (wavenet_training.py:115-124) -- as parallel streams of ONE persistent-kernel job.  Returns float64
         (len(temperatures), num_samples), row k equal to ``generate_fast(num_samples, first_samples, temperatures[k])``
         of sequential calls: sampled rows consume the global numpy RNG in the order of ``temperatures`` (one draw per
-        sample), greedy rows (temperature <= 0, wavenet_model.py:290-294) consume none."""
+        sample), greedy rows (temperature <= 0, wavenet_model.py:290-294) consume none.  top_k / top_p as in generate_fast (greedy rows ignore them)."""
         self.eval()
         temps = [float(t) for t in temperatures]
         if first_samples is None:
@@ -576,8 +587,14 @@ class WaveNetModel(nn.Module):
         for k, t in enumerate(temps):
             if t > 0:
                 uniforms[k] = np.random.random_sample(num_samples)
-        idx = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
-                           uniforms=uniforms if any(t > 0 for t in temps) else None)
+        if top_k or top_p:
+            eng.set_sampling(top_k, top_p)
+        try:
+            idx = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
+                               uniforms=uniforms if any(t > 0 for t in temps) else None)
+        finally:
+            if top_k or top_p:
+                eng.set_sampling(0, 0.)
         self._defer_queues(eng, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
         self.train()
         return self._expand_indices(idx)
