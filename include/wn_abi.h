@@ -299,6 +299,35 @@ int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p);
  * callers then prime through wn_generate.  Asynchronous on hip_stream. */
 int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream);
 
+/* wn_prime for a prompt that ALL streams share: `first_samples` is a DEVICE pointer to ONE row of n_prime given samples.  wn_prime's contract -- freshly
+ * reset queues (else WN_E_STATE), the same shape limits and WN_E_UNSUPPORTED cases, queue time n_prime afterwards, follow with wn_generate(n_given = 1) --
+ * but the stack's products run ONCE over that row, in the workspace of a 1-stream prime, and the ring fill writes the result into every stream and every
+ * layer-split copy; on a handle of several rounds the products run once and every round's rings are filled from that result.  Every stream's queues are
+ * bit for bit what wn_prime leaves on n_streams copies of the row.  Asynchronous on hip_stream.  (Added without a new WN_ABI_VERSION, like wn_score.) */
+int wn_prime_shared(wn_handle* h, const int32_t* first_samples, int64_t n_prime, void* hip_stream);
+
+/* ---- a stream's generation state as data ----
+ * Between two wn_generate calls a stream IS the input rings of its layers (plus the queue time and the last drawn index, which the caller holds).  The
+ * canonical form of those rings is independent of queue time, layer split, channel padding, kernel variant and rounds: for the layers l = 0 .. NL-1 in
+ * order, a block of ML_l x R_own fp32, ML_l = (kernel_size - 1) * d_l + 1, R_own = the CALLER's residual channels (not a padded handle's).  Row j of a
+ * block holds the layer's input at time t - ML_l + j, t = the handle's queue time (wn_info.evals_done): row 0 is the oldest, the last row the newest; on
+ * the handle that row lives in ring slot (t + j) mod ML_l (slot of x[t'] = t' mod ML_l, the DilatedQueue's in_pos rule); rows of negative times are the
+ * zeros of wn_reset.  The oldest row is dead to the next evaluation and kept all the same, so that wn_export_queue round-trips bit for bit.
+ * wn_state_floats: *out = R_own * sum of ML_l, the floats of one state (cfg3: 2.6 MB).
+ * All `state` pointers are DEVICE pointers (16-byte aligned ones are copied with float4 accesses where the channel counts allow).  Both calls wait for
+ * the handle's pending job like wn_export_queue, then run asynchronously on hip_stream -- ONE launch for all layers --, and work through rounds: a stream
+ * index maps to its member handle as in wn_export_queue, a range may straddle the seam.
+ * wn_state_save: the state of stream `stream`: copy 0 of the layer-split copies, un-rotated by the queue time; on a padded handle the caller's channels.
+ * wn_state_load: writes ONE state into EVERY stream of [stream_first, stream_first + stream_count): all layer-split copies, rotated to the destination's
+ *   queue time, zeros in padded channels.  Every ring slot of those streams is overwritten; other streams and the queue time are untouched.  Valid at any
+ *   queue time -- on a freshly reset handle too: the other streams keep their zero history -- and before wn_load_weights.  The state need not come from
+ *   this handle: any handle of the same layers, blocks, kernel_size and residual channels (another stream count, split, kernel, process) wrote a valid one.
+ * WN_E_BADARG: a NULL argument, a stream / range outside the handle (stream_count < 1 included); WN_E_STATE (wn_state_load): a handle whose rounds broke
+ * (a job failed half way through them) until wn_reset.  (Added without a new WN_ABI_VERSION, like wn_score: no existing call or struct changed.) */
+int wn_state_floats(wn_handle* h, int64_t* out);
+int wn_state_save(wn_handle* h, int32_t stream, float* state, void* hip_stream);
+int wn_state_load(wn_handle* h, int32_t stream_first, int32_t stream_count, const float* state, void* hip_stream);
+
 /* ---- training step (WavenetTrainer.train, wavenet_training.py:58-107: output = model(x); loss = cross_entropy; loss.backward()) ----
  * The dilated-conv stack's forward AND backward run as fp32 matrix-core GEMMs; the caller owns the parameters as ONE flat
  * fp32 DEVICE array in the packed layout described by wn_train_layout (each reference parameter appears exactly once, so

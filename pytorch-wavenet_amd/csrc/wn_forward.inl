@@ -357,31 +357,27 @@ extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* tar
 // inputs of the whole window are computed with the forward kernels (no skip / head work -- the reference discards those
 // outputs) and the newest (k-1)*d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
 // (queue time 0); activations before the stream start are zero at every layer, like DilatedQueue.reset().
-extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream) {
-    g_err[0] = 0;
-    if (!h || !first_samples) return wn_fail(WN_E_BADARG, "wn_prime: NULL argument");
-    if (!h->chains.empty()) {
-        if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
-        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
-        for (size_t i = 0; i < h->chains.size(); ++i) {
-            int rc = wn_prime(h->chains[i], first_samples + (size_t)h->chain_first[i] * (size_t)row_stride, n_prime, row_stride, hip_stream);
-            if (rc) return rc;
-        }
-        h->t_base = h->chains[0]->t_base;
-        return WN_OK;
-    }
-    if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_prime: wn_load_weights has not been called");
-    if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
+//
+// The body of wn_prime and wn_prime_shared.  `h` (a handle with rings, not a front of rounds) runs the products on its weights and in its workspace, over
+// the rows of `first_samples`: one per stream of h (wn_prime: fill = {h}), or ONE row whose result the ring fill hands to every stream and copy of every
+// handle of `fill` (shared: h's own rings are filled only if it is listed; the members of a front share their weights, so member 0 computes for all).
+static int wn_prime_run(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, bool shared, wn_handle* const* fill, size_t n_fill,
+                        void* hip_stream, const char* who) {
+    if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
+    if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "%s: bad n_prime / row_stride", who);
     if (n_prime == 0) return WN_OK;
     const WnPlan& pl = h->plan;
-    const int R = pl.R, D = pl.D, NL = pl.NL, ns = pl.n_streams;
-    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32");
+    const int R = pl.R, D = pl.D, NL = pl.NL, ns = shared ? 1 : pl.n_streams;
+    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
     const long long k1 = pl.k - 1;   // a layer's queue holds k1 * d + 1 columns, its conv reaches k1 * d positions back
     if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
-    if (h->t_base != 0) return wn_fail(WN_E_STATE, "wn_prime: queues must be freshly reset (queue time is %lld)", h->t_base);
+    for (size_t i = 0; i < n_fill; ++i) {
+        if (fill[i]->pending) { int rc = wn_wait(fill[i]); if (rc) return rc; }
+        if (fill[i]->t_base != 0) return wn_fail(WN_E_STATE, "%s: queues must be freshly reset (queue time is %lld)", who, fill[i]->t_base);
+    }
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
     const long long n = n_prime;
-    if ((long long)ns * n >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "wn_prime: too many rows");
+    if ((long long)ns * n >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "%s: too many rows", who);
     // q[i] = trailing positions of layer i's input that are needed (its own queue: k1*d+1, and what the layers above need)
     std::vector<long long> q(NL + 1, 0);
     for (int l = NL - 1; l >= 0; --l) {
@@ -395,7 +391,7 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
     const long long Lp = k1 * max_d, Lt = Lp + n;  // every stream's activation rows are preceded by Lp rows of zeros (t < 0): the oldest tap's reach
     const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
     const size_t total = 2 * x_fl + z_fl;
-    if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "wn_prime: workspace of %.1f MB", total * 4e-6);
+    if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
     float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl;
     hipStream_t st = (hipStream_t)hip_stream;
     int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * x_fl * 4, st), "hipMemsetAsync(prime workspace)");
@@ -413,9 +409,13 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
         const int ML = (int)(k1 * d) + 1;
         {   // queue of layer l <- newest min(k1*d+1, n) columns of its input
             const int count = (int)(ML < n ? ML : n);
-            const long long work = (long long)ns * count * (R / 4);
-            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, Lt * R,
-                               h->d_rings + h->ring_off[l], R, ML, ns, pl.P, n, count);
+            for (size_t i = 0; i < n_fill; ++i) {   // (shared: a stream stride of 0 -- every stream of the target reads the one row of activations)
+                const wn_handle* f = fill[i];
+                const int nf = f->plan.n_streams;
+                const long long work = (long long)nf * count * (R / 4);
+                hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, shared ? 0 : Lt * R,
+                                   f->d_rings + f->ring_off[l], R, ML, nf, f->plan.P, n, count);
+            }
         }
         const long long rows = q[l + 1];
         if (l == NL - 1 || rows <= 0) break;
@@ -428,8 +428,40 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
     }
     rc = rt_hip(hipGetLastError(), "wn_prime launches");
     if (rc) return rc;
-    h->t_base = n;
+    for (size_t i = 0; i < n_fill; ++i) fill[i]->t_base = n;
     return WN_OK;
+}
+
+extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !first_samples) return wn_fail(WN_E_BADARG, "wn_prime: NULL argument");
+    if (!h->chains.empty()) {
+        if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "wn_prime: bad n_prime / row_stride");
+        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+        for (size_t i = 0; i < h->chains.size(); ++i) {
+            int rc = wn_prime(h->chains[i], first_samples + (size_t)h->chain_first[i] * (size_t)row_stride, n_prime, row_stride, hip_stream);
+            if (rc) return rc;
+        }
+        h->t_base = h->chains[0]->t_base;
+        return WN_OK;
+    }
+    return wn_prime_run(h, first_samples, n_prime, row_stride, false, &h, 1, hip_stream, "wn_prime");
+}
+
+// wn_prime for a prompt that every stream shares: ONE row of given samples, the stack's products once over it (the workspace of a 1-stream prime), the ring
+// fill into every stream and copy -- of every round, where the handle is a front of rounds (the members share member 0's weights: it computes for all).
+extern "C" int wn_prime_shared(wn_handle* h, const int32_t* first_samples, int64_t n_prime, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !first_samples) return wn_fail(WN_E_BADARG, "wn_prime_shared: NULL argument");
+    if (!h->chains.empty()) {
+        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+        if (h->broken) return wn_fail(WN_E_STATE, "wn_prime_shared: an earlier job failed half way through its rounds; call wn_reset");
+        int rc = wn_prime_run(h->chains[0], first_samples, n_prime, n_prime, true, h->chains.data(), h->chains.size(), hip_stream, "wn_prime_shared");
+        if (rc) return rc;
+        h->t_base = h->chains[0]->t_base;
+        return WN_OK;
+    }
+    return wn_prime_run(h, first_samples, n_prime, n_prime, true, &h, 1, hip_stream, "wn_prime_shared");
 }
 
 // Operand precision of wn_forward's / wn_score's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),

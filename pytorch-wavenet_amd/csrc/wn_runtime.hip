@@ -377,6 +377,7 @@ struct wn_handle {
     float* d_rings = nullptr;
     int32_t *d_dil = nullptr, *d_wg_map = nullptr;
     int64_t* d_ring_off = nullptr;
+    int64_t* d_state_off = nullptr;   // [NL + 1] canonical rows below layer l's block of a saved stream state (wn_state.inl)
     wn_u64* d_gran = nullptr;
     uint32_t* d_status = nullptr;
     size_t blob_floats = 0, ring_floats = 0, gran_count = 0;
@@ -466,7 +467,7 @@ extern "C" void wn_destroy(wn_handle* h) {
     wn_gate_release(h->gate);
     wn_free_weights(h);
     rt_free(h->d_rings); rt_free(h->d_dil);
-    rt_free(h->d_wg_map); rt_free(h->d_ring_off); rt_free(h->d_gran); rt_free(h->d_status); rt_free(h->d_prof); rt_free(h->d_ws);
+    rt_free(h->d_wg_map); rt_free(h->d_ring_off); rt_free(h->d_state_off); rt_free(h->d_gran); rt_free(h->d_status); rt_free(h->d_prof); rt_free(h->d_ws);
     rt_free(h->d_tws);
     rt_free(h->d_xent);
     rt_free(h->d_score_part);
@@ -666,6 +667,8 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
         off += (int64_t)pl.P * pl.n_streams * ML * pl.R;
     }
     h->ring_floats = (size_t)off;
+    std::vector<int64_t> state_off(pl.NL + 1, 0);
+    for (int l = 0; l < pl.NL; ++l) state_off[l + 1] = state_off[l] + (int64_t)(pl.k - 1) * h->dil[l] + 1;
     std::vector<int32_t> wg_map;
     pl.n_blocks = pl.n_wg;
     pl.allow_plain = 0;
@@ -706,10 +709,11 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     h->d_rings = (float*)rt_malloc(h->ring_floats * 4);
     h->d_dil = (int32_t*)rt_malloc((size_t)pl.NL * 4);
     h->d_ring_off = (int64_t*)rt_malloc((size_t)pl.NL * 8);
+    h->d_state_off = (int64_t*)rt_malloc((size_t)(pl.NL + 1) * 8);
     h->d_wg_map = (int32_t*)rt_malloc((size_t)pl.n_blocks * 4);
     h->d_gran = (wn_u64*)rt_malloc(h->gran_count * 8);
     h->d_status = (uint32_t*)rt_malloc((size_t)(8 + pl.n_wg) * 4);
-    if (!h->w.d_blobs || !h->w.d_start_t || !h->w.d_start_b || !h->d_rings || !h->d_dil || !h->d_ring_off || !h->d_wg_map ||
+    if (!h->w.d_blobs || !h->w.d_start_t || !h->w.d_start_b || !h->d_rings || !h->d_dil || !h->d_ring_off || !h->d_state_off || !h->d_wg_map ||
         !h->d_gran || !h->d_status) {
         const double q_mb = h->ring_floats * 4e-6, g_mb = h->gran_count * 8e-6, w_mb = h->blob_floats * 4e-6;
         wn_destroy(h);
@@ -718,6 +722,7 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     int rc = 0;
     rc = rc ? rc : rt_h2d(h->d_dil, h->dil.data(), (size_t)pl.NL * 4);
     rc = rc ? rc : rt_h2d(h->d_ring_off, h->ring_off.data(), (size_t)pl.NL * 8);
+    rc = rc ? rc : rt_h2d(h->d_state_off, state_off.data(), (size_t)(pl.NL + 1) * 8);
     rc = rc ? rc : rt_h2d(h->d_wg_map, wg_map.data(), (size_t)pl.n_blocks * 4);
     rc = rc ? rc : rt_memset_async(h->d_rings, 0, h->ring_floats * 4, nullptr);
     rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)(8 + pl.n_wg) * 4, nullptr);
@@ -1178,5 +1183,6 @@ extern "C" int wn_profile_read(wn_handle* h, int64_t* host_out, int64_t capacity
 }
 
 #include "wn_forward.inl"
+#include "wn_state.inl"
 #include "wn_train.inl"
 #include "wn_optim.inl"

@@ -213,6 +213,55 @@ class Engine:
             return True
         return self.prime(self.mem.upload(fs), fs.shape[1], fs.shape[1])
 
+    # -- the generation state as data (include/wn_abi.h: wn_state_*; mi355_wavenet/state.py holds it on the host)
+    def _need(self, symbol):
+        if not self.lib.has(symbol):
+            raise RuntimeError("mi355_wavenet: %s does not export %s (a library built before the generation state could be saved and loaded): "
+                               "rebuild it with pytorch-wavenet_amd/build.py" % (self.lib.path, symbol))
+        return getattr(self.lib.dll, symbol)
+
+    def state_floats(self):
+        """float32 values of ONE stream's canonical state: the caller's residual channels x the sum of the layers' queue lengths."""
+        n = ctypes.c_int64()
+        self.lib.check(self._need("wn_state_floats")(self._h, ctypes.byref(n)))
+        return int(n.value)
+
+    def state_save(self, stream=0):
+        """The canonical, time-free state of one stream's dilation queues: float32 ndarray (state_floats(),) -- per layer (k-1)d+1 rows of R values,
+        oldest first (wn_state_save).  Waits for the job in flight."""
+        save = self._need("wn_state_save")
+        dev = self.mem.empty((self.state_floats(),), np.float32)
+        self.lib.check(save(self._h, int(stream), self.mem.ptr(dev), self.mem.stream()))
+        return np.ascontiguousarray(self.mem.download(dev), dtype=np.float32)
+
+    def state_load(self, state, stream_first=0, stream_count=None):
+        """Writes ONE canonical state into every stream of [stream_first, stream_first + stream_count) (default: up to the last stream), at the
+        engine's present queue time, which it leaves alone (wn_state_load).  The other streams keep their queues."""
+        load = self._need("wn_state_load")
+        a = np.ascontiguousarray(np.asarray(state), dtype=np.float32).reshape(-1)
+        if a.size != self.state_floats():
+            raise ValueError("the state holds %d values, this engine's streams hold %d" % (a.size, self.state_floats()))
+        if stream_count is None:
+            stream_count = self.n_streams - int(stream_first)
+        dev = self.mem.upload(a)
+        self.lib.check(load(self._h, int(stream_first), int(stream_count), self.mem.ptr(dev), self.mem.stream()))
+
+    def prime_shared(self, first_row):
+        """prime() for a prompt every stream shares: ONE row of teacher-forced class indices, the stack's products once, the result into every
+        stream's queues (wn_prime_shared).  Returns False when the engine cannot (wn_prime's shape limits)."""
+        prime = self._need("wn_prime_shared")
+        row = np.ascontiguousarray(np.asarray(first_row), dtype=np.int32).reshape(-1)
+        if row.size and (row.min() < 0 or row.max() >= self.classes):
+            raise ValueError("first_samples outside [0, classes)")
+        if row.size == 0:
+            return True
+        dev = self.mem.upload(row)
+        rc = prime(self._h, self.mem.ptr(dev), int(row.size), self.mem.stream())
+        if rc == _abi.WN_E_UNSUPPORTED:
+            return False
+        self.lib.check(rc)
+        return True
+
     def upload_uniforms(self, u):
         """float64 (n_streams, n) uniforms -> a resident handle ``generate(uniforms=...)`` accepts"""
         u = np.ascontiguousarray(np.asarray(u, dtype=np.float64))
@@ -222,7 +271,7 @@ class Engine:
     PRIME_BATCH_MIN = 64  # given samples from which the GEMM priming path beats the per-sample chain passes
 
     def generate(self, num_samples, first_samples=None, temperature=1.0, regularize=0.0, uniforms=None,
-                 want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None, top_k=None, top_p=None):
+                 want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None, top_k=None, top_p=None, shared_prompt=False):
         """first_samples: (n_streams, n_given) or (n_given,) ints (broadcast to every stream) or None -> classes//2.
         uniforms: float64 (n_streams, num_samples) (np.random.random_sample draws) or None -> greedy.
         temperature: a number, or one per stream (a stream with temperature <= 0 is greedy and ignores its uniforms row).
@@ -230,6 +279,8 @@ class Engine:
         while_running: optional callable, invoked after the job has been enqueued and before this call waits for it -- host work
         that overlaps the kernel (the facade draws and uploads the NEXT piece's uniforms there).
         top_k / top_p: ``set_sampling`` before the job -- the values STAY on the handle for later jobs; None leaves what the handle has.
+        shared_prompt: the streams share their given samples (a 1-D first_samples, or identical rows -- anything else is a ValueError): the batched
+        priming runs once over the one row and fills every stream's queues (``prime_shared``).
         Returns indices int32 (n_streams, num_samples) [, logits float32 (n_streams, num_samples, classes)]."""
         ns, C = self.n_streams, self.classes
         if top_k is not None or top_p is not None:
@@ -244,6 +295,8 @@ class Engine:
         if fs.min() < 0 or fs.max() >= C:
             raise ValueError("first_samples outside [0, classes)")
         fs = np.ascontiguousarray(fs, dtype=np.int32)
+        if shared_prompt and not (fs == fs[:1]).all():
+            raise ValueError("shared_prompt: the rows of first_samples differ")
         temps_dev = None
         if np.ndim(temperature) > 0:
             temps = np.ascontiguousarray(np.asarray(temperature, dtype=np.float32).reshape(ns))
@@ -265,7 +318,7 @@ class Engine:
         n_given = fs.shape[1]
         if reset:
             self.reset()
-            if batched_prime and n_given - 1 >= self.PRIME_BATCH_MIN and self.prime(first_dev, n_given - 1, n_given):
+            if batched_prime and n_given - 1 >= self.PRIME_BATCH_MIN and (self.prime_shared(fs[0, :-1]) if shared_prompt else self.prime(first_dev, n_given - 1, n_given)):
                 first_dev = self.mem.upload(np.ascontiguousarray(fs[:, -1:]))  # the last given sample is the next input
                 n_given = 1
         self.launch(first_dev, n_given, num_samples, temperature, reg_dev, uni_dev, out_dev, logits_dev, timeout_ms, temps_dev)

@@ -434,17 +434,46 @@ class WaveNetModel(nn.Module):
         return self._wn_engine
 
     def generate_fast(self, num_samples, first_samples=None, temperature=1., regularize=0.,
-                      progress_callback=None, progress_interval=100, *, top_k=0, top_p=0.):
+                      progress_callback=None, progress_interval=100, *, top_k=0, top_p=0., continue_from=None, return_state=False):
         """Same contract as wavenet_model.py:237-315; returns float64 ndarray (num_samples,).
         Extension (keyword only): top_k / top_p truncate every sampled draw inside the sampler kernels (include/wn_abi.h: wn_set_sampling); one
-        uniform per sample is drawn from the global numpy RNG as without them, and the engine's filter is off again when the call returns or raises."""
+        uniform per sample is drawn from the global numpy RNG as without them, and the engine's filter is off again when the call returns or raises.
+        continue_from: a ``mi355_wavenet.state.GenerationState`` (or a list of them, one per stream: the result is then 2-D) -- the call behaves as
+        ``generate_fast(first_samples=[state.last_index])`` except that the dilation queues are LOADED from the state instead of reset: callbacks,
+        the timing print and the RNG's consumption are those of that call.  Together with first_samples it is a ValueError.
+        return_state=True: returns (audio, state) -- the stream's state behind the last generated sample (a list of states for a 2-D prompt or a
+        list given as continue_from), to continue from later, in another process (it pickles; ``state.save(path)``) or on other stream counts."""
+        states = None
+        if continue_from is not None:
+            if first_samples is not None:
+                raise ValueError("generate_fast: continue_from carries the next input (last_index); first_samples must not be given with it")
+            states, first_samples = self._continue_states(continue_from)
         try:
-            return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p)
+            return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
+                                       states, return_state)
         finally:   # (also when a callback raised between two pieces)
             if (top_k or top_p) and self._wn_engine is not None:
                 self._wn_engine.set_sampling(0, 0.)
 
-    def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p):
+    def _continue_states(self, continue_from):
+        """-> (the states as a list, checked against this model; the first_samples that stand for them: 1-D for a single state, else 2-D)"""
+        from mi355_wavenet.state import GenerationState
+        single = isinstance(continue_from, GenerationState)
+        states = [continue_from] if single else list(continue_from)
+        if not states or not all(isinstance(st, GenerationState) for st in states):
+            raise ValueError("continue_from must be a GenerationState or a non-empty list of them")
+        for st in states:
+            st.check(self)
+        last = np.asarray([[st.last_index] for st in states], dtype=np.int64)
+        return states, torch.from_numpy(last[0] if single else last)
+
+    def _stream_state(self, eng, stream, last_index, evals):
+        from mi355_wavenet.state import GenerationState
+        return GenerationState(eng.state_save(stream), last_index, evals, layers=self.layers, blocks=self.blocks, residual_channels=self.residual_channels,
+                               kernel_size=self.kernel_size, classes=self.classes)
+
+    def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
+                       states=None, return_state=False):
         self.eval()
         if first_samples is None:
             first_samples = torch.LongTensor(1).zero_() + (self.classes // 2)
@@ -457,6 +486,9 @@ class WaveNetModel(nn.Module):
             queue.reset()
         eng = self._engine(n_streams)
         eng.reset()
+        if states is not None:   # (queue time 0 again: the canonical form does not depend on it)
+            for s, st in enumerate(states):
+                eng.state_load(st.state, s, 1)
         if top_k or top_p:
             eng.set_sampling(top_k, top_p)   # (handle state: every piece below carries it)
         sampled = temperature > 0
@@ -536,7 +568,13 @@ class WaveNetModel(nn.Module):
         self._defer_queues(eng)
         self.train()
         mu_gen = self._expand_indices(idx)  # :296, :314
-        return mu_gen if batched else mu_gen[0]
+        audio = mu_gen if batched else mu_gen[0]
+        if not return_state:
+            return audio
+        nxt = idx[:, -1] if idx.shape[1] else first[:, -1]   # the input of the next step
+        before = [st.evals for st in states] if states is not None else [0] * n_streams
+        out = [self._stream_state(eng, s, int(nxt[s]), before[s] + n_eval) for s in range(n_streams)]
+        return audio, (out if batched else out[0])
 
     def _expand_indices(self, idx):
         """Class indices -> float64 audio: ``o = idx / classes * 2 - 1`` (wavenet_model.py:296) then ``mu_law_expansion(o)``
@@ -568,12 +606,26 @@ class WaveNetModel(nn.Module):
             if getattr(queue, "_lazy", None) is not None:
                 queue._sync()
 
-    def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0.):
+    # generate_fast_streams primes its shared prompt ONCE (Engine.prime_shared) instead of once per stream: every stream's queues are bit for bit those
+    # of the per-stream pass (tests/test_gpu_generation_state.py), the products run over 1 / n_streams of the rows (profiles/r16_generation_state.txt)
+    SHARED_PRIME = True
+
+    def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0., continue_from=None):
         """Extension: one generate_fast() per entry of ``temperatures`` -- the reference's generate_audio loop
         (wavenet_training.py:115-124) -- as parallel streams of ONE persistent-kernel job.  Returns float64
         (len(temperatures), num_samples), row k equal to ``generate_fast(num_samples, first_samples, temperatures[k])``
         of sequential calls: sampled rows consume the global numpy RNG in the order of ``temperatures`` (one draw per
-        sample), greedy rows (temperature <= 0, wavenet_model.py:290-294) consume none.  top_k / top_p as in generate_fast (greedy rows ignore them)."""
+        sample), greedy rows (temperature <= 0, wavenet_model.py:290-294) consume none.  top_k / top_p as in generate_fast (greedy rows ignore them).
+        continue_from: ONE ``GenerationState`` that every temperature continues from (N variations of a checkpoint) -- as first_samples=[last_index]
+        with the queues loaded into every stream instead of reset; together with first_samples it is a ValueError."""
+        state = None
+        if continue_from is not None:
+            if first_samples is not None:
+                raise ValueError("generate_fast_streams: continue_from carries the next input (last_index); first_samples must not be given with it")
+            states, first_samples = self._continue_states(continue_from)
+            if len(states) != 1:
+                raise ValueError("generate_fast_streams: continue_from is ONE state that all temperatures share")
+            state = states[0]
         self.eval()
         temps = [float(t) for t in temperatures]
         if first_samples is None:
@@ -590,8 +642,12 @@ class WaveNetModel(nn.Module):
         if top_k or top_p:
             eng.set_sampling(top_k, top_p)
         try:
+            if state is not None:
+                eng.reset()
+                eng.state_load(state.state)   # one state, every stream
             idx = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
-                               uniforms=uniforms if any(t > 0 for t in temps) else None)
+                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=state is None,
+                               shared_prompt=self.SHARED_PRIME and state is None and eng.lib.has("wn_prime_shared"))
         finally:
             if top_k or top_p:
                 eng.set_sampling(0, 0.)
