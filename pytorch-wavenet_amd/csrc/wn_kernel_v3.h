@@ -201,7 +201,7 @@ static __device__ __forceinline__ void wn_ap_issue_a1(unsigned off, const wn_u64
         "v_mov_b32_e32 %[sum], 0\n\t"                                             \
         "s_waitcnt vmcnt(0)\n\t"                                                  \
         WN_AP_CHECK4(152, 153, 154, 155, 156, 157, 158, 159)
-#define WN_AP_SPIN4_BODY                                                          \
+#define WN_AP_SPIN4_BODY(EXHAUSTED)                                               \
         WN_AP_SGPR_HAZARD                                                         \
         "s_mov_b32 %[cnt], %[rounds]\n\t"                                         \
         WN_AP_ISSUE4(160, 161, 162, 163, 164, 165, 166, 167)                      \
@@ -219,6 +219,7 @@ static __device__ __forceinline__ void wn_ap_issue_a1(unsigned off, const wn_u64
         "s_sub_u32 %[cnt], %[cnt], 1\n\t"                                         \
         "s_cmp_lg_u32 %[cnt], 0\n\t"                                              \
         "s_cbranch_scc1 1b\n"                                                     \
+        EXHAUSTED                                                                 \
         "2:"
 static __device__ __forceinline__ void wn_ap_look4(uint32_t tag, float& sum, int& ok) {
     float t0;
@@ -234,7 +235,7 @@ static __device__ __forceinline__ int wn_ap_spin4(unsigned off, const wn_u64* p0
     float t0;
     long long m;
     int cnt;
-    asm volatile(WN_AP_SPIN4_BODY
+    asm volatile(WN_AP_SPIN4_BODY("")
                  : [sum] "+v"(sum), [ok] "+v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [cnt] "=&s"(cnt)
                  : [off] "v"(off), [p0] "s"(p0), [p1] "s"(p1), [p2] "s"(p2), [p3] "s"(p3), [tag] "s"(tag), [rounds] "s"(rounds)
                  : WN_AP_CLOBBERS);
@@ -256,7 +257,7 @@ static __device__ __forceinline__ int wn_ap_spin4(unsigned off, const wn_u64* p0
         "v_mov_b32_e32 %[sum], 0\n\t"                                             \
         "s_waitcnt vmcnt(0)\n\t"                                                  \
         WN_AP_CHECK2(152, 153, 154, 155)
-#define WN_AP_SPIN2_BODY                                                          \
+#define WN_AP_SPIN2_BODY(EXHAUSTED)                                               \
         WN_AP_SGPR_HAZARD                                                         \
         "s_mov_b32 %[cnt], %[rounds]\n\t"                                         \
         WN_AP_ISSUE2(160, 161, 162, 163)                                          \
@@ -274,6 +275,7 @@ static __device__ __forceinline__ int wn_ap_spin4(unsigned off, const wn_u64* p0
         "s_sub_u32 %[cnt], %[cnt], 1\n\t"                                         \
         "s_cmp_lg_u32 %[cnt], 0\n\t"                                              \
         "s_cbranch_scc1 1b\n"                                                     \
+        EXHAUSTED                                                                 \
         "2:"
 static __device__ __forceinline__ void wn_ap_look2(uint32_t tag, float& sum, int& ok) {
     float t0;
@@ -287,7 +289,7 @@ static __device__ __forceinline__ int wn_ap_spin2(unsigned off, const wn_u64* p0
     float t0;
     long long m;
     int cnt;
-    asm volatile(WN_AP_SPIN2_BODY
+    asm volatile(WN_AP_SPIN2_BODY("")
                  : [sum] "+v"(sum), [ok] "+v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [cnt] "=&s"(cnt)
                  : [off] "v"(off), [p0] "s"(p0), [p1] "s"(p1), [tag] "s"(tag), [rounds] "s"(rounds)
                  : WN_AP_CLOBBERS);
@@ -299,7 +301,7 @@ static __device__ __forceinline__ int wn_ap_spin2(unsigned off, const wn_u64* p0
         "v_mov_b32_e32 %[sum], 0\n\t"                                             \
         "s_waitcnt vmcnt(0)\n\t"                                                  \
         WN_AP_CHECK1(152, 153)
-#define WN_AP_SPIN1_BODY                                                          \
+#define WN_AP_SPIN1_BODY(EXHAUSTED)                                               \
         WN_AP_SGPR_HAZARD                                                         \
         "s_mov_b32 %[cnt], %[rounds]\n\t"                                         \
         "global_load_dwordx2 v[160:161], %[off], %[p0] sc1\n\t"                      \
@@ -317,6 +319,7 @@ static __device__ __forceinline__ int wn_ap_spin2(unsigned off, const wn_u64* p0
         "s_sub_u32 %[cnt], %[cnt], 1\n\t"                                         \
         "s_cmp_lg_u32 %[cnt], 0\n\t"                                              \
         "s_cbranch_scc1 1b\n"                                                     \
+        EXHAUSTED                                                                 \
         "2:"
 static __device__ __forceinline__ void wn_ap_look1(uint32_t tag, float& sum, int& ok) {
     float t0;
@@ -330,11 +333,76 @@ static __device__ __forceinline__ int wn_ap_spin1(unsigned off, const wn_u64* p0
     float t0;
     long long m;
     int cnt;
-    asm volatile(WN_AP_SPIN1_BODY
+    asm volatile(WN_AP_SPIN1_BODY("")
                  : [sum] "+v"(sum), [ok] "+v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [cnt] "=&s"(cnt)
                  : [off] "v"(off), [p0] "s"(p0), [tag] "s"(tag), [rounds] "s"(rounds)
                  : WN_AP_CLOBBERS);
     return cnt;
+}
+// ---- The STAGING forms of the same blocks (round 17).  A block knows that every active lane of its wave is served the moment its last check leaves
+// vcc == 0, and barrier A is one LDS store away from there -- but written in C++, the store stood behind the structurizer's rendering of the caller's
+// bounded-wait loop: four taken scalar branches (one behind a VALU-written vcc), state-flag moves and the address arithmetic, 18 instructions between
+// the served exit and ds_write_b32, once per layer on the token's path (profiles/r17_staged_poll.txt).  These forms take the lane's LDS byte address
+// of its x element as one more VGPR operand and issue the store THEMSELVES at the served exit: label 2 of a spin, the tail of a successful look.
+// The value is the sum the block formed (same order); nothing is stored on the unserved exit (a stale look; a spin that ran out of rounds, which
+// branches round the store).  They return "a lane is still without its input" (the halves of that lane mask or-ed) -- a scalar, so that the caller's
+// one test is s_cmp + s_cbranch.
+// The blocks run under the caller's lane mask like the others: a partly filled wave stores its active lanes only.  (The LDS counter is waited for by
+// wn_lds_barrier's own s_waitcnt lgkmcnt(0), as for every other LDS store in front of a barrier.)
+#define WN_AP_STAGE_LOOK                                                          \
+        "s_cbranch_vccnz 3f\n\t"                                                  \
+        "ds_write_b32 %[xa], %[sum]\n"                                            \
+        "3:\n\t"                                                                  \
+        "s_or_b32 %[un], vcc_lo, vcc_hi"
+#define WN_AP_STAGE_SPIN                                                          \
+        "\n\t"                                                                    \
+        "ds_write_b32 %[xa], %[sum]\n"                                            \
+        "3:\n\t"                                                                  \
+        "s_or_b32 %[un], vcc_lo, vcc_hi"
+#define WN_AP_LOOK_STAGE_FN(NAME, BODY)                                                                                       \
+    static __device__ __forceinline__ int NAME(uint32_t tag, unsigned xa, float& sum, int& ok) {                              \
+        float t0;                                                                                                             \
+        long long m;                                                                                                          \
+        int un;                                                                                                               \
+        asm volatile(BODY WN_AP_STAGE_LOOK                                                                                    \
+                     : [sum] "=&v"(sum), [ok] "=&v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [un] "=&s"(un)                         \
+                     : [tag] "s"(tag), [xa] "v"(xa)                                                                           \
+                     : WN_AP_CLOBBERS);                                                                                       \
+        return un;                                                                                                            \
+    }
+WN_AP_LOOK_STAGE_FN(wn_ap_look4_stage, WN_AP_LOOK4_BODY)
+WN_AP_LOOK_STAGE_FN(wn_ap_look2_stage, WN_AP_LOOK2_BODY)
+WN_AP_LOOK_STAGE_FN(wn_ap_look1_stage, WN_AP_LOOK1_BODY)
+static __device__ __forceinline__ int wn_ap_spin4_stage(unsigned off, const wn_u64* p0, const wn_u64* p1, const wn_u64* p2, const wn_u64* p3, uint32_t tag, int rounds,
+                                                               unsigned xa, float& sum, int& ok) {
+    float t0;
+    long long m;
+    int cnt, un;
+    asm volatile(WN_AP_SPIN4_BODY("\ts_branch 3f\n") WN_AP_STAGE_SPIN
+                 : [sum] "+v"(sum), [ok] "+v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [cnt] "=&s"(cnt), [un] "=&s"(un)
+                 : [off] "v"(off), [p0] "s"(p0), [p1] "s"(p1), [p2] "s"(p2), [p3] "s"(p3), [tag] "s"(tag), [rounds] "s"(rounds), [xa] "v"(xa)
+                 : WN_AP_CLOBBERS);
+    return un;
+}
+static __device__ __forceinline__ int wn_ap_spin2_stage(unsigned off, const wn_u64* p0, const wn_u64* p1, uint32_t tag, int rounds, unsigned xa, float& sum, int& ok) {
+    float t0;
+    long long m;
+    int cnt, un;
+    asm volatile(WN_AP_SPIN2_BODY("\ts_branch 3f\n") WN_AP_STAGE_SPIN
+                 : [sum] "+v"(sum), [ok] "+v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [cnt] "=&s"(cnt), [un] "=&s"(un)
+                 : [off] "v"(off), [p0] "s"(p0), [p1] "s"(p1), [tag] "s"(tag), [rounds] "s"(rounds), [xa] "v"(xa)
+                 : WN_AP_CLOBBERS);
+    return un;
+}
+static __device__ __forceinline__ int wn_ap_spin1_stage(unsigned off, const wn_u64* p0, uint32_t tag, int rounds, unsigned xa, float& sum, int& ok) {
+    float t0;
+    long long m;
+    int cnt, un;
+    asm volatile(WN_AP_SPIN1_BODY("\ts_branch 3f\n") WN_AP_STAGE_SPIN
+                 : [sum] "+v"(sum), [ok] "+v"(ok), [t0] "=&v"(t0), [m] "=&s"(m), [cnt] "=&s"(cnt), [un] "=&s"(un)
+                 : [off] "v"(off), [p0] "s"(p0), [tag] "s"(tag), [rounds] "s"(rounds), [xa] "v"(xa)
+                 : WN_AP_CLOBBERS);
+    return un;
 }
 
 // ---- The queue group's tap FIFO, hand-scheduled for the same reason.  Queue taps x[t+1-d] are requested WN_V3_TAP_AHEAD items ahead
@@ -449,6 +517,53 @@ static __device__ __forceinline__ void wn_weights_resident() { __builtin_amdgcn_
 // compile-time bool as a function argument (the store flavour of a publication, the host's choice of the DIAG instantiation)
 template <bool B> struct WnBool { static constexpr bool value = B; };
 
+// ---- The layer's input through the staging blocks: every form of the layer role but the slot re-use one, whose schedule has moved by several percent
+// on smaller edits and which therefore keeps look + finish_input (wn_v3_layer), instruction for instruction.  cfg3 x 64: 1.133 -> 1.167 M samples/s,
+// x 32: 663 -> 723 k; the hop 0.447 -> 0.388 us (profiles/r17_staged_poll.txt, with the two other arrangements that were built and measured).  Served exit
+// of either block -> barrier A with no test but the block's own scalar flag; the bounded wait (abort word, wall clock, give up, look again: same order,
+// same bounds and codes as finish_input) sits behind ONE rarely taken branch, entered when a spin has run out of its 64 double rounds.  `xa`, the lane's
+// staging address, is an operand: ready before the wait (the item loop computes it next to the request).  A wave that gives up stages nothing: its
+// workgroup still meets at barrier A and leaves the item loop before barrier B, so what the window computes on the stale x is never published.
+// (A function of its own, not a lambda of wn_v3_layer: the slot re-use form never instantiates it, and its instruction stream stays what it was.)
+// (readfirstlane: the flags ARE scalars; spelled out, because the optimiser merges them with the not-polling lanes' path into lane-dependent values,
+//  and a branch on those is an exec-mask ladder again.)
+// PP = granules per lane: the caller picks the instantiation (layer 0 and an unsplit stack: 1) OUTSIDE, so that a block's flag reaches its test without
+// a merge of the forms' flags in between.
+template <int PP, bool DIAG>
+static __device__ __forceinline__ void wn_v3_fetch_input(WnCtx& cx, const WnRun& r, const wn_u64* xb0, size_t xstep_j, unsigned off, uint32_t tag, unsigned xa,
+                                                        int where, long long e, int s, long long item, bool stamper, long long* park4) {
+    static_assert(PP == 1 || PP == 2 || PP == 4, "the hand-scheduled input poll is written for one, two and four partials");
+    auto look = [&](float& sum, int& ok) -> int {
+        if constexpr (PP == 1) return wn_ap_look1_stage(tag, xa, sum, ok);
+        else if constexpr (PP == 2) return wn_ap_look2_stage(tag, xa, sum, ok);
+        else return wn_ap_look4_stage(tag, xa, sum, ok);
+    };
+    auto spin = [&](float& sum, int& ok) -> int {
+        if constexpr (PP == 1) return wn_ap_spin1_stage(off, xb0, tag, 64, xa, sum, ok);
+        else if constexpr (PP == 2) return wn_ap_spin2_stage(off, xb0, xb0 + xstep_j, tag, 64, xa, sum, ok);
+        else return wn_ap_spin4_stage(off, xb0, xb0 + xstep_j, xb0 + 2 * xstep_j, xb0 + 3 * xstep_j, tag, 64, xa, sum, ok);
+    };
+    float sum;
+    int ok;
+    if (__builtin_expect(__builtin_amdgcn_readfirstlane(look(sum, ok)) != 0, 1)) {   // (a stale first look is the rule where the consumer waits for the token)
+        if (__builtin_expect(__builtin_amdgcn_readfirstlane(spin(sum, ok)) != 0, 0)) {
+            // cold path: ~64 double rounds between looks at the abort word and the wall clock  (cx.fail is 0 here: a wave that gave up has left the item loop)
+            unsigned spins = 0;
+            for (;;) {
+                if (__hip_atomic_load(cx.p->status, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) { cx.fail = 1; break; }
+                const long long now = (long long)wall_clock64();
+                if (spins++ == 0u) cx.t_start = now;
+                else if (now - cx.t_start > cx.r->timeout_ticks) { wn_give_up(cx, where, e, s); break; }
+                if (__builtin_amdgcn_readfirstlane(look(sum, ok)) == 0) break;  // (set A was re-requested at the end of the spin)
+                if (__builtin_amdgcn_readfirstlane(spin(sum, ok)) == 0) break;
+            }
+        }
+    }
+    if constexpr (DIAG) {   // "input in registers" -- and, in this form, on its way to LDS
+        if (r.prof && item < r.prof_items && stamper) park4[item & 1] = (long long)wall_clock64();
+    }
+}
+
 template <class SH, int P, int G, int SK = 0, bool DIAG = false>
 static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds, int l, int c) {
     constexpr int R = SH::R, DC = SH::DC, S = SH::S, T1 = SH::T1, K1 = SH::K1, T2 = SH::T2, K2 = SH::K2, RS = SH::RS;
@@ -552,6 +667,12 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
             if (r.prof && item2 < r.prof_items && (tid & 255) == 0) park4[item2 & 1] = (long long)wall_clock64();
         }
     };
+    // ---- ... and the same with the store inside the poll blocks (wn_v3_fetch_input above): every form but the slot re-use one, which keeps look +
+    // finish_input.  xst0 = the polling lane's byte address in x buffer 0 (a generic pointer into LDS: its low half is the LDS address).
+    constexpr bool STAGED = SK == 0;
+    constexpr unsigned XBUF_BYTES = (unsigned)(G * L::XR * sizeof(float));
+    unsigned xst0 = 0;
+    if constexpr (STAGED) xst0 = (unsigned)(size_t)(xs + tg * L::XR + SH::xpad(tr));
     // the first evaluation's input of layer 0 is a given sample: start_conv row gather (wavenet_model.py:127, 256-257)
     auto given_input = [&](int s2, float* xb2) {
         const int idx = r.first[(size_t)(s2 + tg) * r.n_given];
@@ -607,6 +728,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
         wn_weights_resident();
         if (poller) request(0);
         int buf = 0;
+        unsigned xst = xst0;  // the polling lane's staging address for the coming item
         for (long long e = 0; e < r.n_eval; ++e) {
             const uint32_t tag = (uint32_t)(e + 1);
             for (int s = 0; s < ns; s += G, buf ^= 1) {
@@ -616,10 +738,17 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                 // ---- 1. layer input x[t] of the item's G streams
                 if (l == 0 && e == 0) { if (poller) given_input(s, xb); }
                 else if (poller) {  // (set A was requested at the end of the previous item)
-                    float sum;
-                    int ok;
-                    look(tag, sum, ok);
-                    finish_input(e, s, xb, sum, ok, item);
+                    if constexpr (STAGED) {
+                        const unsigned off = xlane + (unsigned)s * (unsigned)(R * 8);
+                        if (one) wn_v3_fetch_input<1, DIAG>(cx, r, xb0, xstep_j, off, tag, xst, l == 0 ? WN_W_LOGITS : WN_W_X, e, s, item, (tid & 255) == 0, park4);
+                        else if constexpr (P > 1) wn_v3_fetch_input<P, DIAG>(cx, r, xb0, xstep_j, off, tag, xst, WN_W_X, e, s, item, (tid & 255) == 0, park4);
+                    }
+                    else {
+                        float sum;
+                        int ok;
+                        look(tag, sum, ok);
+                        finish_input(e, s, xb, sum, ok, item);
+                    }
                 }
                 const int fail_a = wn_barrier_flag(cx, failflag);  // ---- A(i): x staged
                 wn_stamp<DIAG>(r, park, item, 1);
@@ -732,6 +861,7 @@ static __device__ void wn_v3_layer(const WnPlan& p, const WnRun& r, WnCtx& cx, f
                     }
                 }
                 if (poller) request(s + G < ns ? s + G : 0);  // set A of the coming item
+                if constexpr (STAGED) xst = xst0 + (unsigned)(buf ^ 1) * XBUF_BYTES;  // ... and where its input goes (the other x buffer)
                 if (fail_b) return;
             }
         }
