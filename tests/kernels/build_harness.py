@@ -1,6 +1,6 @@
-"""TEST INFRASTRUCTURE ONLY: builds tests/kernels/libwn_kernel_harness.so, the training-time kernels of the product launched one at a
-time through their own launchers (wn_kernel_harness.hip includes csrc/wn_runtime.hip).  Same compiler and flags as the product's
-runtime unit (pytorch-wavenet_amd/build.py), linked with an object of wn_stacked.hip.  The product package never loads it.
+"""TEST INFRASTRUCTURE ONLY: builds tests/kernels/libwn_kernel_harness.so, the one library of the kernel-level tests: the product's kernels
+launched one at a time through their own launchers (wn_kernel_harness.hip includes csrc/wn_runtime.hip, once).  Same compiler and flags as the
+product's runtime unit (pytorch-wavenet_amd/build.py), linked with an object of wn_stacked.hip.  The product package never loads it.
 
     python tests/kernels/build_harness.py          # build if stale
     python tests/kernels/build_harness.py --force

@@ -1,10 +1,16 @@
-// wn_kernel_harness.hip -- TEST INFRASTRUCTURE ONLY: the product's kernels launched one at a time: the training-time matrix-core kernels
-// (tests/test_gpu_kernels.py) and the inference kernels -- tap product, score head, ring fill, the small layout kernels (tests/test_gpu_infer_kernels.py).
+// wn_kernel_harness.hip -- TEST INFRASTRUCTURE ONLY: the product's kernels launched one at a time, every group of kernel-level tests in one library:
+//   kh_*   the training-time matrix-core kernels (tests/test_gpu_kernels.py) and the inference kernels -- tap product, score head, ring fill, the
+//          small layout kernels (tests/test_gpu_infer_kernels.py)
+//   kf_*   the generation chain's two samplers, one draw per workgroup (tests/test_gpu_sampler_kernels.py, tests/test_gpu_sampler_filter_kernels.py)
+//   kst_*  the gather / scatter of a stream's canonical state (tests/test_gpu_state_kernels.py)
+//   kt_*   the k-tap training step's input-gradient product (tests/test_gpu_taps_train_kernels.py)
+//   kb_*   the bf16 filter/gate product of kernel_size 3 / 4 (tests/test_gpu_taps_bf16_kernels.py)
 //
-// The product's runtime unit is included as it is, so its own static launchers (wn_launch_nn, wn_launch_tn, wn_launch_colsum, wn_launch_layer,
-// wn_launch_bwd_layer) and kernels, with their dispatch conditions, are the code under test: nothing is copied.  The entry points take plain
+// The product's runtime unit is included as it is, ONCE, so its own static launchers (wn_launch_nn, wn_launch_tn, wn_launch_colsum, wn_launch_layer,
+// wn_launch_bwd_layer, ...) and kernels, with their dispatch conditions, are the code under test: nothing is copied.  The entry points take plain
 // scalars and device pointers, zero-fill the argument structs as the product does, launch on the given stream and return hipGetLastError().
-// A row map is passed as (base, batch_stride, row_stride, t0).  The product package never loads this library (tests/kernels/build_harness.py).
+// A row map is passed as (base, batch_stride, row_stride, t0).  The signatures are bound in tests/kernel_lib.py; a change of any of them raises
+// kh_version.  The product package never loads this library (tests/kernels/build_harness.py).
 #include "../../pytorch-wavenet_amd/csrc/wn_runtime.hip"
 
 #define KH_MAP(p) const void *p##_base, long long p##_bs, long long p##_rs, long long p##_t0
@@ -17,9 +23,66 @@ struct KhDet {
     ~KhDet() { t_tn_det[0] = nullptr; }
 };
 
+// ---------------------------------------------------------------- the samplers' callers (wrappers: kf_*, below)
+// wn_sample_1w<true> (wn_kernel_v3.h; <false>, the product form with the filters off) and wn_sample (wn_kernel.h, with wn_smp_carve) on logits handed
+// over bit for bit.  Each kernel does what the sampler's caller does around the call and nothing else: load the row, build the run the sampler reads
+// -- zero-filled, `reg`, and the launch's top_k / top_p as wn_generate would have normalised them (0 = off) --, call, store the index.  `greedy` is
+// the caller's flag (r.greedy != 0 || !(temp > 0)): the samplers take it as an argument.
+#define KF_TAIL 64             // floats behind the planner's sampler scratch that must come back untouched
+#define KF_SENT 0x7FC0DEADu    // (tests/kernel_lib.py SENT32)
+
+// one 64-thread workgroup per row, lane l holds the classes 4l .. 4l+3; every lane stores the index it got
+template <bool FILTER>
+__global__ __launch_bounds__(64) void kf_sample_1w_kernel(int top_k, float top_p, const float* logits, const float* reg, const double* u, const int* greedy,
+                                                          const float* temp, int* out) {
+    const size_t row = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    WnRun r;
+    memset(&r, 0, sizeof(r));
+    r.reg = reg;
+    r.top_k = top_k;
+    r.top_p = top_p;
+    float logit[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) logit[k] = logits[row * 256 + 4 * lane + k];
+    out[row * 64 + lane] = wn_sample_1w<FILTER>(r, logit, lane, u[row], greedy[row] != 0, temp[row]);
+}
+
+// one WN_THREADS workgroup per row; dynamic LDS = smp_floats (wn_smp_floats) + KF_TAIL sentinel floats
+__global__ __launch_bounds__(WN_THREADS) void kf_sample_generic_kernel(int C, int smp_floats, int top_k, float top_p, const float* logits, const float* reg,
+                                                                       const double* u, const int* greedy, const float* temp, int* out, uint32_t* tail) {
+    extern __shared__ __attribute__((aligned(16))) float kf_lds[];
+    const size_t row = blockIdx.x;
+    WnPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    pl.C = C;
+    pl.l_smp = 0;
+    WnRun r;
+    memset(&r, 0, sizeof(r));
+    r.reg = reg;
+    r.top_k = top_k;
+    r.top_p = top_p;
+    WnCtx cx{&pl, &r, kf_lds, 0, 0, 0};
+    const WnSmp sm = wn_smp_carve(pl, kf_lds);
+    WN_PHASE {
+        if (tid < KF_TAIL) reinterpret_cast<uint32_t*>(kf_lds)[smp_floats + tid] = KF_SENT;
+        for (int i = tid; i < C; i += WN_THREADS) sm.lgt[i] = logits[row * C + i];
+    }
+    WN_SYNC();
+    wn_sample(cx, sm, u[row], greedy[row] != 0, temp[row]);
+    WN_PHASE {
+        if (tid == 0) out[row] = sm.iscal[0];
+        if (tid < KF_TAIL) tail[row * KF_TAIL + tid] = reinterpret_cast<const uint32_t*>(kf_lds)[smp_floats + tid];
+    }
+}
+
+// what wn_generate puts into the run: the off values are 0
+static int kf_norm_k(int top_k, int C) { return top_k > 0 && top_k < C ? top_k : 0; }
+static float kf_norm_p(float top_p) { return top_p > 0.f && top_p < 1.f ? top_p : 0.f; }
+
 extern "C" {
 
-int kh_version() { return 2; }
+int kh_version() { return 3; }
 
 // One NN product through wn_launch_nn.  bn != NULL: the bf16 forms (B as bf16 [N][ldb]); else fp32 with B^T = bt [K][N] (bt1: rows k >= k_split).
 int kh_nn(void* stream, int epi, KH_MAP(a0), KH_MAP(a1), int k_split, int K, const float* bt, const float* bt1, int N, const float* bias,
@@ -203,6 +266,114 @@ int kh_transpose_batched(void* stream, const float* in, long long in_batch_strid
     (void)hipGetLastError();
     hipLaunchKernelGGL(wn_transpose_batched, dim3((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32), (unsigned)batches), dim3(256), 0, (hipStream_t)stream,
                        in, in_batch_stride, out, rows, cols);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- the samplers (tests/test_gpu_sampler_kernels.py: filter_form 0 and top_k = top_p = 0; tests/test_gpu_sampler_filter_kernels.py)
+int kf_smp_floats(int C) { return wn_smp_floats(C); }
+int kf_run_bytes() { return (int)sizeof(WnRun); }
+
+// out: rows * 64 indices (one per lane).  filter_form 1: wn_sample_1w<true>, 0: wn_sample_1w<false> (which never looks at top_k / top_p)
+int kf_sample_1w(void* stream, int filter_form, int rows, int top_k, float top_p, const float* logits, const float* reg, const double* u, const int* greedy,
+                 const float* temp, int* out) {
+    if (rows < 1 || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f)) return -1;
+    (void)hipGetLastError();
+    if (filter_form)
+        hipLaunchKernelGGL(kf_sample_1w_kernel<true>, dim3(rows), dim3(64), 0, (hipStream_t)stream, kf_norm_k(top_k, 256), kf_norm_p(top_p), logits, reg, u, greedy, temp, out);
+    else
+        hipLaunchKernelGGL(kf_sample_1w_kernel<false>, dim3(rows), dim3(64), 0, (hipStream_t)stream, 0, 0.f, logits, reg, u, greedy, temp, out);
+    return (int)hipGetLastError();
+}
+
+// out: rows indices; tail: rows * 64 words, the floats behind the scratch as they are after the draw.  -1: arguments the scratch is not planned for
+int kf_sample_generic(void* stream, int rows, int C, int top_k, float top_p, const float* logits, const float* reg, const double* u, const int* greedy,
+                      const float* temp, int* out, uint32_t* tail) {
+    if (rows < 1 || C < 1 || C > 4096 || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f)) return -1;
+    const int smp_floats = wn_smp_floats(C);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kf_sample_generic_kernel, dim3(rows), dim3(WN_THREADS), (size_t)(smp_floats + KF_TAIL) * sizeof(float), (hipStream_t)stream, C, smp_floats,
+                       kf_norm_k(top_k, C), kf_norm_p(top_p), logits, reg, u, greedy, temp, out, tail);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- generation state (tests/test_gpu_state_kernels.py)
+// wn_state_gather / wn_state_scatter (csrc/wn_state.inl) on rings the test makes up, through the product's own launchers (which choose the float4 or the
+// scalar kernel).  The tables (ring offsets, canonical row offsets, dilations) are DEVICE arrays the test uploads, as wn_create does.
+
+// 1 iff the launchers take the float4 kernels for this geometry and state pointer
+int kst_vec(int R, int R_own, const float* state) {
+    WnStateGeom g = {};
+    g.R = R; g.R_own = R_own;
+    return wn_state_vec(g, state) ? 1 : 0;
+}
+
+int kst_gather(void* stream, const int64_t* ring_off, const int64_t* row_off, const int32_t* dil, int NL, int k, int R, int R_own, int n_streams, int P,
+               long long rows, const float* rings, long long t, int s, float* state) {
+    if (NL < 1 || s < 0 || s >= n_streams || R_own > R || rows < 1) return -1;
+    const WnStateGeom g{ring_off, row_off, dil, NL, k, R, R_own, n_streams, P};
+    (void)hipGetLastError();
+    wn_state_launch_gather((hipStream_t)stream, g, rows, rings, t, s, state);
+    return (int)hipGetLastError();
+}
+
+int kst_scatter(void* stream, const int64_t* ring_off, const int64_t* row_off, const int32_t* dil, int NL, int k, int R, int R_own, int n_streams, int P,
+                long long rows, float* rings, long long t, int s0, int count, const float* state) {
+    if (NL < 1 || s0 < 0 || count < 1 || s0 + count > n_streams || R_own > R || rows < 1) return -1;
+    const WnStateGeom g{ring_off, row_off, dil, NL, k, R, R_own, n_streams, P};
+    (void)hipGetLastError();
+    wn_state_launch_scatter((hipStream_t)stream, g, rows, rings, t, s0, count, state);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- the k-tap input-gradient product (tests/test_gpu_taps_train_kernels.py)
+// wn_launch_taps_bwd -> wn_bwd_gemm_taps<3>, <4>.  The argument struct is filled field by field as wn_layer_dx_taps (csrc/wn_forward.inl) fills it, with
+// every quantity that function derives passed in instead, so that the kernel's row windows can be driven apart from the training step's geometry.
+
+// dx = (cin on the rows >= cin_skip_lo of an entry) + sum_j a(t + (taps-1-j) tap_rows) . B_j: `a` = the view of [dF|dG](t) (rows of two_d floats that
+// exist for t in [t_lo, t_hi)), B_j = bt + j * bt_tap_stride, [two_d][N].  -1: not a kernel size of the launcher.
+int kt_bwd_taps(void* stream, int taps, KH_MAP(a), long long tap_rows, long long t_lo, long long t_hi, int two_d, const float* bt, long long bt_tap_stride, int N,
+                KH_MAP(cin), int cin_skip_lo, KH_MAP(c), long long M, int rows_per_batch) {
+    WnTapsBwdArgs x;
+    memset(&x, 0, sizeof(x));
+    x.g.a0 = KH_ROWMAP(a); x.g.a1 = KH_ROWMAP(a); x.g.k_split = two_d; x.g.K = taps * two_d; x.g.bt = bt; x.g.N = N;
+    x.g.cin = KH_ROWMAP(cin); x.g.cin_skip_lo = cin_skip_lo; x.g.c = KH_ROWMAP(c); x.g.M = M; x.g.rows_per_batch = rows_per_batch;
+    x.tap_rows = tap_rows; x.t_lo = t_lo; x.t_hi = t_hi; x.bt_tap_stride = bt_tap_stride;
+    if (taps != 3 && taps != 4) return -1;
+    (void)hipGetLastError();
+    wn_launch_taps_bwd((hipStream_t)stream, taps, x);
+    return (int)hipGetLastError();
+}
+
+// The same product with its arguments built by the training step's own helper (wn_layer_dx_taps): dense [dF|dG] of rows_dfg rows per entry, dx and dx'
+// on the rows_out trailing rows of clips of L rows of R floats (dxin == NULL: the last layer's form, no addend).
+int kt_layer_dx(void* stream, int taps, int R, int D, const float* dfg, long long rows_dfg, long long rows_out, long long d, const float* btT, long long tap_stride,
+                const float* dxin, float* dx, long long L, long long n) {
+    if (taps != 3 && taps != 4) return -1;
+    WnPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    pl.R = R; pl.D = D; pl.k = taps;
+    const WnTapsBwdArgs x = wn_layer_dx_taps(pl, dfg, rows_dfg, rows_out, d, btT, tap_stride, dxin ? wn_rows(dxin, L, R, L - rows_out) : WnRowMap{nullptr, 0, 0, 0},
+                                             wn_rows(dx, L, R, L - rows_out), n);
+    (void)hipGetLastError();
+    wn_launch_taps_bwd((hipStream_t)stream, taps, x);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- the bf16 tap product (tests/test_gpu_taps_bf16_kernels.py)
+// wn_launch_taps_bf16 -> wn_fwd_gemm_taps_bf16<3 | 4, 4 | 8>, its arguments filled as kh_taps fills them.
+
+// z = gate([x(t - (taps-1) tap_rows) | ... | x(t)] . B^T + bias): x fp32 rows of R floats, B = bn, bf16 [N][taps * R].  -1: not a kernel size of the launcher.
+int kb_taps_bf16(void* stream, int taps, KH_MAP(x), long long tap_rows, long long t_min, int R, const unsigned short* bn, int N, const float* bias, KH_MAP(z),
+                 long long M, int rows_per_batch, KH_MAP(c2), int c2_first_row) {
+    WnTapsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g.a0 = KH_ROWMAP(x); a.g.a1 = KH_ROWMAP(x); a.g.k_split = R; a.g.K = taps * R; a.g.N = N; a.g.bias = bias;
+    a.g.c = KH_ROWMAP(z); a.g.M = M; a.g.rows_per_batch = rows_per_batch;
+    a.g.c2 = KH_ROWMAP(c2); a.g.c2_first_row = c2_first_row;
+    a.tap_rows = tap_rows; a.t_min = t_min;
+    if (taps != 3 && taps != 4) return -1;
+    (void)hipGetLastError();
+    wn_launch_taps_bf16((hipStream_t)stream, taps, a, bn);
     return (int)hipGetLastError();
 }
 

@@ -1,7 +1,7 @@
 """The inference kernels one at a time, through the product's own launchers and launch geometry (tests/kernels/wn_kernel_harness.hip includes
 csrc/wn_runtime.hip), against float64 references: the tap product of kernel_size 3 / 4, the score kernels, the ring fill and the small layout
-kernels.  Method, helpers and the session fixture `kh` are those of tests/test_gpu_kernels.py (exact / rounding / bounded; every output inside
-sentinel guards that must come back untouched; NaN in every input row a kernel must not read).
+kernels.  The method is that of tests/test_gpu_kernels.py, the helpers and the session fixture `kh` are tests/kernel_lib.py's (exact / rounding /
+bounded; every output inside sentinel guards that must come back untouched; NaN in every input row a kernel must not read).
 
 Branch table: each hipLaunchKernelGGL line reached -> the cases (test ids) that take it.
   wn_launch_taps   wn_fwd_gemm_taps<3>                      test_taps[k3-*], test_taps_gates[k3-*], test_taps_t_min[k3-*]
@@ -26,10 +26,10 @@ import numpy as np
 import pytest
 import torch
 
-from kernel_lib import NOMAP
+from kernel_lib import (GATE_ABS, NOMAP, SENT16, SENT32, WALL, Rows, _bounded, _check_gate_out, _gate64, _pairwise, _rounding_points, _stream, _worst, assert_bits, bits16,
+                        dev, from16, host, rne16)
+from kernel_lib import kh  # noqa: F401  (the session fixture)
 from parity_common import LOGIT_RTOL
-from test_gpu_kernels import (GATE_ABS, SENT16, SENT32, Rows, WALL, _bounded, _check_gate_out, _rounding_points, _stream, _worst, assert_bits, bits16, dev,  # noqa: F401
-                              from16, host, kh, rne16)
 
 pytestmark = pytest.mark.gpu
 
@@ -63,13 +63,6 @@ TAP_R = [32, 64, 96, 128]        # 2 .. 8 K chunks of WN_GEMM_KC = 16 per view: 
 TAP_N = [64, 128, 192, 256]      # a partial only tile, one full tile, a partial second tile, two full tiles
 TAP_D = [1, 2, 7, "big"]         # tap distance; big = rows_per_batch + 3
 TAP_C2 = ["first", "mid", "last"]
-
-
-def _gate64(v, N):
-    F = np.concatenate([v[:, 64 * j:64 * j + 32] for j in range(N // 64)], axis=1)
-    G = np.concatenate([v[:, 64 * j + 32:64 * j + 64] for j in range(N // 64)], axis=1)
-    th, sg = np.tanh(F), 1 / (1 + np.exp(-G))
-    return th * sg, th, sg
 
 
 def _taps_case(kh, taps, M, rpb, R, N, d, bias, c2_first, gates=None, t0=None, t_min=0, zero_prefix=0, seed=0):
@@ -164,26 +157,6 @@ def _taps_case(kh, taps, M, rpb, R, N, d, bias, c2_first, gates=None, t0=None, t
             assert (g2[M] == SENT32).all(), tag + ": the gates run past row M"
             _bounded("gate tanh", g[:M].view(np.float32), th, 0)
             _bounded("gate sigmoid", g2[:M].view(np.float32), sg, 0)
-
-
-def _pairwise(sizes, seed):
-    """a covering selection: every pair of values of every two factors occurs in some case (greedy over seeded random candidates)"""
-    rs = np.random.RandomState(seed)
-    nf = len(sizes)
-    need = {(a, i, b, j) for a in range(nf) for b in range(a + 1, nf) for i in range(sizes[a]) for j in range(sizes[b])}
-    out = []
-    while need:
-        best, gain = None, -1
-        for _ in range(64):
-            cand = tuple(int(rs.randint(s)) for s in sizes)
-            g = sum((a, cand[a], b, cand[b]) in need for a in range(nf) for b in range(a + 1, nf))
-            if g > gain:
-                best, gain = cand, g
-        if gain <= 0:
-            continue
-        out.append(best)
-        need -= {(a, best[a], b, best[b]) for a in range(nf) for b in range(a + 1, nf)}
-    return out
 
 
 def _tap_cases(taps):

@@ -40,149 +40,17 @@ Branch table: each hipLaunchKernelGGL line of the launchers -> the cases (test i
 (The inference kernels -- wn_launch_taps, the score kernels, ring fill, the small layout kernels: tests/test_gpu_infer_kernels.py, with a table of its own.)
 """
 import os
-import time
 
 import numpy as np
 import pytest
 import torch
 
-import kernel_lib
-from kernel_lib import NOMAP
+from kernel_lib import NOMAP, SENT16, SENT32, Rows, _bounded, _check_gate_out, _rounding_points, _stream, _worst, assert_bits, bits16, dev, from16, host, nan_rows, rne16
+from kernel_lib import kh  # noqa: F401  (the session fixture)
 
 pytestmark = pytest.mark.gpu
 
 PLAIN, GATE, GATE_BWD = 0, 1, 2
-SENT32 = np.uint32(0x7FC0DEAD)    # sentinel of fp32 outputs (a NaN no kernel produces)
-SENT16 = np.uint16(0x7FDE)        # ... of bf16 outputs
-WORST = {}
-WALL = {}    # module -> its own wall time in seconds (modules that share the harness and its closing line)
-_T0 = time.time()
-
-
-def _worst(family, err):
-    WORST[family] = max(WORST.get(family, 0.0), float(err))
-
-
-_KH = []   # the loaded harness: tests/test_gpu_infer_kernels.py imports this fixture, and both modules share one harness and one closing line
-
-
-@pytest.fixture(scope="session")
-def kh(request):
-    if _KH:
-        return _KH[0]
-    t0 = time.time()
-    h = kernel_lib.build_and_load()
-    build_s = time.time() - t0
-
-    def report():
-        capman = request.config.pluginmanager.getplugin("capturemanager")
-        with capman.global_and_fixture_disabled():
-            print("\ntest_gpu_kernels%s: %.1f s wall (harness build / load %.1f s); worst errors of the bounded families: %s"
-                  % ("".join(" (+ %s: %.1f s wall of its own)" % kv for kv in sorted(WALL.items())), time.time() - _T0, build_s, ", ".join("%s %.3g" % kv for kv in sorted(WORST.items()))))
-        h.close()
-    request.addfinalizer(report)
-    _KH.append(h)
-    return h
-
-
-def _stream():
-    return torch.cuda.current_stream().cuda_stream
-
-
-# ---------------------------------------------------------------- numerics
-def rne16(x):
-    """fp32 -> the fp32 value of its bf16 round-to-nearest-even (finite inputs)"""
-    b = np.ascontiguousarray(x, dtype=np.float32).view(np.uint32).astype(np.uint64)
-    b = ((b + 0x7FFF + ((b >> 16) & 1)) >> 16) << 16
-    return (b & 0xFFFFFFFF).astype(np.uint32).view(np.float32)
-
-
-def bits16(x):
-    """fp32 values that are bf16 numbers -> their bf16 bit patterns"""
-    return (np.ascontiguousarray(x, dtype=np.float32).view(np.uint32) >> 16).astype(np.uint16)
-
-
-def from16(b):
-    return (np.asarray(b, dtype=np.uint16).astype(np.uint32) << 16).view(np.float32)
-
-
-def dev(a):
-    a = np.ascontiguousarray(a)
-    if a.dtype == np.uint16:
-        return torch.from_numpy(a.view(np.int16)).cuda()
-    if a.dtype == np.uint32:
-        return torch.from_numpy(a.view(np.int32)).cuda()
-    return torch.from_numpy(a).cuda()
-
-
-def host(t, dtype):
-    return t.cpu().numpy().view(dtype)
-
-
-class Rows:
-    """A (batch, time) row matrix as the kernels address it: entry q of M // rpb (+1), rows t0 .. t0 + rpb - 1 of `T`, `cols` used columns of
-    `ld`.  Everything around the rows in use -- rows before t0, the gap behind each entry, the columns past `cols` -- is a guard."""
-
-    def __init__(self, M, rpb, cols, bf16=False, t0=3, gap=5, pad=8, fill=None):
-        self.M, self.rpb, self.cols, self.bf16, self.t0 = M, rpb, cols, bf16, t0
-        self.nb = (M + rpb - 1) // rpb
-        self.T, self.ld = t0 + rpb + gap, cols + pad
-        if fill is None:
-            self.h = np.full((self.nb, self.T, self.ld), SENT16 if bf16 else SENT32, dtype=np.uint16 if bf16 else np.uint32)
-        else:
-            self.h = fill
-        self.d = None
-
-    def rows(self):
-        m = np.arange(self.M)
-        return m // self.rpb, self.t0 + m % self.rpb
-
-    def put(self, vals):
-        """vals: [M][cols] float32 (bf16 numbers when bf16) written into the rows in use"""
-        q, t = self.rows()
-        v = np.asarray(vals, dtype=np.float32)
-        self.h[q, t, :self.cols] = bits16(v) if self.bf16 else v.view(np.uint32)
-        return self
-
-    def upload(self):
-        self.d = dev(self.h)
-        return self
-
-    def map(self, t0_shift=0):
-        return (self.d.data_ptr(), self.T * self.ld, self.ld, self.t0 + t0_shift)
-
-    def got(self):
-        return host(self.d, np.uint16 if self.bf16 else np.uint32)
-
-    def expect(self, vals, rows=None):
-        """the whole buffer as it must come back: the sentinel, `vals` [M][cols] on the rows in use (or on the rows where `rows` is True)"""
-        e = self.h.copy()
-        q, t = self.rows()
-        v = np.asarray(vals, dtype=np.float32)
-        b = bits16(v) if self.bf16 else v.view(np.uint32)
-        if rows is None:
-            e[q, t, :self.cols] = b
-        else:
-            e[q[rows], t[rows], :self.cols] = b[rows]
-        return e
-
-
-def nan_rows(M, rpb, cols, vals, bf16=False, lo=0, hi=0, t0=3):
-    """an input row matrix: `vals` on its rows, NaN everywhere else -- also on the rows a window hides (rem < lo, rem >= rpb - hi)"""
-    r = Rows(M, rpb, cols, bf16=bf16, t0=t0)
-    r.h[...] = 0x7FC0 if bf16 else 0x7FC00000
-    v = np.array(vals, dtype=np.float32)
-    rem = np.arange(M) % rpb
-    hide = (rem < lo) | (rem >= rpb - hi)
-    v[hide] = np.nan
-    r.put(v)   # (bits16 of a NaN is a bf16 NaN)
-    return r.upload()
-
-
-def assert_bits(got, exp, what):
-    if not np.array_equal(got, exp):
-        bad = np.argwhere(got != exp)
-        raise AssertionError("%s: %d element(s) differ, first at %s: got %s, want %s" % (what, len(bad), tuple(bad[0]), hex(int(got[tuple(bad[0])])), hex(int(exp[tuple(bad[0])]))))
 
 
 # ---------------------------------------------------------------- NN products (wn_launch_nn)
@@ -339,31 +207,6 @@ def _nn_case(kh, form, epi, M, rpb, N, K, k_split=None, a16=False, lo=(0, 0), hi
     del keep
 
 
-# The bound of the gate epilogue: wn_exp is accurate to ~1e-7 absolute on the exponent's range, the reciprocals to 1 ulp, tanh = 2 sigmoid(2f) - 1
-# loses up to 2 ulp of 1 in the subtraction: |tanh - tanh64| <= 4e-7, |sigmoid - sigmoid64| <= 2e-7 (relative where tiny), |z - z64| <= 6e-7.
-GATE_ABS = 1e-6
-
-
-def _bounded(family, got, ref, rel16):
-    """|got - ref| <= GATE_ABS + rel16 * |ref| (rel16 = 2^-8: a bf16 output adds half an ulp of its own)"""
-    err = np.abs(got.astype(np.float64) - ref)
-    ok = err <= GATE_ABS + rel16 * np.abs(ref)
-    ok |= np.isnan(ref) & np.isnan(got)
-    _worst(family, np.nanmax(np.where(np.isnan(ref), 0, err)) if err.size else 0)
-    assert ok.all(), "%s: %d element(s) beyond the bound, worst %.3g" % (family, (~ok).sum(), np.nanmax(err))
-
-
-def _check_gate_out(c, z, tag, is16):
-    got = c.got()
-    q, t = c.rows()
-    vals = got[q, t, :c.cols]
-    gz = from16(vals) if is16 else vals.view(np.float32)
-    _bounded("gate z (bf16)" if is16 else "gate z", gz, z, 2.0 ** -8 if is16 else 0)
-    e = c.h.copy()
-    e[q, t, :c.cols] = vals
-    assert_bits(got, e, tag + " guards")
-
-
 NN_FORMS = [   # (id, form, epi, a16)
     ("f32-plain", "f32", PLAIN, False), ("f32-gate", "f32", GATE, False), ("f32-gatebwd", "f32", GATE_BWD, False),
     ("bf16-plain", "bf16", PLAIN, False), ("bf16-gate", "bf16", GATE, False), ("bf16-gatebwd", "bf16", GATE_BWD, False),
@@ -432,14 +275,6 @@ def test_gate_nonlinearity(kh, form):
     got = c.got()[c.rows()[0], c.rows()[1], :N // 2].view(np.float32)
     assert np.array_equal(np.isnan(got), np.isnan(z)), "NaN where the reference has none, or a NaN lost: %s" % got[0]
     _check_gate_out(c, z, "gate sweep", False)
-
-
-def _rounding_points(shape, rs):
-    """fp32 values below, on (even and odd last bit) and above bf16 rounding points: b + f with b an 8-bit integer, scaled by 2^-7"""
-    b = rs.randint(128, 256, shape).astype(np.float64)
-    f = rs.choice([0.5 - 2.0 ** -16, 0.5, 0.5 + 2.0 ** -16, 0.25, 0.75, 0.0], shape)
-    sgn = rs.choice([-1.0, 1.0], shape)
-    return (sgn * (b + f) / 128).astype(np.float32)
 
 
 @pytest.mark.parametrize("wide", [False, True], ids=["narrow", "wide"])

@@ -1,5 +1,5 @@
 """-m gpu: the two kernels behind wn_state_save / wn_state_load (csrc/wn_state.inl: wn_state_gather, wn_state_scatter) alone, through the product's
-launchers (tests/kernels/wn_state_harness.hip includes csrc/wn_runtime.hip), on made-up rings.  Every float of a ring is a bit pattern that encodes
+launchers (tests/kernels/wn_kernel_harness.hip includes csrc/wn_runtime.hip), on made-up rings.  Every float of a ring is a bit pattern that encodes
 (layer, stream, copy, slot, channel) -- the copies of a stream DIFFER, so a gather that read another copy than 0 would show -- and NaN sentinel bands
 surround every buffer.  All comparisons are on the bits.
 
@@ -9,38 +9,29 @@ surround every buffer.  All comparisons are on the bits.
   * gather back at that time from every stream of the range: the identity
 Dilations 1, 2, 4 with k = 2 and 3; queue times 0, 1, ML-1, ML, 3 ML + 2 (ML of the largest ring); P = 1, 2, 4; streams 0, the middle, the last, a range
 in between; R / R_own = 16/16, 32/24 (padded), 7/7 (scalar kernels), 128/128."""
-import ctypes
-import os
-import sys
 import time
 
 import numpy as np
 import pytest
 import torch
 
+from kernel_lib import kh  # noqa: F401  (the session fixture)
+
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 GUARD = 64
 SENT = np.uint32(0x7FC0DEAD)
 DIL = (1, 2, 4)
 NS = 5
-_P, _I, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
 _T = {}
 
 
 @pytest.fixture(scope="module")
-def kst():
+def kst(kh):
+    """the shared harness's library (tests/kernel_lib.py), and this module's record at its end"""
     t0 = time.time()
-    sys.path.insert(0, os.path.join(HERE, "kernels"))
-    import build_state_harness
-    dll = ctypes.CDLL(os.environ.get("WN_STATE_HARNESS") or build_state_harness.build_harness())
-    dll.kst_gather.argtypes = [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _LL, _P, _LL, _I, _P]
-    dll.kst_scatter.argtypes = [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _LL, _P, _LL, _I, _I, _P]
-    dll.kst_vec.argtypes = [_I, _I, _P]
-    dll.kst_gather.restype = dll.kst_scatter.restype = dll.kst_vec.restype = _I
-    assert dll.kst_version() == 1, "stale harness (tests/kernels/build_state_harness.py --force)"
-    yield dll
-    print("\ntest_gpu_state_kernels: %.1f s wall with the harness's build / load; %d gathers, %d scatters, all bit equal" % (time.time() - t0, _T.get("g", 0), _T.get("s", 0)))
+    yield kh.dll
+    print("\ntest_gpu_state_kernels: %.1f s wall (with the harness's build / load only where this module is the first to ask for it); %d gathers, %d scatters, all bit equal"
+          % (time.time() - t0, _T.get("g", 0), _T.get("s", 0)))
 
 
 def _dev(a):

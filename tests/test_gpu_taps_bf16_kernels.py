@@ -1,4 +1,4 @@
-"""-m gpu: the bf16 filter/gate product of kernel_size 3 / 4, one launch at a time through its own launcher (tests/kernels/wn_taps_bf16_harness.hip
+"""-m gpu: the bf16 filter/gate product of kernel_size 3 / 4, one launch at a time through its own launcher (tests/kernels/wn_kernel_harness.hip
 includes csrc/wn_runtime.hip: wn_launch_taps_bf16 -> wn_fwd_gemm_taps_bf16<3 | 4, 4 | 8>):
 
     z = gate([x(t - (k-1) d) | ... | x(t - d) | x(t)] . B^T + b),   x fp32 rounded to bf16 (RNE) while staged, B bf16 [N][k*R], fp32 accumulation,
@@ -17,23 +17,15 @@ Two operand sets per case:
             accumulation of K terms in whatever grouping the matrix core uses: each partial sum is within 2^-24 of its value relative to Sum|a b|, at
             most K roundings, doubled for slack; the gate's slope is at most 1).  The data must move z by more than 1000 GATE_ABS under truncation.
 In both sets the data must tell a reversed, a row-shifted and a zeroed view by more than 1000 GATE_ABS in every 128-row tile where that view is read."""
-import ctypes
-import os
-import sys
-
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_infer_kernels import _gate64, _pairwise
-from test_gpu_kernels import GATE_ABS, Rows, _stream, assert_bits, bits16, dev, rne16
+from kernel_lib import GATE_ABS, Rows, _gate64, _pairwise, _stream, assert_bits, bits16, dev, rne16
+from kernel_lib import kh  # noqa: F401  (the session fixture)
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 NAN32 = np.uint32(0x7FC00000)
-_P, _I, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-_MAP = [_P, _LL, _LL, _LL]
-NOMAP = (None, 0, 0, 0)
 RPB = 37
 
 KB_R = [64, 128]
@@ -44,14 +36,8 @@ KB_TMIN = ["eq", "above", "below"]   # t0 - (k-1) d, the oldest tap of an entry'
 
 
 @pytest.fixture(scope="module")
-def kb():
-    sys.path.insert(0, os.path.join(HERE, "kernels"))
-    import build_taps_bf16_harness
-    dll = ctypes.CDLL(build_taps_bf16_harness.build_harness())
-    dll.kb_taps_bf16.argtypes = [_P, _I] + _MAP + [_LL, _LL, _I, _P, _I, _P] + _MAP + [_LL, _I] + _MAP + [_I]
-    dll.kb_taps_bf16.restype = _I
-    assert dll.kb_version() == 1, "stale harness (tests/kernels/build_taps_bf16_harness.py --force)"
-    return dll
+def kb(kh):
+    return kh.dll
 
 
 def _case_data(taps, M, R, N, d, tmin, bias, mode, seed):

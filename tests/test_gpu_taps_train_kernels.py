@@ -1,5 +1,5 @@
 """-m gpu: the input-gradient product of the kernel_size 3 / 4 training step, one launch at a time through its own launcher
-(tests/kernels/wn_taps_train_harness.hip includes csrc/wn_runtime.hip: wn_launch_taps_bwd -> wn_bwd_gemm_taps<3>, <4>):
+(tests/kernels/wn_kernel_harness.hip includes csrc/wn_runtime.hip: wn_launch_taps_bwd -> wn_bwd_gemm_taps<3>, <4>):
 
     dx(i) = cin(i) [i >= cin_skip_lo]  +  sum_j a(i - sh + (k-1-j) d) . B_j      for the output rows i of every batch entry,
 
@@ -14,35 +14,20 @@ Cases: for k = 3 and 4 a pairwise cover of M in {127, 129, 383} x rows_per_batch
 (the last leaves only the shift-0 view alive) x N = R in {32, 96, 160} (narrower than, and across, the 128-column tile) x 2D in {64, 192} x the addend
 (absent, cin_skip_lo = 0, cin_skip_lo = (k-1) d); single-row clips; and the product as the training step's own helper describes it (wn_layer_dx_taps).
 sh = (k-1) d, the training step's value, where that leaves an entry rows of [dF|dG] -- both ends of the window are then in play --, else 0."""
-import ctypes
-import os
-import sys
-
 import numpy as np
 import pytest
 import torch
 
-from test_gpu_infer_kernels import _pairwise
-from test_gpu_kernels import SENT32, Rows, _stream, assert_bits, dev, nan_rows
+from kernel_lib import NOMAP, SENT32, Rows, _pairwise, _stream, assert_bits, dev, nan_rows
+from kernel_lib import kh  # noqa: F401  (the session fixture)
 
 pytestmark = pytest.mark.gpu
-HERE = os.path.dirname(os.path.abspath(__file__))
 NAN32 = np.uint32(0x7FC00000)
-_P, _I, _LL = ctypes.c_void_p, ctypes.c_int, ctypes.c_longlong
-_MAP = [_P, _LL, _LL, _LL]
-NOMAP = (None, 0, 0, 0)
 
 
 @pytest.fixture(scope="module")
-def kt():
-    sys.path.insert(0, os.path.join(HERE, "kernels"))
-    import build_taps_train_harness
-    dll = ctypes.CDLL(build_taps_train_harness.build_harness())
-    dll.kt_bwd_taps.argtypes = [_P, _I] + _MAP + [_LL, _LL, _LL, _I, _P, _LL, _I] + _MAP + [_I] + _MAP + [_LL, _I]
-    dll.kt_layer_dx.argtypes = [_P, _I, _I, _I, _P, _LL, _LL, _LL, _P, _LL, _P, _P, _LL, _LL]
-    dll.kt_bwd_taps.restype = dll.kt_layer_dx.restype = _I
-    assert dll.kt_version() == 1, "stale harness (tests/kernels/build_taps_train_harness.py --force)"
-    return dll
+def kt(kh):
+    return kh.dll
 
 
 def _operands(rs, shape):

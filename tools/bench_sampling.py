@@ -5,10 +5,9 @@
 Jobs: per (config, streams) one engine; every round runs the legs one after the other -- filter off, filter on, and with --other-lib the unfiltered job
 on another build of the library (the parent commit's, for the "unfiltered legs did not move" comparison) -- and the table gives median and min - max of
 the rounds in samples/s.  --samplers N adds the same legs on an engine planned with WN_SAMPLERS=N (multi-stream jobs: the sampler workgroups may be what
-a filtered job waits for).  --kernels: the two samplers alone through tests/kernels/libwn_sampler_filter_harness.so (one draw per workgroup), time of a
+a filtered job waits for).  --kernels: the two samplers alone through tests/kernels/libwn_kernel_harness.so (one draw per workgroup), time of a
 launch of 4096 rows and of 64 rows, filter off / top_k / top_p / both, HIP events, median of 20."""
 import argparse
-import ctypes
 import os
 import statistics
 import sys
@@ -76,12 +75,9 @@ def bench_jobs(args):
 
 
 def bench_kernels(args):
-    sys.path.insert(0, os.path.join(ROOT, "tests", "kernels"))
-    import build_sampler_filter_harness
-    kf = ctypes.CDLL(build_sampler_filter_harness.build_harness())
-    P, I, F = ctypes.c_void_p, ctypes.c_int, ctypes.c_float
-    kf.kf_sample_1w.argtypes = [P, I, I, I, F, P, P, P, P, P, P]
-    kf.kf_sample_generic.argtypes = [P, I, I, I, F, P, P, P, P, P, P, P]
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import kernel_lib
+    kf = kernel_lib.build_and_load().dll
     rs = np.random.RandomState(2)
     dev = torch.device("cuda", 0)
     stream = torch.cuda.current_stream(dev).cuda_stream
