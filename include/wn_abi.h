@@ -290,6 +290,31 @@ int wn_set_forward_precision(wn_handle* h, int32_t bf16);
  * changed; a caller that must run against an older library of version 5 looks the symbol up.) */
 int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p);
 
+/* Per-sample log-probabilities of the NEXT wn_generate on the handle, written by the sampler kernels next to out_idx.
+ *   logp: DEVICE pointer to float32 [n_streams][num_samples], laid out like out_idx; capacity: its size in floats.  Valid after wn_wait.  Given
+ *     (teacher-forced) samples have no position in the array, as in out_idx.
+ *   The call ARMS the next wn_generate only: that call consumes the arming whether it succeeds or not (a pointer that stayed behind would be an
+ *     out-of-bounds write of a later, longer job).  An armed wn_generate whose n_streams * num_samples exceeds capacity returns WN_E_BADARG and
+ *     launches nothing.  logp == NULL disarms.  WN_E_BADARG: a NULL handle, a negative capacity, a mode other than the two below.  Valid before
+ *     wn_load_weights.  A handle of several rounds hands every member its slice of the array, as for out_idx.
+ *   What is written for generated sample g of stream s, i being the class the sampler returned -- stated in float64 on float32 inputs that are
+ *   the same bits on host and device:
+ *     WN_LOGP_MODEL:    l = the summed float32 logits of the step (what dbg_logits dumps: before the regulariser, no temperature, no filter);
+ *       logp = l_i - max(l) - log(sum_j exp(l_j - max(l))): the model's own log-likelihood of the sample, the negative of wn_score's row_nll for
+ *       that position; the same for sampled and greedy streams.
+ *     WN_LOGP_SAMPLING: the distribution the draw was made from.  x = the row of wn_set_sampling's contract, fl32(logit - regularizer), then
+ *       fl32(x / temperature); K = the set that contract keeps (all classes without a filter); logp = x_i - max(x) - log(sum_{j in K} exp(x_j -
+ *       max(x))), and -inf if i is not in K (the clamp at u >= 1 alone returns such a class).  A greedy stream has no division and no filter: the
+ *       log-softmax of fl32(logit - regularizer) at the argmax.
+ *     Rows with non-finite logits are unspecified.
+ *   The kernels evaluate (x_i - gm) - logf(tot) in float32, gm and tot being the very maximum and kept-mass sum the draw uses: the value does not
+ *   come from log(mass), so a kept class whose float32 mass underflowed still gets a finite value.
+ * An armed job runs the instantiations that carry the sampling filters (a greedy one too); a job that is not armed runs, instruction for
+ * instruction, the kernel it ran before this function existed.  (Added without a new WN_ABI_VERSION, like wn_set_sampling.) */
+#define WN_LOGP_SAMPLING 0
+#define WN_LOGP_MODEL 1
+int wn_set_logprob_output(wn_handle* h, float* logp, int64_t capacity, int32_t mode);
+
 /* The priming loop of generate_fast (wavenet_model.py:259-269) for ALL given samples at once: `first_samples` is a DEVICE
  * pointer to int32 [n_streams][row_stride]; the first n_prime (= n_given - 1) samples of every stream are evaluated teacher
  * forced with the forward GEMM kernels (no skip / head work: the reference discards those outputs) and the queues are left

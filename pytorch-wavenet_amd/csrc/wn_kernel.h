@@ -123,6 +123,12 @@ WN_DEV bool wn_not_resident(WnCtx& cx, float* lds) {
     return failed != 0;
 }
 
+// The log-probability output of an armed job (r.logp != 0): float32 [n_streams][num_samples], laid out like out_idx.  The pointer sits in status[6..7], written by
+// the host behind the status words' memset and ahead of the launch; NULL (never on an armed job) means "write nothing".
+WN_DEV float* wn_logp_out(const WnPlan& p) {
+    return reinterpret_cast<float*>(__hip_atomic_load(reinterpret_cast<const wn_u64*>(p.status + 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+
 // Spin until the granule carries `tag`.  Bounded: gives up after r->timeout_ticks of wall clock or as
 // soon as any workgroup has raised the abort word, so the kernel always terminates.
 WN_DEV float wn_wait_granule(WnCtx& cx, const wn_u64* g, uint32_t tag, int where, long long e, int s) {
@@ -381,6 +387,73 @@ WN_DEV void wn_sample(WnCtx& cx, const WnSmp& sm, double u, bool greedy, float t
     WN_SYNC();
 }
 
+// The log-probability of the class wn_sample just returned (wn_set_logprob_output; the contract is in include/wn_abi.h), from what it left in LDS:
+// (v_i - max v) - logf(sum of the kept exp(v_j - max v)) in fp32, sums in wn_sample's order (16 chunks, then the chunks' partials).
+//   WN_LOGP_SAMPLING: v = xsm and the maximum is the draw's fscal[0]; a sampled stream's sum is the draw's own (its partials ps[] are still there -- not
+//                     log(mass): a kept class whose mass underflowed gets a finite value), a greedy stream's is computed here.  A class the filter dropped
+//                     (the clamp at u >= 1 alone returns one) gets -inf.
+//   WN_LOGP_MODEL:    v = lgt, the step's summed logits: one more maximum and sum, through pm / ps / fscal[2], which nobody reads any more.
+WN_DEV void wn_sample_logp(WnCtx& cx, const WnSmp& sm, bool greedy, size_t at) {
+    const WnPlan& p = *cx.p;
+    const WnRun& r = *cx.r;
+    const int C = p.C, G = WN_SAMPLER_GROUPS, chunk = (C + G - 1) / G;
+    const bool model = r.logp == 2;
+    const float* v = model ? sm.lgt : sm.xsm;
+    const int mslot = model ? 2 : 0;
+    if (model) {
+        WN_PHASE {
+            if (tid < G) {
+                const int lo = tid * chunk, hi = lo + chunk < C ? lo + chunk : C;
+                float m = -INFINITY;
+                for (int i = lo; i < hi; ++i) m = v[i] > m ? v[i] : m;
+                sm.pm[tid] = m;
+            }
+        }
+        WN_SYNC();
+        WN_PHASE {
+            if (tid == 0) {
+                float m = sm.pm[0];
+                for (int g = 1; g < G; ++g) m = sm.pm[g] > m ? sm.pm[g] : m;
+                sm.fscal[2] = m;
+            }
+        }
+        WN_SYNC();
+    }
+    if (model || greedy) {
+        WN_PHASE {
+            if (tid < G) {
+                const int lo = tid * chunk, hi = lo + chunk < C ? lo + chunk : C;
+                const float m = sm.fscal[mslot];
+                float s = 0.f;
+                for (int i = lo; i < hi; ++i) s += expf(v[i] - m);
+                sm.ps[tid] = s;
+            }
+        }
+        WN_SYNC();
+    }
+    WN_PHASE {
+        if (tid == 0) {
+            const int idx = sm.iscal[0];
+            const float m = sm.fscal[mslot], vi = v[idx];
+            float s = 0.f;
+            for (int g = 0; g < G; ++g) s += sm.ps[g];
+            bool member = true;
+            if (!model && !greedy && sm.pp[idx] == 0.f) {
+                // mass 0.0: dropped by a filter, or kept and underflowed.  An underflowed class never survives top_p (the mass above it is the whole: the
+                // maximum's 1.0 is part of it); it survives top_k iff fewer than k classes are strictly greater.
+                member = expf(vi - m) == 0.f && !(r.top_p > 0.f);
+                if (member && r.top_k > 0) {
+                    int above = 0;
+                    for (int j = 0; j < C; ++j) above += sm.xsm[j] > vi ? 1 : 0;
+                    member = above < r.top_k;
+                }
+            }
+            float* out = wn_logp_out(p);
+            if (out) out[at] = member ? (vi - m) - logf(s) : -INFINITY;
+        }
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // L0 only: obtain the class index that enters the network at evaluation e of stream s and turn it into
 // the layer-0 input x (start_conv column).  e == n_eval is the extra, sample-only iteration.
@@ -421,6 +494,7 @@ WN_DEV bool wn_l0_input(WnCtx& cx, int c, long long e, int s) {
             if (c == 0) {
                 WN_PHASE { if (tid == 0) r.out_idx[(size_t)s * r.num_samples + g] = sm.iscal[0]; }
             }
+            if (r.logp && c == 0) wn_sample_logp(cx, sm, greedy, (size_t)s * r.num_samples + g);
         }
     }
     if (e == r.n_eval) { WN_SYNC(); return true; }

@@ -1544,7 +1544,8 @@ static __device__ __forceinline__ uint32_t wn_order_key(float x) {
     const uint32_t b = __float_as_uint(x == 0.f ? 0.f : x);
     return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
-static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, const float (&x)[4], float gm, float (&pk)[4]) {
+// `keep`: bit k of the lane's word says whether class 4 lane + k stayed (what the log-probability needs: a kept class whose fp32 mass underflowed has pk = 0.0 too)
+static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, const float (&x)[4], float gm, float (&pk)[4], uint32_t& keep) {
     uint32_t key[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) key[k] = wn_order_key(x[k]);
@@ -1575,14 +1576,38 @@ static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, cons
         }
 #pragma unroll
         for (int k = 0; k < 4; ++k) pk[k] = key[k] > edge ? pk[k] : 0.f;
+        kth = edge >= kth ? edge + 1u : kth;   // (edge < 2^32 - 1: the largest key has no mass above it.  The survivors of both: key >= kth)
     }
+    keep = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) keep |= key[k] >= kth ? 1u << k : 0u;
+}
+static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, const float (&x)[4], float gm, float (&pk)[4]) {
+    uint32_t keep;
+    wn_filter_1w(top_k, top_p, x, gm, pk, keep);
 }
 
 // FILTER = false is the product's sampler, instruction for instruction what it was before the filters existed; FILTER = true (the DIAG kernels, which a
 // job with a filter runs: wn_chain_launch) reads r.top_k / r.top_p HERE -- behind the logits' poll, like the temperature -- and with both off computes
 // the same pk[] as the other form.  u >= 1 clamps to class 255 whatever the filter kept (a harness-only input).
-template <bool FILTER = false>
-static __device__ __forceinline__ int wn_sample_1w(const WnRun& r, const float (&logit)[4], int lane, double u, bool greedy, float temperature) {
+//
+// LOGP (wn_set_logprob_output, include/wn_abi.h; the instantiations that carry the filters, and there only while r.logp is set): the log-probability of the
+// class that was returned, (v_i - max v) - logf(sum of the kept exp(v_j - max v)) in fp32.  v_i is one readlane (idx is wave-uniform after the draw).
+//   WN_LOGP_SAMPLING: v = x, and max and sum are the draw's own gm and tot -- not log(mass): a kept class whose mass underflowed gets a finite value; a class
+//                     the filter dropped (the clamp at u >= 1 alone returns one) gets -inf.  A greedy stream computes the sum here: it needs none to draw.
+//   WN_LOGP_MODEL:    v = logit, the step's summed logits (what dbg_logits dumps): a second max / expf / sum over the wave, the same for every kind of stream.
+static __device__ __forceinline__ float wn_lane_class_f(const float (&v)[4], int idx) {   // v of class idx (wave-uniform): lane idx / 4, element idx % 4
+    const int k = idx & 3;
+    const float mine = k == 0 ? v[0] : k == 1 ? v[1] : k == 2 ? v[2] : v[3];
+    return wn_lane_f(mine, (idx >> 2) & 63);
+}
+static __device__ __forceinline__ float wn_logp_model_1w(const float (&logit)[4], int idx) {
+    const float m = wn_wave_max(fmaxf(fmaxf(logit[0], logit[1]), fmaxf(logit[2], logit[3])));
+    const float t = wn_wave_sum(((expf(logit[0] - m) + expf(logit[1] - m)) + expf(logit[2] - m)) + expf(logit[3] - m));
+    return (wn_lane_class_f(logit, idx) - m) - logf(t);
+}
+template <bool FILTER, bool LOGP>
+static __device__ __forceinline__ int wn_sample_1w_lp(const WnRun& r, const float (&logit)[4], int lane, double u, bool greedy, float temperature, float& logp) {
     float x[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1593,11 +1618,24 @@ static __device__ __forceinline__ int wn_sample_1w(const WnRun& r, const float (
     const float gm = wn_wave_max(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
     if (greedy) {  // first index of the maximum (torch.max semantics)
         const int mine = x[0] == gm ? 4 * lane : x[1] == gm ? 4 * lane + 1 : x[2] == gm ? 4 * lane + 2 : x[3] == gm ? 4 * lane + 3 : 0x7fffffff;
-        return wn_wave_min_i(mine);
+        const int idx = wn_wave_min_i(mine);
+        if constexpr (LOGP) {
+            if (r.logp) {
+                if (r.logp == 2) {
+                    logp = wn_logp_model_1w(logit, idx);
+                } else {
+                    const float t = wn_wave_sum(((expf(x[0] - gm) + expf(x[1] - gm)) + expf(x[2] - gm)) + expf(x[3] - gm));
+                    logp = (wn_lane_class_f(x, idx) - gm) - logf(t);
+                }
+            }
+        }
+        return idx;
     }
     float pk[4];
+    uint32_t keep = 0xfu;
     if constexpr (FILTER) {
-        wn_filter_1w(r.top_k, r.top_p, x, gm, pk);   // (dropped classes: mass 0.0; the rest of the draw is the same code)
+        if constexpr (LOGP) wn_filter_1w(r.top_k, r.top_p, x, gm, pk, keep);
+        else wn_filter_1w(r.top_k, r.top_p, x, gm, pk);   // (dropped classes: mass 0.0; the rest of the draw is the same code)
     } else {
 #pragma unroll
         for (int k = 0; k < 4; ++k) pk[k] = expf(x[k] - gm);
@@ -1640,7 +1678,23 @@ static __device__ __forceinline__ int wn_sample_1w(const WnRun& r, const float (
     int idx = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) idx += __popcll(__builtin_amdgcn_ballot_w64(le[k]));
-    return idx > 255 ? 255 : idx;
+    idx = idx > 255 ? 255 : idx;
+    if constexpr (LOGP) {
+        if (r.logp) {
+            if (r.logp == 2) {
+                logp = wn_logp_model_1w(logit, idx);
+            } else {
+                const bool member = ((uint32_t)__builtin_amdgcn_readlane((int)keep, (idx >> 2) & 63) >> (idx & 3)) & 1u;
+                logp = member ? (wn_lane_class_f(x, idx) - gm) - logf(tot) : -INFINITY;
+            }
+        }
+    }
+    return idx;
+}
+template <bool FILTER = false>
+static __device__ __forceinline__ int wn_sample_1w(const WnRun& r, const float (&logit)[4], int lane, double u, bool greedy, float temperature) {
+    float logp;
+    return wn_sample_1w_lp<FILTER, false>(r, logit, lane, u, greedy, temperature, logp);   // (the draw alone: what the product kernels run)
 }
 
 // the partial logits of N head slices (h0 ..) for this lane's four consecutive classes (32 contiguous bytes per slice: two 16-byte
@@ -1719,7 +1773,8 @@ static __device__ __forceinline__ void wn_poll_class(WnCtx& cx, __amdgpu_buffer_
 // sums meet in LDS (lds_lg, 256 floats) and wave 0 draws as in the one-wave form -- same sums in the same order, two LDS barriers more.
 // (Variant 4 takes WIDE from eight head slices up, wn_kernel_v4.h; in variant 3 it was level and is not used: profiles/r04_sampler_prefetch_and_wide_sampler.txt.)
 // FILTER: the draw is wn_sample_1w<FILTER> (by default what DIAG says; the slot re-use form, whose ONE instantiation is DIAG = true and serves unfiltered
-// product jobs, keeps the unfiltered draw there and has the filter in a kernel of its own: wn_generate_kernel_v3m_filter).
+// product jobs, keeps the unfiltered draw there and has the filter in a kernel of its own: wn_generate_kernel_v3m_filter).  The log-probabilities live
+// where the filters live -- wn_sample_1w_lp<true, true>, guarded by r.logp --, so the FILTER = false samplers do not gain even a scalar branch.
 template <class SH, bool WIDE = false, bool DIAG = false, bool FILTER = DIAG>
 static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds_smp, float* lds_tab, int j, float* lds_lg = nullptr) {
     constexpr int R = SH::R, NP = (R / 2 + 63) / 64;  // pairs of row elements per lane
@@ -1803,8 +1858,20 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
                         for (int k = 0; k < 4; ++k) r.dbg_logits[((size_t)s * r.num_samples + g) * 256 + 4 * lane + k] = logit[k];
                     }
                 }
-                idx = wn_sample_1w<FILTER>(r, logit, lane, u, greedy, temp);   // (a job with a sampling filter runs a DIAG instantiation as well)
-                if (lane == 0) r.out_idx[(size_t)s * r.num_samples + g] = idx;
+                if constexpr (FILTER) {   // (a job with a sampling filter or a log-probability output runs a DIAG instantiation as well)
+                    float logp = 0.f;
+                    idx = wn_sample_1w_lp<true, true>(r, logit, lane, u, greedy, temp, logp);
+                    if (lane == 0) {
+                        r.out_idx[(size_t)s * r.num_samples + g] = idx;
+                        if (r.logp) {
+                            float* out = wn_logp_out(p);   // (loaded where it is used: two registers less across the poll)
+                            if (out) out[(size_t)s * r.num_samples + g] = logp;
+                        }
+                    }
+                } else {
+                    idx = wn_sample_1w<false>(r, logit, lane, u, greedy, temp);
+                    if (lane == 0) r.out_idx[(size_t)s * r.num_samples + g] = idx;
+                }
             }
             if (e < r.n_eval) {
                 auto publish = [&](auto li_c) __attribute__((always_inline)) {   // (the uniform test of the flavour outside the lane predicate)
@@ -1832,8 +1899,8 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
 // by construction, not by the luck of the allocator; the launch bound still gives every lane the 168 the blocks address).  On gfx90a and
 // later the backend DOUBLES the attribute's value (unified VGPR + AGPR file) before it compares it with the occupancy limit -- a value above
 // 84 is silently dropped at 3 waves per SIMD -- hence WN_V3_COMPILER_VGPRS / 2; build.py disassembles the library and checks the result.
-// DIAG: the instantiation with the wall-clock stamps (wn_profile_next), the sampler's logits dump and the sampling filters (wn_set_sampling); the
-// product instantiation has none of them.
+// DIAG: the instantiation with the wall-clock stamps (wn_profile_next), the sampler's logits dump, the sampling filters (wn_set_sampling) and the
+// per-sample log-probabilities (wn_set_logprob_output); the product instantiation has none of them.
 // SK > 0 (the slot re-use form) exists in the DIAG = true instantiation ALONE and is what an unfiltered job of 96 streams and more runs
 // (wn_runtime.hip: wn_v2_entry): its sampler keeps the unfiltered draw, so that its instruction stream is what it was before the filters existed.
 template <int R, int DC, int S, int EC, int P, int G = 1, int SK = 0, bool DIAG = false>

@@ -75,7 +75,7 @@ struct WnPlan {
     wn_u64* g0;               // variant 3: layer 0's input, the start_conv row of the sampled class [n_streams][R] (samplers -> L0)
     int32_t n_smp;            // dedicated sampler workgroups (0 in the single-stream kernels)
     int32_t start_in_lds;     // v2 single-stream: layer 0 holds start_conv^T in LDS
-    uint32_t* status;         // [8] 0: abort code, 1: chain position, 2: eval, 3: stream, 4: where
+    uint32_t* status;         // [8] 0: abort code, 1: chain position, 2: eval, 3: stream, 4: where, 5: residency count, 6-7: the log-probability output pointer (WnRun::logp)
     uint32_t* xcc_tab;        // [n_wg] XCC id + 1 of every chain position, written by the workgroups at start
     int32_t n_blocks;         // grid size (>= n_wg; blocks mapped to -1 exit at once)
     int32_t allow_plain;      // same-XCD producers may publish with L2-resident (non write-through) stores
@@ -97,7 +97,9 @@ struct WnRun {
     int64_t timeout_ticks;  // wall_clock64 ticks
     long long* prof;        // optional [n_wg][prof_items][4] wall-clock stamps (diagnostics), or NULL
     int32_t prof_items;
-    int32_t pad;
+    int32_t logp;               // per-sample log-probabilities (wn_set_logprob_output, include/wn_abi.h): 0 = off, else 1 + WN_LOGP_* (1: of the distribution the
+                                // draw was made from, 2: of the step's summed logits).  The former padding word: WnRun keeps its size and every offset.  The output
+                                // pointer does not fit here: the host puts it into status[6..7] (WnPlan::status) ahead of the launch -- wn_logp_out, wn_kernel.h
     const float* stream_temps;  // optional [n_streams]: per-stream temperature (<= 0: that stream is greedy); NULL = `temperature` for all
     int64_t resident_ticks;     // bound of the start-up residency barrier (wn_resident_barrier), wall_clock64 ticks
     // sampling filters (wn_set_sampling, include/wn_abi.h), normalised by the host: 0 = off.  APPENDED: WnRun is the kernels' last argument, so no offset

@@ -116,7 +116,7 @@ struct WnV2Entry {
     // the shape has no such form
     const void* fn_v3[3];
     const void* fn_v3_diag[3];   // the same forms with the stamps and the logits dump compiled in (DIAG: a job with wn_profile_next or dbg_logits)
-    const void* fn_v3_filter;    // form 2 with the sampling filters (the forms 0 and 1 have them in fn_v3_diag); NULL where the shape has no form 2
+    const void* fn_v3_filter;    // form 2 with the sampling filters and the log-probabilities (the forms 0 and 1 have them in fn_v3_diag); NULL where the shape has no form 2
     int (*lds_floats_v3)(int ns, int g2);
     int lds_pre_v3;  // float offset of the per-stream area = what head / sampler workgroups use in front of their own tables
     void (*launch_v3)(int form, bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
@@ -209,7 +209,7 @@ static WnV2Entry wn_v2_entry() {
             auto go = [&](auto diag_c) {
                 constexpr bool DG = decltype(diag_c)::value;
                 if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
-                    if (form == 2 && (r.top_k != 0 || r.top_p != 0.f)) { wn_v3_cfg3_slots_filter_launch(grid, lds, st, p, r); return; }
+                    if (form == 2 && (r.top_k != 0 || r.top_p != 0.f || r.logp != 0)) { wn_v3_cfg3_slots_filter_launch(grid, lds, st, p, r); return; }
                     if (form == 2) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
                 }
                 if constexpr (wn_v3_g2_fits<SH>()) {
@@ -387,6 +387,7 @@ struct wn_handle {
     int fw_bf16_taps = 0;                          //   kernel_size 3 and 4: bf16 operands for wn_forward / wn_score alone (WN_PRECISION_BF16_TAPS)
     int prof_items = 0;      // stamps requested for the next job (0 = off)
     int32_t smp_top_k = 0; float smp_top_p = 0.f;   // sampling filters of every later job (wn_set_sampling; as given: wn_generate normalises the off values)
+    float* logp_out = nullptr; int64_t logp_capacity = 0; int32_t logp_mode = 0;   // log-probability output of the NEXT job alone (wn_set_logprob_output; wn_generate consumes it)
     int prof_recorded = 0;   // stamps held in d_prof
     std::vector<int64_t> ring_off;
     std::vector<int32_t> dil;
@@ -416,7 +417,7 @@ static void wn_free_weights(wn_handle* h) {   // (members i > 0 of a rounds fron
 
 // The chain kernel a handle runs: its function (for the attribute and occupancy queries of wn_create), its workgroup size, its launch
 // (variants 3 and 4 exist twice: the product instantiation and the DIAG one -- wall-clock stamps, logits dump -- that a job with wn_profile_next or
-//  dbg_logits or a sampling filter runs; the generic kernel tests at run time)
+//  dbg_logits or a sampling filter or a log-probability output runs; the generic kernel tests at run time)
 struct WnChainKernel { const void* fn; int threads; };
 static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
     if (h->variant == 4) return WnChainKernel{diag ? wn_v4_table()[h->v2_index].fn_diag : wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
@@ -427,7 +428,7 @@ static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
     return WnChainKernel{(const void*)wn_generate_kernel, WN_THREADS};
 }
 static void wn_chain_launch(const wn_handle* h, hipStream_t st, const WnRun& r) {
-    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr || r.top_k != 0 || r.top_p != 0.f;   // (the sampling filters live in the DIAG samplers)
+    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr || r.top_k != 0 || r.top_p != 0.f || r.logp != 0;   // (the sampling filters and the log-probabilities live in the DIAG samplers)
     if (h->variant == 4)
         wn_v4_table()[h->v2_index].launch(diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
     else if (h->variant == 3)
@@ -906,6 +907,14 @@ extern "C" int wn_reset(wn_handle* h, void* hip_stream) {
 extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     g_err[0] = 0;
     if (!h || !a) return wn_fail(WN_E_BADARG, "wn_generate: NULL argument");
+    // the log-probability output armed for THIS call (wn_set_logprob_output): consumed here, whatever becomes of the call
+    float* const logp_out = h->logp_out;
+    const int64_t logp_capacity = h->logp_capacity;
+    const int32_t logp_mode = h->logp_mode;
+    h->logp_out = nullptr; h->logp_capacity = 0; h->logp_mode = 0;
+    if (logp_out && a->num_samples > 0 && (long long)h->plan.n_streams * (long long)a->num_samples > (long long)logp_capacity)
+        return wn_fail(WN_E_BADARG, "wn_generate: the log-probability output holds %lld floats, the job writes %d x %lld; nothing was launched",
+                       (long long)logp_capacity, h->plan.n_streams, (long long)a->num_samples);
     if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_generate: wn_load_weights has not been called");
     if (!h->chains.empty()) {   // rounds: member i owns streams [chain_first[i], chain_first[i + 1]); one after the other on the caller's stream
         if (a->n_given < 1 || a->num_samples < 0) return wn_fail(WN_E_BADARG, "wn_generate: n_given must be >= 1 and num_samples >= 0");
@@ -922,6 +931,12 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
             if (a->out_idx) b.out_idx = a->out_idx + s0 * (size_t)a->num_samples;
             if (a->dbg_logits) b.dbg_logits = a->dbg_logits + s0 * (size_t)a->num_samples * h->plan.C;
             if (a->stream_temperatures) b.stream_temperatures = a->stream_temperatures + s0;
+            if (logp_out) {   // (the member's slice; the whole array's capacity was checked above)
+                wn_handle* m = h->chains[i];
+                m->logp_out = logp_out + s0 * (size_t)a->num_samples;
+                m->logp_capacity = (int64_t)(h->chain_first[i + 1] - h->chain_first[i]) * a->num_samples;
+                m->logp_mode = logp_mode;
+            }
             if (i == 0 && h->prof_items > 0) { h->chains[0]->prof_items = h->prof_items; h->prof_items = 0; }
             rc = wn_generate(h->chains[i], &b);
             if (rc) {
@@ -957,7 +972,8 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     r.first = a->first_samples; r.n_given = a->n_given; r.num_samples = a->num_samples; r.n_eval = n_eval;
     r.t_base = h->t_base; r.temperature = a->temperature; r.greedy = greedy ? 1 : 0; r.reg = a->regularizer;
     r.uniforms = a->uniforms; r.out_idx = a->out_idx; r.dbg_logits = a->dbg_logits; r.stream_temps = a->stream_temperatures;
-    if (!greedy) {   // (nothing is drawn in a greedy job: it runs the kernel it always ran)
+    r.logp = logp_out ? 1 + logp_mode : 0;   // (the pointer travels in status[6..7], below; an armed job, a greedy one too, runs the instantiation that carries the log-probabilities: wn_chain_launch)
+    if (!greedy) {   // (nothing is drawn in a greedy job: no filter applies to it, and unarmed it runs the kernel it always ran)
         r.top_k = h->smp_top_k < h->plan.C ? h->smp_top_k : 0;
         r.top_p = h->smp_top_p < 1.f ? h->smp_top_p : 0.f;
     }
@@ -1013,6 +1029,11 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     // hand-off words restart at tag 1 every call: zero them (and the status word) ahead of the launch
     int rc = rt_memset_async(h->d_gran, 0, h->gran_count * 8, a->hip_stream);
     rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)(8 + h->plan.n_wg) * 4, a->hip_stream);
+    if (!rc && logp_out) {   // the log-probability output pointer, behind the memset: two 32-bit fills, no host buffer to keep alive (wn_logp_out, wn_kernel.h)
+        const unsigned long long bits = (unsigned long long)(uintptr_t)logp_out;
+        rc = rt_hip(hipMemsetD32Async((hipDeviceptr_t)(h->d_status + 6), (int)(uint32_t)bits, 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
+        rc = rc ? rc : rt_hip(hipMemsetD32Async((hipDeviceptr_t)(h->d_status + 7), (int)(uint32_t)(bits >> 32), 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
+    }
     if (rc) { wn_gate_release(h->gate); h->gate.reset(); return rc; }
     wn_chain_launch(h, (hipStream_t)a->hip_stream, r);
     rc = rt_hip(hipGetLastError(), "launch wn_generate_kernel");
@@ -1158,6 +1179,17 @@ extern "C" int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p) {
     if (!(top_p >= 0.f && top_p <= 1.f)) return wn_fail(WN_E_BADARG, "wn_set_sampling: top_p must lie in [0, 1] (0 and 1: off), got %g", (double)top_p);
     for (wn_handle* c : h->chains) { int rc = wn_set_sampling(c, top_k, top_p); if (rc) return rc; }   // (rounds: every member draws with the same filter)
     h->smp_top_k = top_k; h->smp_top_p = top_p;
+    return WN_OK;
+}
+
+// Per-sample log-probabilities of the NEXT job on the handle (include/wn_abi.h has the contract; wn_generate consumes the arming, the kernels read WnRun)
+extern "C" int wn_set_logprob_output(wn_handle* h, float* logp, int64_t capacity, int32_t mode) {
+    g_err[0] = 0;
+    if (capacity < 0) return wn_fail(WN_E_BADARG, "wn_set_logprob_output: capacity must be >= 0, got %lld", (long long)capacity);
+    if (mode != WN_LOGP_SAMPLING && mode != WN_LOGP_MODEL)
+        return wn_fail(WN_E_BADARG, "wn_set_logprob_output: mode must be WN_LOGP_SAMPLING (0) or WN_LOGP_MODEL (1), got %d", (int)mode);
+    if (!h) return wn_fail(WN_E_BADARG, "wn_set_logprob_output: NULL handle");   // (behind the value checks: those are testable without a device)
+    h->logp_out = logp; h->logp_capacity = logp ? capacity : 0; h->logp_mode = logp ? mode : 0;
     return WN_OK;
 }
 

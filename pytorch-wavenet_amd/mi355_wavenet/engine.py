@@ -182,6 +182,19 @@ class Engine:
         self.lib.check(self.lib.dll.wn_profile_read(self._h, out.ctypes.data, out.size))
         return out
 
+    LOGPROB_MODES = {"sampling": _abi.WN_LOGP_SAMPLING, "model": _abi.WN_LOGP_MODEL}
+
+    def set_logprob_output(self, logp_dev, capacity, mode):
+        """Arms the NEXT job alone to write the log-probability of every generated sample into logp_dev, float32 (n_streams, num_samples) on the device
+        (C ABI wn_set_logprob_output; the contract is in include/wn_abi.h).  mode: "sampling" -- of the distribution the draw was made from -- or "model"
+        -- of the step's own logits.  logp_dev None disarms.  A library without the symbol raises."""
+        if mode not in self.LOGPROB_MODES:
+            raise ValueError('logprobs must be "sampling" or "model", got %r' % (mode,))
+        if not self.lib.has("wn_set_logprob_output"):
+            raise RuntimeError("mi355_wavenet: %s does not export wn_set_logprob_output (a library built before the per-sample log-probabilities were "
+                               "added): rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
+        self.lib.check(self.lib.dll.wn_set_logprob_output(self._h, self.mem.ptr(logp_dev), int(capacity), self.LOGPROB_MODES[mode]))
+
     def launch(self, first_dev, n_given, num_samples, temperature, reg_dev, uni_dev, out_dev, logits_dev, timeout_ms=0,
                temps_dev=None):
         """Enqueue one job on the current stream (asynchronous).  temps_dev: optional fp32 (n_streams,) per-stream temperatures."""
@@ -271,7 +284,8 @@ class Engine:
     PRIME_BATCH_MIN = 64  # given samples from which the GEMM priming path beats the per-sample chain passes
 
     def generate(self, num_samples, first_samples=None, temperature=1.0, regularize=0.0, uniforms=None,
-                 want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None, top_k=None, top_p=None, shared_prompt=False):
+                 want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None, top_k=None, top_p=None, shared_prompt=False,
+                 logprobs=None):
         """first_samples: (n_streams, n_given) or (n_given,) ints (broadcast to every stream) or None -> classes//2.
         uniforms: float64 (n_streams, num_samples) (np.random.random_sample draws) or None -> greedy.
         temperature: a number, or one per stream (a stream with temperature <= 0 is greedy and ignores its uniforms row).
@@ -281,8 +295,12 @@ class Engine:
         top_k / top_p: ``set_sampling`` before the job -- the values STAY on the handle for later jobs; None leaves what the handle has.
         shared_prompt: the streams share their given samples (a 1-D first_samples, or identical rows -- anything else is a ValueError): the batched
         priming runs once over the one row and fills every stream's queues (``prime_shared``).
-        Returns indices int32 (n_streams, num_samples) [, logits float32 (n_streams, num_samples, classes)]."""
+        logprobs: None, "sampling" or "model" -- the log-probability of every generated sample, written by the sampler kernels (``set_logprob_output``).
+        Returns indices int32 (n_streams, num_samples) [, logits float32 (n_streams, num_samples, classes)] [, logp float32 (n_streams, num_samples)]:
+        a tuple as soon as there is more than the indices, the log-probabilities last."""
         ns, C = self.n_streams, self.classes
+        if logprobs is not None and logprobs not in self.LOGPROB_MODES:
+            raise ValueError('logprobs must be None, "sampling" or "model", got %r' % (logprobs,))
         if top_k is not None or top_p is not None:
             self.set_sampling(self._sampling[0] if top_k is None else top_k, self._sampling[1] if top_p is None else top_p)
         if first_samples is None:
@@ -321,11 +339,17 @@ class Engine:
             if batched_prime and n_given - 1 >= self.PRIME_BATCH_MIN and (self.prime_shared(fs[0, :-1]) if shared_prompt else self.prime(first_dev, n_given - 1, n_given)):
                 first_dev = self.mem.upload(np.ascontiguousarray(fs[:, -1:]))  # the last given sample is the next input
                 n_given = 1
+        logp_dev = None
+        if logprobs is not None:
+            logp_dev = self.mem.empty((ns, max(num_samples, 1)), np.float32)
+            self.set_logprob_output(logp_dev, ns * max(num_samples, 1), logprobs)   # (armed right before the job that consumes it)
         self.launch(first_dev, n_given, num_samples, temperature, reg_dev, uni_dev, out_dev, logits_dev, timeout_ms, temps_dev)
         if while_running is not None:
             while_running()
         self.wait()
-        idx = self.mem.download(out_dev)[:, :num_samples]
+        out = [self.mem.download(out_dev)[:, :num_samples]]
         if want_logits:
-            return idx, self.mem.download(logits_dev)[:, :num_samples]
-        return idx
+            out.append(self.mem.download(logits_dev)[:, :num_samples])
+        if logprobs is not None:
+            out.append(self.mem.download(logp_dev)[:, :num_samples])
+        return out[0] if len(out) == 1 else tuple(out)

@@ -434,7 +434,8 @@ class WaveNetModel(nn.Module):
         return self._wn_engine
 
     def generate_fast(self, num_samples, first_samples=None, temperature=1., regularize=0.,
-                      progress_callback=None, progress_interval=100, *, top_k=0, top_p=0., continue_from=None, return_state=False):
+                      progress_callback=None, progress_interval=100, *, top_k=0, top_p=0., continue_from=None, return_state=False,
+                      return_logprobs=False):
         """Same contract as wavenet_model.py:237-315; returns float64 ndarray (num_samples,).
         Extension (keyword only): top_k / top_p truncate every sampled draw inside the sampler kernels (include/wn_abi.h: wn_set_sampling); one
         uniform per sample is drawn from the global numpy RNG as without them, and the engine's filter is off again when the call returns or raises.
@@ -442,7 +443,12 @@ class WaveNetModel(nn.Module):
         ``generate_fast(first_samples=[state.last_index])`` except that the dilation queues are LOADED from the state instead of reset: callbacks,
         the timing print and the RNG's consumption are those of that call.  Together with first_samples it is a ValueError.
         return_state=True: returns (audio, state) -- the stream's state behind the last generated sample (a list of states for a 2-D prompt or a
-        list given as continue_from), to continue from later, in another process (it pickles; ``state.save(path)``) or on other stream counts."""
+        list given as continue_from), to continue from later, in another process (it pickles; ``state.save(path)``) or on other stream counts.
+        return_logprobs="sampling" | "model" (True: "sampling"): the result gains a float32 array shaped like the audio, directly behind it -- (audio,
+        logp) or (audio, logp, state) -- with the log-probability of every generated sample, written by the sampler kernels (include/wn_abi.h:
+        wn_set_logprob_output): of the distribution the draw was made from (temperature and filters applied), or of the model's own logits.  The RNG's
+        consumption, the callbacks and the queues left behind are those of the call without it."""
+        logprobs = self._logprob_mode(return_logprobs)
         states = None
         if continue_from is not None:
             if first_samples is not None:
@@ -450,10 +456,21 @@ class WaveNetModel(nn.Module):
             states, first_samples = self._continue_states(continue_from)
         try:
             return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                                       states, return_state)
+                                       states, return_state, logprobs)
         finally:   # (also when a callback raised between two pieces)
             if (top_k or top_p) and self._wn_engine is not None:
                 self._wn_engine.set_sampling(0, 0.)
+
+    @staticmethod
+    def _logprob_mode(return_logprobs):
+        """return_logprobs of the facade -> Engine.generate's logprobs: None, "sampling" or "model" """
+        if return_logprobs is False or return_logprobs is None:
+            return None
+        if return_logprobs is True:
+            return "sampling"
+        if return_logprobs in ("sampling", "model"):
+            return return_logprobs
+        raise ValueError('return_logprobs must be False, True, "sampling" or "model", got %r' % (return_logprobs,))
 
     def _continue_states(self, continue_from):
         """-> (the states as a list, checked against this model; the first_samples that stand for them: 1-D for a single state, else 2-D)"""
@@ -473,7 +490,7 @@ class WaveNetModel(nn.Module):
                                kernel_size=self.kernel_size, classes=self.classes)
 
     def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                       states=None, return_state=False):
+                       states=None, return_state=False, logprobs=None):
         self.eval()
         if first_samples is None:
             first_samples = torch.LongTensor(1).zero_() + (self.classes // 2)
@@ -528,7 +545,7 @@ class WaveNetModel(nn.Module):
         def n_generated(a0, b0):  # samples the piece [a0, b0) of evaluations generates
             return (b0 - a0) - max(0, min(b0, n_prime) - a0)
 
-        pieces = []
+        pieces, logp_pieces = [], []
         last = None
         tic = time.time()
         ends = sorted(c for c in cuts if c > a)
@@ -551,7 +568,11 @@ class WaveNetModel(nn.Module):
                     def overlap(n_next=n_generated(b, nxt[0])):
                         nonlocal drawn
                         drawn = eng.upload_uniforms(np.random.random_sample((n_streams, n_next)))
-                out = eng.generate(n_new, head, temperature=temperature, regularize=regularize, uniforms=u, reset=False, while_running=overlap)
+                out = eng.generate(n_new, head, temperature=temperature, regularize=regularize, uniforms=u, reset=False, while_running=overlap,
+                                   logprobs=logprobs if n_new > 0 else None)
+                if n_new > 0 and logprobs is not None:
+                    out, lp = out
+                    logp_pieces.append(lp)
                 if n_new > 0:
                     pieces.append(out)
                     last = out[:, -1:].astype(np.int64)
@@ -569,12 +590,16 @@ class WaveNetModel(nn.Module):
         self.train()
         mu_gen = self._expand_indices(idx)  # :296, :314
         audio = mu_gen if batched else mu_gen[0]
+        result = (audio,)
+        if logprobs is not None:   # (the pieces are concatenated like the indices)
+            logp = np.concatenate(logp_pieces, axis=1) if logp_pieces else np.zeros((n_streams, 0), dtype=np.float32)
+            result += (logp if batched else logp[0],)
         if not return_state:
-            return audio
+            return result[0] if len(result) == 1 else result
         nxt = idx[:, -1] if idx.shape[1] else first[:, -1]   # the input of the next step
         before = [st.evals for st in states] if states is not None else [0] * n_streams
         out = [self._stream_state(eng, s, int(nxt[s]), before[s] + n_eval) for s in range(n_streams)]
-        return audio, (out if batched else out[0])
+        return result + (out if batched else out[0],)
 
     def _expand_indices(self, idx):
         """Class indices -> float64 audio: ``o = idx / classes * 2 - 1`` (wavenet_model.py:296) then ``mu_law_expansion(o)``
@@ -610,14 +635,18 @@ class WaveNetModel(nn.Module):
     # of the per-stream pass (tests/test_gpu_generation_state.py), the products run over 1 / n_streams of the rows (profiles/r16_generation_state.txt)
     SHARED_PRIME = True
 
-    def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0., continue_from=None):
+    def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0., continue_from=None,
+                              return_logprobs=False):
         """Extension: one generate_fast() per entry of ``temperatures`` -- the reference's generate_audio loop
         (wavenet_training.py:115-124) -- as parallel streams of ONE persistent-kernel job.  Returns float64
         (len(temperatures), num_samples), row k equal to ``generate_fast(num_samples, first_samples, temperatures[k])``
         of sequential calls: sampled rows consume the global numpy RNG in the order of ``temperatures`` (one draw per
         sample), greedy rows (temperature <= 0, wavenet_model.py:290-294) consume none.  top_k / top_p as in generate_fast (greedy rows ignore them).
         continue_from: ONE ``GenerationState`` that every temperature continues from (N variations of a checkpoint) -- as first_samples=[last_index]
-        with the queues loaded into every stream instead of reset; together with first_samples it is a ValueError."""
+        with the queues loaded into every stream instead of reset; together with first_samples it is a ValueError.
+        return_logprobs as in generate_fast: returns (audio, logp), logp float32 (len(temperatures), num_samples); a greedy row holds the log-softmax
+        value of its argmax."""
+        logprobs = self._logprob_mode(return_logprobs)
         state = None
         if continue_from is not None:
             if first_samples is not None:
@@ -647,13 +676,15 @@ class WaveNetModel(nn.Module):
                 eng.state_load(state.state)   # one state, every stream
             idx = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
                                uniforms=uniforms if any(t > 0 for t in temps) else None, reset=state is None,
-                               shared_prompt=self.SHARED_PRIME and state is None and eng.lib.has("wn_prime_shared"))
+                               shared_prompt=self.SHARED_PRIME and state is None and eng.lib.has("wn_prime_shared"), logprobs=logprobs)
+            if logprobs is not None:
+                idx, logp = idx
         finally:
             if top_k or top_p:
                 eng.set_sampling(0, 0.)
         self._defer_queues(eng, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
         self.train()
-        return self._expand_indices(idx)
+        return self._expand_indices(idx) if logprobs is None else (self._expand_indices(idx), logp)
 
     # ------------------------------------------------------------------ bookkeeping
     def parameter_count(self):
