@@ -297,15 +297,15 @@ int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p);
  *     out-of-bounds write of a later, longer job).  An armed wn_generate whose n_streams * num_samples exceeds capacity returns WN_E_BADARG and
  *     launches nothing.  logp == NULL disarms.  WN_E_BADARG: a NULL handle, a negative capacity, a mode other than the two below.  Valid before
  *     wn_load_weights.  A handle of several rounds hands every member its slice of the array, as for out_idx.
- *   What is written for generated sample g of stream s, i being the class the sampler returned -- stated in float64 on float32 inputs that are
- *   the same bits on host and device:
+ *   What is written for generated sample g of stream s, i being the class written to out_idx (the sampler's draw, or the forced class of
+ *   wn_set_forced_samples) -- stated in float64 on float32 inputs that are the same bits on host and device:
  *     WN_LOGP_MODEL:    l = the summed float32 logits of the step (what dbg_logits dumps: before the regulariser, no temperature, no filter);
  *       logp = l_i - max(l) - log(sum_j exp(l_j - max(l))): the model's own log-likelihood of the sample, the negative of wn_score's row_nll for
  *       that position; the same for sampled and greedy streams.
  *     WN_LOGP_SAMPLING: the distribution the draw was made from.  x = the row of wn_set_sampling's contract, fl32(logit - regularizer), then
  *       fl32(x / temperature); K = the set that contract keeps (all classes without a filter); logp = x_i - max(x) - log(sum_{j in K} exp(x_j -
- *       max(x))), and -inf if i is not in K (the clamp at u >= 1 alone returns such a class).  A greedy stream has no division and no filter: the
- *       log-softmax of fl32(logit - regularizer) at the argmax.
+ *       max(x))), and -inf if i is not in K (only the clamp at u >= 1 or a forced sample gives such a class).  A greedy stream has no division
+ *       and no filter: the log-softmax of fl32(logit - regularizer) at i (the argmax, unless the position is forced).
  *     Rows with non-finite logits are unspecified.
  *   The kernels evaluate (x_i - gm) - logf(tot) in float32, gm and tot being the very maximum and kept-mass sum the draw uses: the value does not
  *   come from log(mass), so a kept class whose float32 mass underflowed still gets a finite value.
@@ -314,6 +314,26 @@ int wn_set_sampling(wn_handle* h, int32_t top_k, float top_p);
 #define WN_LOGP_SAMPLING 0
 #define WN_LOGP_MODEL 1
 int wn_set_logprob_output(wn_handle* h, float* logp, int64_t capacity, int32_t mode);
+
+/* Forced samples of the NEXT wn_generate on the handle: the caller says what a stream emits at a position (ragged prompts, infill, scoring of a
+ * continuation), the sampler kernels put that class where the draw's would go.
+ *   forced: DEVICE pointer to int32 [n_streams][num_samples], laid out like out_idx; capacity: its size in int32 values.  It must stay valid
+ *     until wn_wait.  Given samples have no position in the array, as in out_idx.
+ *   The call ARMS the next wn_generate only: that call consumes the arming whether it succeeds or not (a pointer that stayed behind would be an
+ *     out-of-bounds read of a later, longer job).  An armed wn_generate whose n_streams * num_samples exceeds capacity returns WN_E_BADARG and
+ *     launches nothing.  forced == NULL disarms.  WN_E_BADARG: a NULL handle, a negative capacity.  Valid before wn_load_weights.  A handle of
+ *     several rounds hands every member its slice of the array, as for out_idx and logp.
+ *   Entries: f = forced[s][g].  0 <= f < classes: generated sample g of stream s is forced.  EVERY other value is a free position and the draw
+ *     happens as without the call (-1 is the canonical free value); the kernels test (unsigned)f < classes before f indexes anything.
+ *   A forced position: out_idx[s][g] = f, the start_conv row of f is the next input, queues and state are those of a stream that drew f.
+ *     dbg_logits dumps the step's logits as always.  The position's uniform is not used, but `uniforms` keeps its layout (one per generated
+ *     sample).  Log-probabilities (wn_set_logprob_output) are those of f under the step's distribution, by that contract: WN_LOGP_MODEL is the
+ *     model's log-likelihood of f; WN_LOGP_SAMPLING is -inf if a filter drops f.
+ *   An armed job whose entries are all free returns the bits of the job that was not armed: indices, log-probabilities, queues.
+ * An armed job runs the instantiations that carry the sampling filters and the log-probabilities; a job that is not armed runs, instruction for
+ * instruction, the kernel it ran before this function existed.  A forced position still costs a full chain evaluation: a long forced run whose
+ * log-probabilities nobody wants is a prompt, and wn_prime serves it better.  (Added without a new WN_ABI_VERSION, like wn_set_logprob_output.) */
+int wn_set_forced_samples(wn_handle* h, const int32_t* forced, int64_t capacity);
 
 /* The priming loop of generate_fast (wavenet_model.py:259-269) for ALL given samples at once: `first_samples` is a DEVICE
  * pointer to int32 [n_streams][row_stride]; the first n_prime (= n_given - 1) samples of every stream are evaluated teacher

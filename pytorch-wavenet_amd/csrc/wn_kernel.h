@@ -123,10 +123,15 @@ WN_DEV bool wn_not_resident(WnCtx& cx, float* lds) {
     return failed != 0;
 }
 
-// The log-probability output of an armed job (r.logp != 0): float32 [n_streams][num_samples], laid out like out_idx.  The pointer sits in status[6..7], written by
+// The log-probability output of an armed job (r.logp & WN_RUN_LOGP_MASK): float32 [n_streams][num_samples], laid out like out_idx.  The pointer sits in status[6..7], written by
 // the host behind the status words' memset and ahead of the launch; NULL (never on an armed job) means "write nothing".
 WN_DEV float* wn_logp_out(const WnPlan& p) {
     return reinterpret_cast<float*>(__hip_atomic_load(reinterpret_cast<const wn_u64*>(p.status + 6), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+}
+// The forced samples of an armed job (r.logp & WN_RUN_FORCED; wn_set_forced_samples, include/wn_abi.h): int32 [n_streams][num_samples], laid out like out_idx.  The
+// pointer sits behind xcc_tab in the status block, written by the host like the one above.  Read ONLY on an armed job: other status blocks may end at xcc_tab.
+WN_DEV const int32_t* wn_forced_in(const WnPlan& p) {
+    return reinterpret_cast<const int32_t*>(__hip_atomic_load(reinterpret_cast<const wn_u64*>(p.status + WN_STATUS_FORCED(p.n_wg)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 }
 
 // Spin until the granule carries `tag`.  Bounded: gives up after r->timeout_ticks of wall clock or as
@@ -391,13 +396,13 @@ WN_DEV void wn_sample(WnCtx& cx, const WnSmp& sm, double u, bool greedy, float t
 // (v_i - max v) - logf(sum of the kept exp(v_j - max v)) in fp32, sums in wn_sample's order (16 chunks, then the chunks' partials).
 //   WN_LOGP_SAMPLING: v = xsm and the maximum is the draw's fscal[0]; a sampled stream's sum is the draw's own (its partials ps[] are still there -- not
 //                     log(mass): a kept class whose mass underflowed gets a finite value), a greedy stream's is computed here.  A class the filter dropped
-//                     (the clamp at u >= 1 alone returns one) gets -inf.
+//                     (the clamp at u >= 1 returns one, and a forced sample may be one) gets -inf.
 //   WN_LOGP_MODEL:    v = lgt, the step's summed logits: one more maximum and sum, through pm / ps / fscal[2], which nobody reads any more.
 WN_DEV void wn_sample_logp(WnCtx& cx, const WnSmp& sm, bool greedy, size_t at) {
     const WnPlan& p = *cx.p;
     const WnRun& r = *cx.r;
     const int C = p.C, G = WN_SAMPLER_GROUPS, chunk = (C + G - 1) / G;
-    const bool model = r.logp == 2;
+    const bool model = (r.logp & WN_RUN_LOGP_MASK) == 2;
     const float* v = model ? sm.lgt : sm.xsm;
     const int mslot = model ? 2 : 0;
     if (model) {
@@ -491,10 +496,19 @@ WN_DEV bool wn_l0_input(WnCtx& cx, int c, long long e, int s) {
             const bool greedy = r.greedy != 0 || !(temp > 0.f);
             const double u = greedy ? 0. : r.uniforms[(size_t)s * r.num_samples + g];
             wn_sample(cx, sm, u, greedy, temp);
+            if (r.logp & WN_RUN_FORCED) {   // a forced position: the class given replaces the draw (in EVERY slice's copy: each feeds its own start_conv gather),
+                WN_PHASE {                  // ahead of the log-probability, whose maximum and sums stay the draw's.  Anything outside [0, C) is a free position
+                    if (tid == 0) {
+                        const int32_t f = wn_forced_in(p)[(size_t)s * r.num_samples + g];
+                        if ((uint32_t)f < (uint32_t)p.C) sm.iscal[0] = f;
+                    }
+                }
+                WN_SYNC();
+            }
             if (c == 0) {
                 WN_PHASE { if (tid == 0) r.out_idx[(size_t)s * r.num_samples + g] = sm.iscal[0]; }
             }
-            if (r.logp && c == 0) wn_sample_logp(cx, sm, greedy, (size_t)s * r.num_samples + g);
+            if ((r.logp & WN_RUN_LOGP_MASK) && c == 0) wn_sample_logp(cx, sm, greedy, (size_t)s * r.num_samples + g);
         }
     }
     if (e == r.n_eval) { WN_SYNC(); return true; }

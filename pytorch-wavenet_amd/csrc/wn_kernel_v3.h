@@ -1594,7 +1594,7 @@ static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, cons
 // LOGP (wn_set_logprob_output, include/wn_abi.h; the instantiations that carry the filters, and there only while r.logp is set): the log-probability of the
 // class that was returned, (v_i - max v) - logf(sum of the kept exp(v_j - max v)) in fp32.  v_i is one readlane (idx is wave-uniform after the draw).
 //   WN_LOGP_SAMPLING: v = x, and max and sum are the draw's own gm and tot -- not log(mass): a kept class whose mass underflowed gets a finite value; a class
-//                     the filter dropped (the clamp at u >= 1 alone returns one) gets -inf.  A greedy stream computes the sum here: it needs none to draw.
+//                     the filter dropped (the clamp at u >= 1 returns one, and a forced sample may be one: wn_set_forced_samples) gets -inf.  A greedy stream computes the sum here: it needs none to draw.
 //   WN_LOGP_MODEL:    v = logit, the step's summed logits (what dbg_logits dumps): a second max / expf / sum over the wave, the same for every kind of stream.
 static __device__ __forceinline__ float wn_lane_class_f(const float (&v)[4], int idx) {   // v of class idx (wave-uniform): lane idx / 4, element idx % 4
     const int k = idx & 3;
@@ -1606,8 +1606,12 @@ static __device__ __forceinline__ float wn_logp_model_1w(const float (&logit)[4]
     const float t = wn_wave_sum(((expf(logit[0] - m) + expf(logit[1] - m)) + expf(logit[2] - m)) + expf(logit[3] - m));
     return (wn_lane_class_f(logit, idx) - m) - logf(t);
 }
+// `forced` (LOGP alone; wn_set_forced_samples): a class in [0, 256) replaces the draw's answer -- wave-uniform, ahead of the log-probability, so that gm, tot and keep
+// stay the draw's own: WN_LOGP_SAMPLING of a forced class that the filter dropped is -inf; anything else (the caller passes -1) leaves the draw alone.
 template <bool FILTER, bool LOGP>
-static __device__ __forceinline__ int wn_sample_1w_lp(const WnRun& r, const float (&logit)[4], int lane, double u, bool greedy, float temperature, float& logp) {
+static __device__ __forceinline__ int wn_sample_1w_lp(const WnRun& r, const float (&logit)[4], int lane, double u, bool greedy, float temperature, float& logp,
+                                                      int forced = -1) {
+    const int lpm = LOGP ? r.logp & WN_RUN_LOGP_MASK : 0;
     float x[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1618,10 +1622,11 @@ static __device__ __forceinline__ int wn_sample_1w_lp(const WnRun& r, const floa
     const float gm = wn_wave_max(fmaxf(fmaxf(x[0], x[1]), fmaxf(x[2], x[3])));
     if (greedy) {  // first index of the maximum (torch.max semantics)
         const int mine = x[0] == gm ? 4 * lane : x[1] == gm ? 4 * lane + 1 : x[2] == gm ? 4 * lane + 2 : x[3] == gm ? 4 * lane + 3 : 0x7fffffff;
-        const int idx = wn_wave_min_i(mine);
+        int idx = wn_wave_min_i(mine);
         if constexpr (LOGP) {
-            if (r.logp) {
-                if (r.logp == 2) {
+            idx = forced >= 0 ? forced : idx;
+            if (lpm) {
+                if (lpm == 2) {
                     logp = wn_logp_model_1w(logit, idx);
                 } else {
                     const float t = wn_wave_sum(((expf(x[0] - gm) + expf(x[1] - gm)) + expf(x[2] - gm)) + expf(x[3] - gm));
@@ -1680,8 +1685,9 @@ static __device__ __forceinline__ int wn_sample_1w_lp(const WnRun& r, const floa
     for (int k = 0; k < 4; ++k) idx += __popcll(__builtin_amdgcn_ballot_w64(le[k]));
     idx = idx > 255 ? 255 : idx;
     if constexpr (LOGP) {
-        if (r.logp) {
-            if (r.logp == 2) {
+        idx = forced >= 0 ? forced : idx;
+        if (lpm) {
+            if (lpm == 2) {
                 logp = wn_logp_model_1w(logit, idx);
             } else {
                 const bool member = ((uint32_t)__builtin_amdgcn_readlane((int)keep, (idx >> 2) & 63) >> (idx & 3)) & 1u;
@@ -1774,7 +1780,8 @@ static __device__ __forceinline__ void wn_poll_class(WnCtx& cx, __amdgpu_buffer_
 // (Variant 4 takes WIDE from eight head slices up, wn_kernel_v4.h; in variant 3 it was level and is not used: profiles/r04_sampler_prefetch_and_wide_sampler.txt.)
 // FILTER: the draw is wn_sample_1w<FILTER> (by default what DIAG says; the slot re-use form, whose ONE instantiation is DIAG = true and serves unfiltered
 // product jobs, keeps the unfiltered draw there and has the filter in a kernel of its own: wn_generate_kernel_v3m_filter).  The log-probabilities live
-// where the filters live -- wn_sample_1w_lp<true, true>, guarded by r.logp --, so the FILTER = false samplers do not gain even a scalar branch.
+// where the filters live -- wn_sample_1w_lp<true, true>, guarded by r.logp --, so the FILTER = false samplers do not gain even a scalar branch; so do the
+// forced samples (wn_set_forced_samples): one load behind the poll on an armed job, and the class replaces the draw's inside wn_sample_1w_lp.
 template <class SH, bool WIDE = false, bool DIAG = false, bool FILTER = DIAG>
 static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx, float* lds_smp, float* lds_tab, int j, float* lds_lg = nullptr) {
     constexpr int R = SH::R, NP = (R / 2 + 63) / 64;  // pairs of row elements per lane
@@ -1805,6 +1812,12 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
     const unsigned lane32 = (unsigned)lane * 32;  // byte offset of the lane's four granules inside a slice's 256
     if constexpr (WIDE) wn_lds_barrier();  // (the fail flag is initialised)
     const int lane0 = (int)threadIdx.x >> 8;
+    // the forced samples of an armed job (wn_set_forced_samples): the table's address is fetched ONCE, here -- fetched per item it is a second dependent load
+    // behind the logits' poll, a quarter of a microsecond of a single stream's step -- and kept in a VGPR pair (+ lane0, as below: not in scalar registers)
+    const int32_t* forced_tab = nullptr;
+    if constexpr (FILTER) {
+        if (r.logp & WN_RUN_FORCED) forced_tab = wn_forced_in(p) + lane0;
+    }
     for (long long e = 1; e <= r.n_eval; ++e) {
         for (int s = j; s < ns; s += p.n_smp) {
             const long long item = (e - 1) * ns + s;  // stamps (diagnostics): 0 start of the wait, 1 logits complete, 2 row published
@@ -1848,6 +1861,13 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
             const float temp = r.stream_temps ? r.stream_temps[s + lane0] : r.temperature;
             const bool greedy = r.greedy != 0 || !(temp > 0.f);
             const int given = g < 0 ? r.first[(size_t)s * r.n_given + e + lane0] : 0;
+            int forced = -1;
+            if constexpr (FILTER) {   // (behind the poll as well; made a scalar: the fork and the log-probability's readlane are wave-uniform)
+                if (g >= 0 && forced_tab) {
+                    const int f = __builtin_amdgcn_readfirstlane(forced_tab[(size_t)s * r.num_samples + g]);
+                    forced = (uint32_t)f < 256u ? f : -1;   // (tested before it indexes anything: a garbage entry is a free position)
+                }
+            }
             int idx;
             if (g < 0) {
                 idx = given;
@@ -1860,10 +1880,10 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
                 }
                 if constexpr (FILTER) {   // (a job with a sampling filter or a log-probability output runs a DIAG instantiation as well)
                     float logp = 0.f;
-                    idx = wn_sample_1w_lp<true, true>(r, logit, lane, u, greedy, temp, logp);
+                    idx = wn_sample_1w_lp<true, true>(r, logit, lane, u, greedy, temp, logp, forced);
                     if (lane == 0) {
                         r.out_idx[(size_t)s * r.num_samples + g] = idx;
-                        if (r.logp) {
+                        if (r.logp & WN_RUN_LOGP_MASK) {
                             float* out = wn_logp_out(p);   // (loaded where it is used: two registers less across the poll)
                             if (out) out[(size_t)s * r.num_samples + g] = logp;
                         }

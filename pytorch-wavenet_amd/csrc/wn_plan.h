@@ -76,6 +76,7 @@ struct WnPlan {
     int32_t n_smp;            // dedicated sampler workgroups (0 in the single-stream kernels)
     int32_t start_in_lds;     // v2 single-stream: layer 0 holds start_conv^T in LDS
     uint32_t* status;         // [8] 0: abort code, 1: chain position, 2: eval, 3: stream, 4: where, 5: residency count, 6-7: the log-probability output pointer (WnRun::logp)
+                              // (behind xcc_tab, at word WN_STATUS_FORCED(n_wg): the forced samples' pointer of an armed job -- wn_forced_in, wn_kernel.h)
     uint32_t* xcc_tab;        // [n_wg] XCC id + 1 of every chain position, written by the workgroups at start
     int32_t n_blocks;         // grid size (>= n_wg; blocks mapped to -1 exit at once)
     int32_t allow_plain;      // same-XCD producers may publish with L2-resident (non write-through) stores
@@ -97,9 +98,10 @@ struct WnRun {
     int64_t timeout_ticks;  // wall_clock64 ticks
     long long* prof;        // optional [n_wg][prof_items][4] wall-clock stamps (diagnostics), or NULL
     int32_t prof_items;
-    int32_t logp;               // per-sample log-probabilities (wn_set_logprob_output, include/wn_abi.h): 0 = off, else 1 + WN_LOGP_* (1: of the distribution the
-                                // draw was made from, 2: of the step's summed logits).  The former padding word: WnRun keeps its size and every offset.  The output
-                                // pointer does not fit here: the host puts it into status[6..7] (WnPlan::status) ahead of the launch -- wn_logp_out, wn_kernel.h
+    int32_t logp;               // bits 0-1 (WN_RUN_LOGP_MASK): per-sample log-probabilities (wn_set_logprob_output, include/wn_abi.h): 0 = off, else 1 + WN_LOGP_*
+                                // (1: of the distribution the draw was made from, 2: of the step's summed logits).  Bit 2 (WN_RUN_FORCED): the job is armed with forced
+                                // samples (wn_set_forced_samples).  The former padding word: WnRun keeps its size and every offset.  The pointers do not fit here: the
+                                // host puts them into the status block (WnPlan::status) ahead of the launch -- wn_logp_out, wn_forced_in, wn_kernel.h
     const float* stream_temps;  // optional [n_streams]: per-stream temperature (<= 0: that stream is greedy); NULL = `temperature` for all
     int64_t resident_ticks;     // bound of the start-up residency barrier (wn_resident_barrier), wall_clock64 ticks
     // sampling filters (wn_set_sampling, include/wn_abi.h), normalised by the host: 0 = off.  APPENDED: WnRun is the kernels' last argument, so no offset
@@ -107,6 +109,12 @@ struct WnRun {
     int32_t top_k;              // 1 .. C-1: keep the classes x_i >= the k-th largest x (ties at the threshold all stay)
     float top_p;                // (0, 1): of those, keep class i iff the mass of the classes with x_j > x_i is < top_p * the survivors' mass
 };
+
+#define WN_RUN_LOGP_MASK 3
+#define WN_RUN_FORCED 4
+// The status block is 8 words, the n_wg words of xcc_tab and, 8-byte aligned behind them, the two words of the forced samples' pointer
+#define WN_STATUS_FORCED(n_wg) (8 + (((n_wg) + 1) & ~1))
+#define WN_STATUS_WORDS(n_wg) (WN_STATUS_FORCED(n_wg) + 2)
 
 // ---- host-side planner / packer (plain C++; also parsed, unused, in the device pass) ----
 #include <functional>

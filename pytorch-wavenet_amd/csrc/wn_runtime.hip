@@ -388,6 +388,7 @@ struct wn_handle {
     int prof_items = 0;      // stamps requested for the next job (0 = off)
     int32_t smp_top_k = 0; float smp_top_p = 0.f;   // sampling filters of every later job (wn_set_sampling; as given: wn_generate normalises the off values)
     float* logp_out = nullptr; int64_t logp_capacity = 0; int32_t logp_mode = 0;   // log-probability output of the NEXT job alone (wn_set_logprob_output; wn_generate consumes it)
+    const int32_t* forced_in = nullptr; int64_t forced_capacity = 0;               // forced samples of the NEXT job alone (wn_set_forced_samples; likewise)
     int prof_recorded = 0;   // stamps held in d_prof
     std::vector<int64_t> ring_off;
     std::vector<int32_t> dil;
@@ -417,7 +418,7 @@ static void wn_free_weights(wn_handle* h) {   // (members i > 0 of a rounds fron
 
 // The chain kernel a handle runs: its function (for the attribute and occupancy queries of wn_create), its workgroup size, its launch
 // (variants 3 and 4 exist twice: the product instantiation and the DIAG one -- wall-clock stamps, logits dump -- that a job with wn_profile_next or
-//  dbg_logits or a sampling filter or a log-probability output runs; the generic kernel tests at run time)
+//  dbg_logits or a sampling filter, a log-probability output or forced samples runs; the generic kernel tests at run time)
 struct WnChainKernel { const void* fn; int threads; };
 static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
     if (h->variant == 4) return WnChainKernel{diag ? wn_v4_table()[h->v2_index].fn_diag : wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
@@ -428,7 +429,7 @@ static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
     return WnChainKernel{(const void*)wn_generate_kernel, WN_THREADS};
 }
 static void wn_chain_launch(const wn_handle* h, hipStream_t st, const WnRun& r) {
-    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr || r.top_k != 0 || r.top_p != 0.f || r.logp != 0;   // (the sampling filters and the log-probabilities live in the DIAG samplers)
+    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr || r.top_k != 0 || r.top_p != 0.f || r.logp != 0;   // (the sampling filters, the log-probabilities and the forced fork live in the DIAG samplers: r.logp carries both flags)
     if (h->variant == 4)
         wn_v4_table()[h->v2_index].launch(diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
     else if (h->variant == 3)
@@ -713,7 +714,7 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     h->d_state_off = (int64_t*)rt_malloc((size_t)(pl.NL + 1) * 8);
     h->d_wg_map = (int32_t*)rt_malloc((size_t)pl.n_blocks * 4);
     h->d_gran = (wn_u64*)rt_malloc(h->gran_count * 8);
-    h->d_status = (uint32_t*)rt_malloc((size_t)(8 + pl.n_wg) * 4);
+    h->d_status = (uint32_t*)rt_malloc((size_t)WN_STATUS_WORDS(pl.n_wg) * 4);
     if (!h->w.d_blobs || !h->w.d_start_t || !h->w.d_start_b || !h->d_rings || !h->d_dil || !h->d_ring_off || !h->d_state_off || !h->d_wg_map ||
         !h->d_gran || !h->d_status) {
         const double q_mb = h->ring_floats * 4e-6, g_mb = h->gran_count * 8e-6, w_mb = h->blob_floats * 4e-6;
@@ -726,7 +727,7 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     rc = rc ? rc : rt_h2d(h->d_state_off, state_off.data(), (size_t)(pl.NL + 1) * 8);
     rc = rc ? rc : rt_h2d(h->d_wg_map, wg_map.data(), (size_t)pl.n_blocks * 4);
     rc = rc ? rc : rt_memset_async(h->d_rings, 0, h->ring_floats * 4, nullptr);
-    rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)(8 + pl.n_wg) * 4, nullptr);
+    rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)WN_STATUS_WORDS(pl.n_wg) * 4, nullptr);
     rc = rc ? rc : rt_sync(nullptr);
     if (rc) { wn_destroy(h); return rc; }
     pl.blobs = h->w.d_blobs; pl.start_t = h->w.d_start_t; pl.start_b = nullptr;
@@ -907,14 +908,21 @@ extern "C" int wn_reset(wn_handle* h, void* hip_stream) {
 extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     g_err[0] = 0;
     if (!h || !a) return wn_fail(WN_E_BADARG, "wn_generate: NULL argument");
-    // the log-probability output armed for THIS call (wn_set_logprob_output): consumed here, whatever becomes of the call
+    // the log-probability output (wn_set_logprob_output) and the forced samples (wn_set_forced_samples) armed for THIS call: BOTH are consumed here, ahead
+    // of either capacity test, whatever becomes of the call -- a job refused for one of them must not leave the other behind for the next job
     float* const logp_out = h->logp_out;
     const int64_t logp_capacity = h->logp_capacity;
     const int32_t logp_mode = h->logp_mode;
     h->logp_out = nullptr; h->logp_capacity = 0; h->logp_mode = 0;
+    const int32_t* const forced_in = h->forced_in;
+    const int64_t forced_capacity = h->forced_capacity;
+    h->forced_in = nullptr; h->forced_capacity = 0;
     if (logp_out && a->num_samples > 0 && (long long)h->plan.n_streams * (long long)a->num_samples > (long long)logp_capacity)
         return wn_fail(WN_E_BADARG, "wn_generate: the log-probability output holds %lld floats, the job writes %d x %lld; nothing was launched",
                        (long long)logp_capacity, h->plan.n_streams, (long long)a->num_samples);
+    if (forced_in && a->num_samples > 0 && (long long)h->plan.n_streams * (long long)a->num_samples > (long long)forced_capacity)
+        return wn_fail(WN_E_BADARG, "wn_generate: the forced samples hold %lld values, the job reads %d x %lld; nothing was launched",
+                       (long long)forced_capacity, h->plan.n_streams, (long long)a->num_samples);
     if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_generate: wn_load_weights has not been called");
     if (!h->chains.empty()) {   // rounds: member i owns streams [chain_first[i], chain_first[i + 1]); one after the other on the caller's stream
         if (a->n_given < 1 || a->num_samples < 0) return wn_fail(WN_E_BADARG, "wn_generate: n_given must be >= 1 and num_samples >= 0");
@@ -936,6 +944,11 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
                 m->logp_out = logp_out + s0 * (size_t)a->num_samples;
                 m->logp_capacity = (int64_t)(h->chain_first[i + 1] - h->chain_first[i]) * a->num_samples;
                 m->logp_mode = logp_mode;
+            }
+            if (forced_in) {
+                wn_handle* m = h->chains[i];
+                m->forced_in = forced_in + s0 * (size_t)a->num_samples;
+                m->forced_capacity = (int64_t)(h->chain_first[i + 1] - h->chain_first[i]) * a->num_samples;
             }
             if (i == 0 && h->prof_items > 0) { h->chains[0]->prof_items = h->prof_items; h->prof_items = 0; }
             rc = wn_generate(h->chains[i], &b);
@@ -972,7 +985,8 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     r.first = a->first_samples; r.n_given = a->n_given; r.num_samples = a->num_samples; r.n_eval = n_eval;
     r.t_base = h->t_base; r.temperature = a->temperature; r.greedy = greedy ? 1 : 0; r.reg = a->regularizer;
     r.uniforms = a->uniforms; r.out_idx = a->out_idx; r.dbg_logits = a->dbg_logits; r.stream_temps = a->stream_temperatures;
-    r.logp = logp_out ? 1 + logp_mode : 0;   // (the pointer travels in status[6..7], below; an armed job, a greedy one too, runs the instantiation that carries the log-probabilities: wn_chain_launch)
+    if (forced_in && a->num_samples > 0) r.logp |= WN_RUN_FORCED;   // (its pointer travels behind xcc_tab; the forced fork lives where the log-probabilities live)
+    r.logp |= logp_out ? 1 + logp_mode : 0;   // (the pointer travels in status[6..7], below; an armed job, a greedy one too, runs the instantiation that carries the log-probabilities: wn_chain_launch)
     if (!greedy) {   // (nothing is drawn in a greedy job: no filter applies to it, and unarmed it runs the kernel it always ran)
         r.top_k = h->smp_top_k < h->plan.C ? h->smp_top_k : 0;
         r.top_p = h->smp_top_p < 1.f ? h->smp_top_p : 0.f;
@@ -1028,11 +1042,17 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     }
     // hand-off words restart at tag 1 every call: zero them (and the status word) ahead of the launch
     int rc = rt_memset_async(h->d_gran, 0, h->gran_count * 8, a->hip_stream);
-    rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)(8 + h->plan.n_wg) * 4, a->hip_stream);
+    rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)WN_STATUS_WORDS(h->plan.n_wg) * 4, a->hip_stream);   // (the whole block: no pointer of an earlier armed job stays in its tail)
     if (!rc && logp_out) {   // the log-probability output pointer, behind the memset: two 32-bit fills, no host buffer to keep alive (wn_logp_out, wn_kernel.h)
         const unsigned long long bits = (unsigned long long)(uintptr_t)logp_out;
         rc = rt_hip(hipMemsetD32Async((hipDeviceptr_t)(h->d_status + 6), (int)(uint32_t)bits, 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
         rc = rc ? rc : rt_hip(hipMemsetD32Async((hipDeviceptr_t)(h->d_status + 7), (int)(uint32_t)(bits >> 32), 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
+    }
+    if (!rc && (r.logp & WN_RUN_FORCED)) {   // the forced samples' pointer, likewise (wn_forced_in, wn_kernel.h)
+        const unsigned long long bits = (unsigned long long)(uintptr_t)forced_in;
+        uint32_t* at = h->d_status + WN_STATUS_FORCED(h->plan.n_wg);
+        rc = rt_hip(hipMemsetD32Async((hipDeviceptr_t)at, (int)(uint32_t)bits, 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
+        rc = rc ? rc : rt_hip(hipMemsetD32Async((hipDeviceptr_t)(at + 1), (int)(uint32_t)(bits >> 32), 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
     }
     if (rc) { wn_gate_release(h->gate); h->gate.reset(); return rc; }
     wn_chain_launch(h, (hipStream_t)a->hip_stream, r);
@@ -1190,6 +1210,15 @@ extern "C" int wn_set_logprob_output(wn_handle* h, float* logp, int64_t capacity
         return wn_fail(WN_E_BADARG, "wn_set_logprob_output: mode must be WN_LOGP_SAMPLING (0) or WN_LOGP_MODEL (1), got %d", (int)mode);
     if (!h) return wn_fail(WN_E_BADARG, "wn_set_logprob_output: NULL handle");   // (behind the value checks: those are testable without a device)
     h->logp_out = logp; h->logp_capacity = logp ? capacity : 0; h->logp_mode = logp ? mode : 0;
+    return WN_OK;
+}
+
+// Forced samples of the NEXT job on the handle (include/wn_abi.h has the contract; wn_generate consumes the arming, the kernels read the status block)
+extern "C" int wn_set_forced_samples(wn_handle* h, const int32_t* forced, int64_t capacity) {
+    g_err[0] = 0;
+    if (capacity < 0) return wn_fail(WN_E_BADARG, "wn_set_forced_samples: capacity must be >= 0, got %lld", (long long)capacity);
+    if (!h) return wn_fail(WN_E_BADARG, "wn_set_forced_samples: NULL handle");   // (behind the value check: that one is testable without a device)
+    h->forced_in = forced; h->forced_capacity = forced ? capacity : 0;
     return WN_OK;
 }
 

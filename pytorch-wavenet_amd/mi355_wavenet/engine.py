@@ -195,6 +195,34 @@ class Engine:
                                "added): rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
         self.lib.check(self.lib.dll.wn_set_logprob_output(self._h, self.mem.ptr(logp_dev), int(capacity), self.LOGPROB_MODES[mode]))
 
+    def _need_forced(self):
+        if not self.lib.has("wn_set_forced_samples"):
+            raise RuntimeError("mi355_wavenet: %s does not export wn_set_forced_samples (a library built before forced samples were added): "
+                               "rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
+
+    def set_forced_samples(self, forced_dev, capacity):
+        """Arms the NEXT job alone to read forced samples from forced_dev, int32 (n_streams, num_samples) on the device: a value in [0, classes) is what
+        the stream emits at that position, anything else (canonically -1) leaves the draw alone (C ABI wn_set_forced_samples; the contract is in
+        include/wn_abi.h).  forced_dev None disarms.  A library without the symbol raises."""
+        self._need_forced()
+        self.lib.check(self.lib.dll.wn_set_forced_samples(self._h, self.mem.ptr(forced_dev), int(capacity)))
+
+    def _forced_array(self, forced, num_samples):
+        """generate()'s ``forced`` as int32 (n_streams, num_samples), -1 = free; ValueError for anything else"""
+        ns, C = self.n_streams, self.classes
+        if num_samples < 1:
+            raise ValueError("forced: the job generates no sample")
+        f = np.asarray(forced)
+        if f.dtype.kind not in "iu":
+            raise ValueError("forced must be an integer array, got dtype %s" % f.dtype)
+        if f.ndim == 1:
+            f = np.broadcast_to(f[None, :], (ns, f.shape[0]))
+        if f.shape != (ns, num_samples):
+            raise ValueError("forced has shape %r, the job needs %r (or (%d,))" % (np.shape(forced), (ns, num_samples), num_samples))
+        if f.min() < -1 or f.max() >= C:
+            raise ValueError("forced outside [-1, classes): -1 is a free position, 0 .. classes - 1 a forced class")
+        return np.array(f, dtype=np.int32, order="C")   # (a copy: the broadcast view is read-only)
+
     def launch(self, first_dev, n_given, num_samples, temperature, reg_dev, uni_dev, out_dev, logits_dev, timeout_ms=0,
                temps_dev=None):
         """Enqueue one job on the current stream (asynchronous).  temps_dev: optional fp32 (n_streams,) per-stream temperatures."""
@@ -285,7 +313,7 @@ class Engine:
 
     def generate(self, num_samples, first_samples=None, temperature=1.0, regularize=0.0, uniforms=None,
                  want_logits=False, reset=True, timeout_ms=0, batched_prime=True, while_running=None, top_k=None, top_p=None, shared_prompt=False,
-                 logprobs=None):
+                 logprobs=None, forced=None):
         """first_samples: (n_streams, n_given) or (n_given,) ints (broadcast to every stream) or None -> classes//2.
         uniforms: float64 (n_streams, num_samples) (np.random.random_sample draws) or None -> greedy.
         temperature: a number, or one per stream (a stream with temperature <= 0 is greedy and ignores its uniforms row).
@@ -296,11 +324,17 @@ class Engine:
         shared_prompt: the streams share their given samples (a 1-D first_samples, or identical rows -- anything else is a ValueError): the batched
         priming runs once over the one row and fills every stream's queues (``prime_shared``).
         logprobs: None, "sampling" or "model" -- the log-probability of every generated sample, written by the sampler kernels (``set_logprob_output``).
+        forced: None, or ints (n_streams, num_samples) or (num_samples,) (broadcast to every stream) -- a value in [0, classes) is what the stream emits at
+        that position (it enters the network like a drawn sample; its log-probability is reported like one), -1 leaves the draw alone
+        (``set_forced_samples``).  ``uniforms`` keeps its shape: the uniform of a forced position is not used.
         Returns indices int32 (n_streams, num_samples) [, logits float32 (n_streams, num_samples, classes)] [, logp float32 (n_streams, num_samples)]:
         a tuple as soon as there is more than the indices, the log-probabilities last."""
         ns, C = self.n_streams, self.classes
         if logprobs is not None and logprobs not in self.LOGPROB_MODES:
             raise ValueError('logprobs must be None, "sampling" or "model", got %r' % (logprobs,))
+        if forced is not None:
+            forced = self._forced_array(forced, num_samples)
+            self._need_forced()   # (before anything is reset or enqueued)
         if top_k is not None or top_p is not None:
             self.set_sampling(self._sampling[0] if top_k is None else top_k, self._sampling[1] if top_p is None else top_p)
         if first_samples is None:
@@ -343,6 +377,9 @@ class Engine:
         if logprobs is not None:
             logp_dev = self.mem.empty((ns, max(num_samples, 1)), np.float32)
             self.set_logprob_output(logp_dev, ns * max(num_samples, 1), logprobs)   # (armed right before the job that consumes it)
+        if forced is not None:
+            forced_dev = self.mem.upload(forced)   # (held until the wait below)
+            self.set_forced_samples(forced_dev, forced.size)
         self.launch(first_dev, n_given, num_samples, temperature, reg_dev, uni_dev, out_dev, logits_dev, timeout_ms, temps_dev)
         if while_running is not None:
             while_running()

@@ -435,7 +435,7 @@ class WaveNetModel(nn.Module):
 
     def generate_fast(self, num_samples, first_samples=None, temperature=1., regularize=0.,
                       progress_callback=None, progress_interval=100, *, top_k=0, top_p=0., continue_from=None, return_state=False,
-                      return_logprobs=False):
+                      return_logprobs=False, forced=None):
         """Same contract as wavenet_model.py:237-315; returns float64 ndarray (num_samples,).
         Extension (keyword only): top_k / top_p truncate every sampled draw inside the sampler kernels (include/wn_abi.h: wn_set_sampling); one
         uniform per sample is drawn from the global numpy RNG as without them, and the engine's filter is off again when the call returns or raises.
@@ -447,8 +447,13 @@ class WaveNetModel(nn.Module):
         return_logprobs="sampling" | "model" (True: "sampling"): the result gains a float32 array shaped like the audio, directly behind it -- (audio,
         logp) or (audio, logp, state) -- with the log-probability of every generated sample, written by the sampler kernels (include/wn_abi.h:
         wn_set_logprob_output): of the distribution the draw was made from (temperature and filters applied), or of the model's own logits.  The RNG's
-        consumption, the callbacks and the queues left behind are those of the call without it."""
+        consumption, the callbacks and the queues left behind are those of the call without it.
+        forced: an int array shaped like the audio (1-D, or 2-D with the prompt's rows) -- a class index in [0, classes) is what the stream emits at
+        that position, -1 leaves the position to the draw (include/wn_abi.h: wn_set_forced_samples).  A forced sample enters the network and the
+        state like a drawn one and gets its log-probability like one; its uniform is drawn and not used, so the RNG's consumption, the callbacks and the
+        timing print are those of the call without it.  Ragged prompts: the common prefix as first_samples, the rest of each prompt as a forced prefix."""
         logprobs = self._logprob_mode(return_logprobs)
+        forced = self._forced_arg(forced, num_samples)
         states = None
         if continue_from is not None:
             if first_samples is not None:
@@ -456,7 +461,7 @@ class WaveNetModel(nn.Module):
             states, first_samples = self._continue_states(continue_from)
         try:
             return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                                       states, return_state, logprobs)
+                                       states, return_state, logprobs, forced)
         finally:   # (also when a callback raised between two pieces)
             if (top_k or top_p) and self._wn_engine is not None:
                 self._wn_engine.set_sampling(0, 0.)
@@ -471,6 +476,17 @@ class WaveNetModel(nn.Module):
         if return_logprobs in ("sampling", "model"):
             return return_logprobs
         raise ValueError('return_logprobs must be False, True, "sampling" or "model", got %r' % (return_logprobs,))
+
+    def _forced_arg(self, forced, num_samples):
+        """forced of the facade -> None or an int32 array (num_samples,) / (rows, num_samples) with values in [-1, classes); ValueError otherwise"""
+        if forced is None:
+            return None
+        f = forced.detach().cpu().numpy() if torch.is_tensor(forced) else np.asarray(forced)
+        if f.dtype.kind not in "iu" or f.ndim not in (1, 2) or f.shape[-1] != num_samples or num_samples < 1:
+            raise ValueError("forced must be an integer array shaped like the audio, (%d,) or (streams, %d); got %s %r" % (num_samples, num_samples, f.dtype, f.shape))
+        if f.min() < -1 or f.max() >= self.classes:
+            raise ValueError("forced outside [-1, classes): -1 is a free position, 0 .. classes - 1 a forced class")
+        return f.astype(np.int32)
 
     def _continue_states(self, continue_from):
         """-> (the states as a list, checked against this model; the first_samples that stand for them: 1-D for a single state, else 2-D)"""
@@ -490,7 +506,7 @@ class WaveNetModel(nn.Module):
                                kernel_size=self.kernel_size, classes=self.classes)
 
     def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                       states=None, return_state=False, logprobs=None):
+                       states=None, return_state=False, logprobs=None, forced=None, timing_print=True):
         self.eval()
         if first_samples is None:
             first_samples = torch.LongTensor(1).zero_() + (self.classes // 2)
@@ -499,6 +515,10 @@ class WaveNetModel(nn.Module):
         first = first.reshape(first.shape[0], -1) if batched else first.reshape(1, -1)
         n_streams, num_given = first.shape
         total_samples = num_given + num_samples
+        if forced is not None:
+            if forced.ndim == 2 and forced.shape[0] != n_streams:
+                raise ValueError("forced has %d rows, the job has %d stream%s" % (forced.shape[0], n_streams, "" if n_streams == 1 else "s"))
+            forced = np.broadcast_to(forced.reshape(-1, num_samples), (n_streams, num_samples))
         for queue in self.dilated_queues:  # :250-251
             queue.reset()
         eng = self._engine(n_streams)
@@ -546,6 +566,7 @@ class WaveNetModel(nn.Module):
             return (b0 - a0) - max(0, min(b0, n_prime) - a0)
 
         pieces, logp_pieces = [], []
+        done = 0  # generated samples behind us: where the next piece's slice of `forced` starts
         last = None
         tic = time.time()
         ends = sorted(c for c in cuts if c > a)
@@ -569,7 +590,9 @@ class WaveNetModel(nn.Module):
                         nonlocal drawn
                         drawn = eng.upload_uniforms(np.random.random_sample((n_streams, n_next)))
                 out = eng.generate(n_new, head, temperature=temperature, regularize=regularize, uniforms=u, reset=False, while_running=overlap,
-                                   logprobs=logprobs if n_new > 0 else None)
+                                   logprobs=logprobs if n_new > 0 else None,
+                                   forced=forced[:, done:done + n_new] if (forced is not None and n_new > 0) else None)
+                done += n_new
                 if n_new > 0 and logprobs is not None:
                     out, lp = out
                     logp_pieces.append(lp)
@@ -580,7 +603,7 @@ class WaveNetModel(nn.Module):
             ev = b - 1  # the evaluation that just finished
             if ev < 0:
                 continue
-            if ev >= n_prime and ev - n_prime + 1 == 100:
+            if ev >= n_prime and ev - n_prime + 1 == 100 and timing_print:
                 toc = time.time()
                 print("one generating step does take approximately " + str((toc - tic) * 0.01) + " seconds)")
             if callback_due(ev):  # (priming: not a second time after batched priming)
@@ -636,7 +659,7 @@ class WaveNetModel(nn.Module):
     SHARED_PRIME = True
 
     def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0., continue_from=None,
-                              return_logprobs=False):
+                              return_logprobs=False, forced=None):
         """Extension: one generate_fast() per entry of ``temperatures`` -- the reference's generate_audio loop
         (wavenet_training.py:115-124) -- as parallel streams of ONE persistent-kernel job.  Returns float64
         (len(temperatures), num_samples), row k equal to ``generate_fast(num_samples, first_samples, temperatures[k])``
@@ -645,8 +668,12 @@ class WaveNetModel(nn.Module):
         continue_from: ONE ``GenerationState`` that every temperature continues from (N variations of a checkpoint) -- as first_samples=[last_index]
         with the queues loaded into every stream instead of reset; together with first_samples it is a ValueError.
         return_logprobs as in generate_fast: returns (audio, logp), logp float32 (len(temperatures), num_samples); a greedy row holds the log-softmax
-        value of its argmax."""
+        value of its argmax.
+        forced as in generate_fast: (num_samples,) shared by all rows, or (len(temperatures), num_samples); -1 is a free position."""
         logprobs = self._logprob_mode(return_logprobs)
+        forced = self._forced_arg(forced, num_samples)
+        if forced is not None and forced.ndim == 2 and forced.shape[0] != len(temperatures):
+            raise ValueError("forced has %d rows for %d temperatures" % (forced.shape[0], len(temperatures)))
         state = None
         if continue_from is not None:
             if first_samples is not None:
@@ -676,7 +703,7 @@ class WaveNetModel(nn.Module):
                 eng.state_load(state.state)   # one state, every stream
             idx = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
                                uniforms=uniforms if any(t > 0 for t in temps) else None, reset=state is None,
-                               shared_prompt=self.SHARED_PRIME and state is None and eng.lib.has("wn_prime_shared"), logprobs=logprobs)
+                               shared_prompt=self.SHARED_PRIME and state is None and eng.lib.has("wn_prime_shared"), logprobs=logprobs, forced=forced)
             if logprobs is not None:
                 idx, logp = idx
         finally:
@@ -685,6 +712,38 @@ class WaveNetModel(nn.Module):
         self._defer_queues(eng, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
         self.train()
         return self._expand_indices(idx) if logprobs is None else (self._expand_indices(idx), logp)
+
+    def score_continuation(self, indices, continue_from=None, first_samples=None, return_state=False):
+        """The model's log-likelihood of audio that CONTINUES a stream: float32 shaped like ``indices`` (class indices, 1-D or 2-D), entry g being
+        log p(indices[g] | the prompt or state, indices[:g]) in nats -- the negative of score_indices' row losses, computed by the generation kernels
+        in constant memory: a greedy job (no uniform is drawn: the numpy RNG is left alone) in which every position is forced
+        (include/wn_abi.h: wn_set_forced_samples) under return_logprobs="model".  Any length, any kernel_size the generation kernels serve.
+        continue_from: a GenerationState (a list of them, one per row, for 2-D indices), or first_samples as in generate_fast (default: classes // 2).
+        return_state=True: returns (logp, state) with the state behind the last sample -- chunked scoring: score a long clip piece by piece, each
+        piece continuing from the state the piece before returned, for the same values as the single call."""
+        idx = indices.detach().cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
+        if idx.dtype.kind not in "iu" or idx.ndim not in (1, 2) or idx.shape[-1] < 1:
+            raise ValueError("score_continuation: indices must be a non-empty integer array, 1-D or (streams, n); got %s %r" % (idx.dtype, idx.shape))
+        if idx.min() < 0 or idx.max() >= self.classes:
+            raise ValueError("score_continuation: indices outside [0, classes)")
+        states = None
+        if continue_from is not None:
+            if first_samples is not None:
+                raise ValueError("score_continuation: continue_from carries the next input (last_index); first_samples must not be given with it")
+            states, first_samples = self._continue_states(continue_from)
+            if first_samples.ndim != idx.ndim or (idx.ndim == 2 and len(states) != idx.shape[0]):
+                raise ValueError("score_continuation: one GenerationState for 1-D indices, a list of one per row for 2-D indices")
+        elif first_samples is not None and idx.ndim == 2:
+            rows = torch.as_tensor(first_samples)
+            if rows.ndim != 2 or rows.shape[0] != idx.shape[0]:
+                raise ValueError("score_continuation: 2-D indices need first_samples with the same number of rows")
+        elif first_samples is None and idx.ndim == 2:
+            first_samples = torch.full((idx.shape[0], 1), self.classes // 2, dtype=torch.int64)
+        elif first_samples is not None and torch.as_tensor(first_samples).ndim != 1:
+            raise ValueError("score_continuation: 1-D indices need 1-D first_samples")
+        out = self._generate_fast(idx.shape[-1], first_samples, 0., 0., None, 100, 0, 0., states, return_state, "model", idx.astype(np.int32),
+                                  timing_print=False)
+        return (out[1], out[2]) if return_state else out[1]
 
     # ------------------------------------------------------------------ bookkeeping
     def parameter_count(self):
