@@ -97,7 +97,7 @@ static __device__ __forceinline__ float wn_exp(float x) {
 #define WN_STAMPS 8
 // Stamps are parked in LDS (one ds_write, no vector-memory traffic on the critical path) and flushed to HBM by
 // wn_stamp_flush at the end of the step.
-// DIAG is a compile-time property of the kernel (the host launches the DIAG instantiation for a job with stamps or a logits dump, wn_chain_launch): in the
+// DIAG is a compile-time property of the kernel (the host launches the DIAG instantiation for a job with stamps or a logits dump, wn_job_slot): in the
 // product instantiation the stamps do not exist -- as run-time tests of r.prof each was an exec-mask save + branch pair on the token's path, the
 // stamp body laid out inline (profiles/r12_lean_item_loops.txt).
 template <bool DIAG>

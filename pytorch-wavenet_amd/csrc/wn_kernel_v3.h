@@ -27,7 +27,7 @@
 // as they have staged the current ones; samplers perform layer 0's start_conv.
 //
 // Throughput form (template parameter G = 2, chosen by the host from 56 streams up together with two replicas of the head
-// workgroups, wn_v3_mode in wn_runtime.hip): a pipeline item of a layer workgroup carries TWO streams, s and s+1.  Hand-offs stay per
+// workgroups, wn_v3_mode_for in wn_plan.h): a pipeline item of a layer workgroup carries TWO streams, s and s+1.  Hand-offs stay per
 // stream (the granules of consecutive streams are R / S apart), so head and sampler workgroups and the protocol are unchanged; the
 // request round trip, both barriers and every LDS / DPP / transcendental latency of an item are paid once per two streams and
 // every weight operand is used twice.  All G*R lanes poll / stage / push (lane t: element t % R of stream s + t / R); x, z and the
@@ -1588,7 +1588,7 @@ static __device__ __forceinline__ void wn_filter_1w(int top_k, float top_p, cons
 }
 
 // FILTER = false is the product's sampler, instruction for instruction what it was before the filters existed; FILTER = true (the DIAG kernels, which a
-// job with a filter runs: wn_chain_launch) reads r.top_k / r.top_p HERE -- behind the logits' poll, like the temperature -- and with both off computes
+// job with a filter runs: wn_job_slot) reads r.top_k / r.top_p HERE -- behind the logits' poll, like the temperature -- and with both off computes
 // the same pk[] as the other form.  u >= 1 clamps to class 255 whatever the filter kept (a harness-only input).
 //
 // LOGP (wn_set_logprob_output, include/wn_abi.h; the instantiations that carry the filters, and there only while r.logp is set): the log-probability of the
@@ -1872,7 +1872,7 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
             if (g < 0) {
                 idx = given;
             } else {
-                if constexpr (DIAG) {   // (a job that dumps its logits runs the DIAG instantiation: wn_chain_launch)
+                if constexpr (DIAG) {   // (a job that dumps its logits runs the DIAG instantiation: wn_job_slot)
                     if (r.dbg_logits) {
 #pragma unroll
                         for (int k = 0; k < 4; ++k) r.dbg_logits[((size_t)s * r.num_samples + g) * 256 + 4 * lane + k] = logit[k];
@@ -1922,7 +1922,7 @@ static __device__ void wn_v3_sampler(const WnPlan& p, const WnRun& r, WnCtx& cx,
 // DIAG: the instantiation with the wall-clock stamps (wn_profile_next), the sampler's logits dump, the sampling filters (wn_set_sampling) and the
 // per-sample log-probabilities (wn_set_logprob_output); the product instantiation has none of them.
 // SK > 0 (the slot re-use form) exists in the DIAG = true instantiation ALONE and is what an unfiltered job of 96 streams and more runs
-// (wn_runtime.hip: wn_v2_entry): its sampler keeps the unfiltered draw, so that its instruction stream is what it was before the filters existed.
+// (wn_runtime.hip: wn_v3_kernels_of): its sampler keeps the unfiltered draw, so that its instruction stream is what it was before the filters existed.
 template <int R, int DC, int S, int EC, int P, int G = 1, int SK = 0, bool DIAG = false>
 __global__ __launch_bounds__(WN_THREADS_V3) __attribute__((amdgpu_num_vgpr(WN_V3_COMPILER_VGPRS / 2)))
 void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
@@ -1944,7 +1944,7 @@ void wn_generate_kernel_v3m(WnPlan p, WnRun r) {
     else if (threadIdx.x < 64) wn_v3_sampler<SH, false, DIAG, DIAG && SK == 0>(p, r, cx, wn_lds3m + WnV3Lds<SH, 1>::smp, wn_lds3m + WnV3Lds<SH, 1>::pre, w - n_layer_wg - p.PA * p.HR);
 }
 
-// ... and the slot re-use form WITH the sampling filters, what a job of that form runs while a filter is set (wn_chain_launch): the kernel above with
+// ... and the slot re-use form WITH the sampling filters, what a job of that form runs while a filter is set (wn_job_slot): the kernel above with
 // DIAG = true and the filtering sampler.  (Its body is written out a second time on purpose: as a function shared by both kernels, plan and run reach the
 // roles by reference instead of as kernel arguments, and every existing kernel's instruction stream moved.)
 template <int R, int DC, int S, int EC, int P, int G, int SK>

@@ -117,9 +117,14 @@ struct WnRun {
 #define WN_STATUS_WORDS(n_wg) (WN_STATUS_FORCED(n_wg) + 2)
 
 // ---- host-side planner / packer (plain C++; also parsed, unused, in the device pass) ----
+#include <stdlib.h>
+#include <string.h>
+
 #include <functional>
 #include <string>
 #include <vector>
+
+#include "../../include/wn_abi.h"
 
 static inline int wn_pow2floor(int v) { int p = 1; while (p * 2 <= v) p *= 2; return p; }
 static inline int wn_pow2ceil(int v) { int p = 1; while (p < v) p *= 2; return p; }
@@ -459,6 +464,243 @@ static inline int wn_pad_pick(const WnShapeRow* rows, int n_rows, int R, int D, 
 
 // ---- variant 4 (wn_kernel_v4.h): streams up to which the stacked chain of n_stack workgroups beats variant 3's longer pipeline
 static inline int wn_v4_stream_limit(int n_stack) { const int n = (n_stack + 2) / 2; return n < 1 ? 1 : n; }
+
+// ---- the generation chain's planner: (wn_config, CU count, development pins, instantiated shapes) -> everything wn_create derives before its first
+// allocation.  Pure host arithmetic (tests/test_chain_plan_host.py runs it without a device; tests/test_gpu_chain_plan.py against wn_get_info).
+// One instantiated shape of the wave-specialised kernel (kind 3, wn_kernel_v3.h) or the stacked kernel (kind 4, wn_kernel_v4.h) as numbers: the rows are
+// listed in wn_chain_shapes.h, which computes these facts from WnV2Shape / WnV3Lds / WnV4Shape / WnV4Lds.
+struct WnChainShape {
+    int kind, index;          // 3 / 4; row of the kind's kernel pointer table (wn_runtime.hip, wn_stacked.hip)
+    int R, DC, S, EC;         // DC: dilation channels of a layer slice (kind 4: all of them, D); EC: end channels of a head slice
+    int Pm;                   // kind 3: slices per layer the kernel is compiled for (its input poll is unrolled over them); kind 4: LPW, layers per workgroup
+    int nwl, lanes, nwh;      // weight image of a layer (slice): nwl words for each of `lanes` lanes; of a head slice: nwh words for each of 256
+    int has_g2, has_slots;    // kind 3: the two-streams-per-item form and its skip-lane slot re-use form exist
+    int lds_pre[2];           // LDS floats in front of the per-stream area of a layer workgroup, by streams per item - 1 ([1]: has_g2)
+    int lds_stride;           // ... and per stream there
+    int lds_head, lds_smp;    // LDS floats of a head workgroup (its LDS-resident weights) and of a sampler workgroup that holds start_conv^T
+};
+// The development switches that steer the planner, read once per wn_create (wn_runtime.hip: wn_dev_env): WN_KERNEL, WN_SAMPLERS, WN_V3_MODE and
+// WN_V3_SLOTS as given (NULL: unset), WN_CHAINS=1 and WN_NO_LOCAL_STORES=1 as flags.  no_padding has no switch: wn_create sets it (and no_rounds) to plan
+// again after the device refused a padded (a rounds) handle.
+struct WnPins { const char *kernel, *samplers, *v3_mode, *v3_slots; bool no_rounds, no_local_stores, no_padding; };
+
+static inline int wn_shape_lds_floats(const WnChainShape& e, int ns, int g2) {
+    int need = e.lds_pre[g2 && e.has_g2 ? 1 : 0] + ns * e.lds_stride;
+    if (e.lds_head > need) need = e.lds_head;
+    if (e.lds_smp * 4 <= WN_LDS_MAX_BYTES && e.lds_smp > need) need = e.lds_smp;
+    return need;
+}
+// dedicated sampler workgroups of a multi-stream chain (each serves the streams s = j mod n): 4 by default, WN_SAMPLERS = 1..16 pins
+static inline int wn_sampler_count(int n_streams, const char* pin) {
+    const int n = pin && atoi(pin) >= 1 && atoi(pin) <= 16 ? atoi(pin) : 4;
+    return n_streams < n ? n_streams : n;
+}
+static inline bool wn_pin_is(const char* pin, const char* v) { return pin && !strcmp(pin, v); }
+struct WnChainPick { int row, P, PA; };
+// the stacked kernel serves a configuration of an instantiated shape exactly, few streams, no pinned split.  WN_KERNEL = "v3" / "generic" pin another
+// kernel, "v4" lifts the stream limit
+static inline bool wn_v4_pick(const wn_config& c, int n_cu, const WnPins& pins, const WnChainShape* sh, int n_sh, WnChainPick* out) {
+    if (wn_pin_is(pins.kernel, "generic") || wn_pin_is(pins.kernel, "v3")) return false;
+    if (c.kernel_size != 2 || c.classes != 256 || c.layer_split > 0 || c.head_split > 0 || c.n_streams < 1 || c.n_streams > 16) return false;
+    for (int i = 0; i < n_sh; ++i) {
+        const WnChainShape& e = sh[i];
+        if (e.kind != 4 || e.R != c.residual_channels || e.DC != c.dilation_channels || e.S != c.skip_channels || c.end_channels % e.EC) continue;
+        const int PA = c.end_channels / e.EC, n_stack = wn_cdiv(c.layers * c.blocks, e.Pm);
+        if (PA > 16) continue;
+        // The stacked chain is a short pipeline (n_stack + 2 stages, each busy ~3 us per item): it saturates at about half a token per stage,
+        // beyond that the one-layer-per-workgroup pipeline of variant 3 wins (measured, profiles/r04_v4_vs_v3_streams.txt: cfg2 -- 10 stack
+        // workgroups -- up to 6 streams, cfg1 -- 2 -- up to 2, the train_script shape -- 15 -- up to 8).
+        if (!wn_pin_is(pins.kernel, "v4") && c.n_streams > wn_v4_stream_limit(n_stack)) continue;
+        if (n_stack + PA + wn_sampler_count(c.n_streams, pins.samplers) > n_cu) continue;
+        if (wn_shape_lds_floats(e, c.n_streams, 0) * 4 > WN_LDS_MAX_BYTES) continue;
+        *out = WnChainPick{i, 1, PA};
+        return true;
+    }
+    return false;
+}
+// the wave-specialised kernel serves a configuration with ONE chain: an instantiated shape in the split it is compiled for, one CU per workgroup, the
+// parked tap-0 sums of all streams fit the LDS next to the activations.  WN_KERNEL = "generic" pins the LDS-resident kernel
+static inline bool wn_v3_pick(const wn_config& c, int n_cu, const WnPins& pins, const WnChainShape* sh, int n_sh, WnChainPick* out) {
+    if (wn_pin_is(pins.kernel, "generic") || c.kernel_size != 2 || c.classes != 256) return false;
+    const int NL = c.layers * c.blocks, n_smp = wn_sampler_count(c.n_streams, pins.samplers);
+    for (int i = 0; i < n_sh; ++i) {
+        const WnChainShape& e = sh[i];
+        if (e.kind != 3 || e.R != c.residual_channels || e.S != c.skip_channels || c.dilation_channels % e.DC || c.end_channels % e.EC) continue;
+        const int P = c.dilation_channels / e.DC, PA = c.end_channels / e.EC;
+        if (P != e.Pm || PA > 16) continue;
+        if ((c.layer_split > 0 && c.layer_split != P) || (c.head_split > 0 && c.head_split != PA)) continue;
+        if (NL * P + PA + n_smp > n_cu) continue;
+        if (wn_shape_lds_floats(e, c.n_streams, wn_v3_mode_for(c.n_streams, pins.v3_mode, NL) & 1) * 4 > WN_LDS_MAX_BYTES) return false;
+        *out = WnChainPick{i, P, PA};
+        return true;
+    }
+    return false;
+}
+
+// Zero padding of the channel counts.  Extra residual channels stay 0 for ever (zero rows in start_conv and the residual convs), extra
+// dilation channels give tanh(0) * sigmoid(0) = 0, extra skip / end channels give relu(0) = 0 against zero weights: the padded network
+// computes the same logits, and every product only gains exact zeros.  So a kernel_size-2, 256-class model whose channel shape is not
+// in the table of the wave-specialised kernel (e.g. 48 / 48 / 300 / 200) runs as the cheapest instantiated shape that holds it instead
+// of on the generic LDS-resident kernel (last measured 6-13x slower).  Not applied when the caller pins layer_split / head_split.
+static inline bool wn_pad_config(const wn_config& c, int n_cu, const WnPins& pins, const WnChainShape* sh, int n_sh, wn_config* padded) {
+    if (c.kernel_size != 2 || c.classes != 256 || c.layer_split > 0 || c.head_split > 0 || (c.reserved[0] & WN_CFG_NO_PADDING)) return false;
+    wn_config probe = c;
+    if (probe.n_streams > WN_V3_ROUND_STREAMS) probe.n_streams = WN_V3_ROUND_STREAMS;
+    WnChainPick pk;
+    if (wn_v4_pick(probe, n_cu, pins, sh, n_sh, &pk) || wn_v3_pick(probe, n_cu, pins, sh, n_sh, &pk)) return false;   // served as it is
+    std::vector<WnShapeRow> rows;
+    for (int i = 0; i < n_sh; ++i)
+        if (sh[i].kind == 3) rows.push_back(WnShapeRow{sh[i].R, sh[i].DC, sh[i].S, sh[i].EC, sh[i].Pm});
+    int dims[4];
+    const int pick = wn_pad_pick(rows.data(), (int)rows.size(), c.residual_channels, c.dilation_channels, c.skip_channels, c.end_channels, c.layers * c.blocks,
+                                 [&](int R2, int D2, int S2, int E2) {
+                                     wn_config p2 = probe;
+                                     p2.residual_channels = R2; p2.dilation_channels = D2; p2.skip_channels = S2; p2.end_channels = E2;
+                                     return wn_v3_pick(p2, n_cu, pins, sh, n_sh, &pk);
+                                 }, dims);
+    if (pick < 0) return false;
+    *padded = c;
+    padded->residual_channels = dims[0]; padded->dilation_channels = dims[1]; padded->skip_channels = dims[2]; padded->end_channels = dims[3];
+    return true;
+}
+
+// what wn_create refuses before it looks at the device: 0, or the error code (include/wn_abi.h) and the reason
+static inline int wn_config_refusal(const wn_config& c, std::string& why) {
+    if (c.layers < 1 || c.blocks < 1 || c.dilation_channels < 1 || c.residual_channels < 1 || c.skip_channels < 1 || c.end_channels < 1 || c.classes < 2 || c.n_streams < 1)
+        return why = "non-positive dimension in wn_config", WN_E_BADARG;
+    if (c.kernel_size < 1) return why = "kernel_size must be >= 1", WN_E_BADARG;
+    if (c.layers > 24) return why = "layers > 24 (dilation 2^layers overflows the queue)", WN_E_UNSUPPORTED;
+    if (c.layer_split < 0 || c.head_split < 0 || (c.reserved[0] & ~WN_CFG_NO_PADDING) || c.reserved[1] || c.reserved[2])
+        return why = "negative split / non-zero reserved field", WN_E_BADARG;
+    return WN_OK;
+}
+
+struct WnChainPlan {
+    wn_config cfg;               // the configuration that was planned: the caller's, or (`padded`) its zero-padded form
+    bool padded;
+    WnPlan pl;                   // model, geometry, LDS layout, grid; the device pointers stay NULL
+    int variant, row;            // 1 = generic LDS-resident kernel, 3 = wave-specialised, 4 = stacked; row of the shapes (-1: generic)
+    int v3_mode, v3_slots;       // variant 3: wn_v3_mode_for after its corrections (no such form / no CUs for a second head set); wn_v3_slots_for
+    int lds_bytes, gate_need;    // dynamic LDS of the launch; workgroups that stay resident on the fullest XCD
+    std::vector<int32_t> dil, wg_map;
+    std::vector<int64_t> ring_off, state_off;   // state_off: [NL + 1] canonical rows below layer l's block of a saved stream state (wn_state.inl)
+    size_t ring_floats, gx_n, gs_n, gl_n, g0_n, gran_count, blob_floats;
+    std::vector<WnChainPlan> rounds;   // a rounds front (more streams than one chain holds): its members' plans; the rest is then member 0's
+};
+
+// ONE chain for exactly this configuration.  Returns "" or the reason why no kernel serves it.
+static inline std::string wn_chain_plan_one(const wn_config& c, int n_cu, const WnPins& pins, const WnChainShape* sh, int n_sh, WnChainPlan& cp) {
+    cp = WnChainPlan();
+    cp.cfg = c; cp.variant = 1; cp.row = -1;
+    WnPlan& pl = cp.pl;
+    pl.layers = c.layers; pl.blocks = c.blocks; pl.NL = c.layers * c.blocks;
+    pl.R = c.residual_channels; pl.D = c.dilation_channels; pl.S = c.skip_channels; pl.E = c.end_channels;
+    pl.C = c.classes; pl.k = c.kernel_size; pl.has_bias = c.bias ? 1 : 0; pl.n_streams = c.n_streams;
+    WnChainPick pk;
+    size_t layer_img, head_img;   // floats of one layer-role workgroup's weight image and of one head slice's
+    if (wn_v4_pick(c, n_cu, pins, sh, n_sh, &pk) || wn_v3_pick(c, n_cu, pins, sh, n_sh, &pk)) {
+        const WnChainShape& e = sh[pk.row];
+        cp.variant = e.kind; cp.row = pk.row;
+        wn_plan_geometry(pl, pk.P, pk.PA);
+        pl.LPW = e.kind == 4 ? e.Pm : 1;
+        pl.n_lw = e.kind == 4 ? wn_cdiv(pl.NL, pl.LPW) : pl.NL * pk.P;
+        pl.n_smp = wn_sampler_count(c.n_streams, pins.samplers);   // sampling runs on dedicated workgroups (they also feed layer 0)
+        pl.n_wg = pl.n_lw + pk.PA + pl.n_smp;
+        pl.start_in_lds = e.lds_smp * 4 <= WN_LDS_MAX_BYTES ? 1 : 0;   // the samplers' copy of start_conv^T
+        if (e.kind == 3) {
+            cp.v3_mode = wn_v3_mode_for(pl.n_streams, pins.v3_mode, pl.NL);
+            if (!e.has_g2) cp.v3_mode &= ~1;   // (shapes whose filter/gate slices cannot be halved: one stream per item only)
+            if ((cp.v3_mode & 2) && pl.n_wg + pk.PA <= n_cu) { pl.HR = 2; pl.n_wg += pk.PA; }   // a second set of head workgroups
+            else cp.v3_mode &= 1;
+            cp.v3_slots = wn_v3_slots_for(pl.n_streams, cp.v3_mode, e.has_slots != 0, pins.v3_slots, pl.NL);
+        }
+        cp.lds_bytes = wn_shape_lds_floats(e, pl.n_streams, cp.v3_mode & 1) * 4;
+        // 1-4 streams (8: measured level, profiles/archive/r03_few_stream_lds_queues.txt): the layers' dilation queues live in LDS where they fit (wn_v3_layer)
+        if (e.kind == 3 && pl.n_streams <= 4 && !(cp.v3_mode & 1)) cp.lds_bytes = WN_LDS_MAX_BYTES;
+        pl.lds_floats = cp.lds_bytes / 4;
+        layer_img = (size_t)pl.LPW * e.nwl * e.lanes; head_img = (size_t)e.nwh * 256;
+    } else {
+        const std::string why = wn_plan_choose(pl, n_cu, c.layer_split, c.head_split);
+        if (!why.empty()) return why;
+        cp.lds_bytes = (pl.lds_floats + 8) * 4;  // + the fail-flag word (wn_any_failed)
+        pl.LPW = 1; pl.n_lw = pl.NL * pl.P;
+        layer_img = (size_t)pl.blob_layer_floats; head_img = (size_t)pl.blob_head_floats;
+    }
+    pl.head_blob_off = (int64_t)((size_t)pl.n_lw * layer_img);
+    cp.blob_floats = (size_t)pl.head_blob_off + (size_t)pl.PA * head_img;
+    cp.dil.resize(pl.NL); cp.ring_off.resize(pl.NL); cp.state_off.assign(pl.NL + 1, 0);
+    int64_t off = 0;
+    for (int l = 0; l < pl.NL; ++l) {
+        const int d = 1 << (l % pl.layers);  // wavenet_model.py:72,108-110
+        const int64_t ML = (int64_t)(pl.k - 1) * d + 1;  // wavenet_model.py:78
+        cp.dil[l] = d;
+        cp.ring_off[l] = off;
+        off += (int64_t)pl.P * pl.n_streams * ML * pl.R;
+        cp.state_off[l + 1] = cp.state_off[l] + ML;
+    }
+    cp.ring_floats = (size_t)off;
+    pl.n_blocks = pl.n_wg;
+    if (cp.variant >= 3 && n_cu % 8 == 0 && wn_make_wg_map_layers(cp.variant == 4 ? pl.n_lw : pl.NL, pl.P, pl.PA * pl.HR, pl.n_smp, 8, n_cu / 8, cp.wg_map, &pl.n_blocks))
+        pl.allow_plain = pins.no_local_stores ? 0 : 1;
+    else
+        wn_make_wg_map(pl.n_wg, 8, cp.wg_map);
+    // what a job keeps RESIDENT per XCD (block b lands on XCD b % 8; padding blocks exit at once and hold nothing)
+    int per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+    const int nx = n_cu % 8 == 0 ? 8 : 1;
+    for (int b = 0; b < pl.n_blocks; ++b)
+        if (cp.wg_map[b] >= 0 && ++per_xcd[b % nx] > cp.gate_need) cp.gate_need = per_xcd[b % nx];
+    cp.gx_n = (size_t)pl.n_lw * pl.n_streams * pl.R; cp.gs_n = (size_t)pl.n_lw * pl.n_streams * pl.S; cp.gl_n = (size_t)pl.PA * pl.n_streams * pl.C;
+    cp.g0_n = cp.variant >= 3 ? (size_t)pl.n_streams * pl.R : 0;
+    cp.gran_count = cp.gx_n + cp.gs_n + cp.gl_n + (size_t)pl.n_streams + cp.g0_n;
+    return std::string();
+}
+
+// The plan of a handle: the zero-padded form of the model where that gets it onto a register-resident kernel, rounds of up to WN_V3_ROUND_STREAMS
+// streams where one chain of the wave-specialised kernel cannot hold the job (its LDS parks a tap-0 sum per stream: cfg3 ~150 streams), one chain otherwise
+static inline std::string wn_chain_plan(const wn_config& c, int n_cu, const WnPins& pins, const WnChainShape* sh, int n_sh, WnChainPlan& cp) {
+    wn_config eff;
+    if (!pins.no_padding && wn_pad_config(c, n_cu, pins, sh, n_sh, &eff)) {
+        WnPins unpadded = pins;
+        unpadded.no_padding = true;
+        if (wn_chain_plan(eff, n_cu, unpadded, sh, n_sh, cp).empty() && cp.variant >= 3) { cp.padded = true; return std::string(); }
+    }   // (not the kernel the padding was for: plan the caller's shape instead)
+    WnChainPick pk;
+    wn_config probe = c;
+    probe.n_streams = WN_V3_ROUND_STREAMS;
+    if (!pins.no_rounds && c.n_streams > WN_V3_ROUND_STREAMS && !wn_v3_pick(c, n_cu, pins, sh, n_sh, &pk) && wn_v3_pick(probe, n_cu, pins, sh, n_sh, &pk)) {
+        std::vector<WnChainPlan> members;
+        for (int n : wn_v3_round_sizes(c.n_streams, WN_V3_ROUND_STREAMS)) {
+            wn_config part = c;
+            part.n_streams = n;
+            members.emplace_back();
+            if (!wn_chain_plan_one(part, n_cu, pins, sh, n_sh, members.back()).empty() || members.back().variant != 3) { members.clear(); break; }
+        }
+        if (!members.empty()) {
+            cp = members[0];
+            cp.cfg = c; cp.pl.n_streams = c.n_streams;
+            cp.rounds.swap(members);
+            return std::string();
+        }
+    }
+    return wn_chain_plan_one(c, n_cu, pins, sh, n_sh, cp);
+}
+
+// ---- which kernel a job runs.  A handle resolves three slots at creation; a job takes the slot of what it needs:
+//        needs                                           slot         forms 0 / 1 of variant 3, variant 4     slot re-use form          generic kernel
+//        nothing                                         0 product    the product instantiation               the form's one kernel     the kernel
+//        stamps (wn_profile_next) or a logits dump       1 diag       the DIAG instantiation                  the form's one kernel     the kernel
+//        a sampling filter, log-probabilities, forced    2 extras     the DIAG instantiation                  the filter kernel         the kernel
+// (extras outrank stamps: the DIAG instantiations and the filter kernel carry both.)
+static inline int wn_kernel_slot(bool stamps_or_dump, bool extras) { return extras ? 2 : (stamps_or_dump ? 1 : 0); }
+static inline int wn_job_slot(const WnRun& r) {   // (r.logp carries the log-probability mode and the forced flag)
+    return wn_kernel_slot(r.prof != nullptr || r.dbg_logits != nullptr, r.top_k != 0 || r.top_p != 0.f || r.logp != 0);
+}
+// column of the kernel tables a slot resolves to: 0 = the product instantiation, 1 = the DIAG one, 2 = the slot form's filter kernel
+static inline int wn_slot_column(int variant, bool slot_form, int slot) {
+    if (variant < 3) return 0;
+    if (slot_form) return slot == 2 ? 2 : 0;
+    return slot ? 1 : 0;
+}
 
 // ---- time geometry of WaveNetModel.forward() (wn_forward / wn_train_*; comment: wn_runtime.hip above wn_forward_geometry)
 struct WnFwdGeom { std::vector<long long> a, rows, zlo; };

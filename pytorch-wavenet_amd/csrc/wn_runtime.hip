@@ -26,7 +26,6 @@ static thread_local char g_err[512] = "";
 // planner would: they exist for A/B runs and for the tests that pin a form, and are IGNORED unless WN_TESTING=1 is set as well -- a
 // stray variable in a production environment must not silently change what runs (wn_get_info reports the form that does).
 static thread_local int g_dev_env_used = 0;
-static thread_local int g_create_depth = 0;  // wn_create is building the member handles of a rounds front
 static const char* wn_dev_env(const char* name) {
     const char* t = getenv("WN_TESTING");
     if (!t || t[0] != '1') return nullptr;
@@ -105,21 +104,17 @@ __global__ __launch_bounds__(WN_THREADS) void wn_generate_kernel(WnPlan p, WnRun
 
 
 // ------------------------------------------------------------------------------------------------ register-resident shapes
-// Shapes the wave-specialised kernel (variant 3, wn_kernel_v3.h) is instantiated for: (R, D/P, S, E/PA, P).  Anything else runs on the
-// generic LDS-resident kernel above.  (Rounds 1-2 also had 256-thread kernels on these shapes -- "variant 2", one chain or several
-// sharing the CUs two by two; round 3 moved every shape to variant 3 and removed them.)
-struct WnV2Entry {
-    int R, DC, S, EC, nwl, nwh;
-    int Pm;  // layer split the kernel is compiled for (its input poll is unrolled over it)
+// Kernel pointers of the shapes the wave-specialised kernel (variant 3, wn_kernel_v3.h) is instantiated for: one row per shape of WN_V3_SHAPES
+// (wn_chain_shapes.h, where the planner's facts of the same rows are computed).  Anything else runs on the generic LDS-resident kernel above.
+// (Rounds 1-2 also had 256-thread kernels on these shapes -- "variant 2", one chain or several sharing the CUs two by two; round 3 moved every
+// shape to variant 3 and removed them.)
+struct WnV3Kernels {
     void (*pack)(const WnPlan& pl, const WnHostWeights& w, std::vector<float>& out);
-    // [form]: 0 = one stream per pipeline item of a layer workgroup, 1 = two (wn_v3_mode), 2 = two + skip-lane slot re-use (wn_v3_slots_for); NULL where
+    // [form]: 0 = one stream per pipeline item of a layer workgroup, 1 = two (wn_v3_mode_for), 2 = two + skip-lane slot re-use (wn_v3_slots_for); NULL where
     // the shape has no such form
-    const void* fn_v3[3];
-    const void* fn_v3_diag[3];   // the same forms with the stamps and the logits dump compiled in (DIAG: a job with wn_profile_next or dbg_logits)
-    const void* fn_v3_filter;    // form 2 with the sampling filters and the log-probabilities (the forms 0 and 1 have them in fn_v3_diag); NULL where the shape has no form 2
-    int (*lds_floats_v3)(int ns, int g2);
-    int lds_pre_v3;  // float offset of the per-stream area = what head / sampler workgroups use in front of their own tables
-    void (*launch_v3)(int form, bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r);
+    const void* fn[3];
+    const void* fn_diag[3];   // the same forms with the stamps and the logits dump compiled in (DIAG)
+    const void* fn_filter;    // form 2 with the sampling filters and the log-probabilities (the forms 0 and 1 have them in fn_diag); NULL where the shape has no form 2
 };
 
 template <class SH>
@@ -169,152 +164,35 @@ static void wn_pack_v2(const WnPlan& pl, const WnHostWeights& w, std::vector<flo
     }
 }
 
-template <int R, int DC, int S, int EC, int PM, int SK = 0>
-static WnV2Entry wn_v2_entry() {
+template <int R, int DC, int S, int EC, int PM, int SK>
+static WnV3Kernels wn_v3_kernels_of() {
     using SH = WnV2Shape<R, DC, S, EC>;
-    WnV2Entry e;
-    e.R = R; e.DC = DC; e.S = S; e.EC = EC; e.nwl = SH::NWL; e.nwh = SH::NWH; e.Pm = PM;
+    WnV3Kernels e = {};
     e.pack = wn_pack_v2<SH>;
-    e.fn_v3[0] = e.fn_v3[1] = e.fn_v3[2] = nullptr; e.fn_v3_diag[0] = e.fn_v3_diag[1] = e.fn_v3_diag[2] = nullptr; e.fn_v3_filter = nullptr; e.lds_floats_v3 = nullptr; e.launch_v3 = nullptr; e.lds_pre_v3 = 0;
-    static_assert(wn_v3_fits<SH, PM>(), "every table entry runs the wave-specialised kernel");
-    {
-        e.fn_v3[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, false>;
-        e.fn_v3_diag[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, true>;
-        if constexpr (wn_v3_g2_fits<SH>()) {
-            e.fn_v3[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, false>;
-            e.fn_v3_diag[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, true>;
-        }
-        // The slot re-use form exists in ONE instantiation, the one that tests r.prof at run time: its product instantiation measured 7 % SLOWER than the
-        // parent's kernel on the jobs the form is for (cfg3 x 128: 1.45 M against 1.57 M; x 96: 1.37 against 1.43), this one 3 % faster (1.61 / 1.47 M) --
-        // the form is throughput bound, what the stamps cost is not on its path, and the compiler's schedule of the kernel without them is the worse one
-        // (profiles/r12_lean_item_loops.txt).
-        // Because unfiltered product jobs run it, its sampler does NOT carry the sampling filters (wn_kernel_v3.h: the kernel is, instruction for instruction,
-        // what it was before they existed): a job of this form with a filter set runs wn_generate_kernel_v3m_filter, compiled in the other unit (wn_stacked_table.h).
-        if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
-            e.fn_v3[2] = e.fn_v3_diag[2] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>;
-            static_assert(R == 128 && DC == 32 && S == 512 && EC == 32 && PM == 4 && SK == 4, "the slot form's filter kernel is instantiated for this shape (wn_stacked.hip)");
-            e.fn_v3_filter = wn_v3_cfg3_slots_filter_fn();
-        }
-        e.lds_pre_v3 = WnV3Lds<SH, 1>::pre;
-        e.lds_floats_v3 = [](int ns, int g2) {
-            int lay = WnV3Lds<SH, 1>::floats(ns);
-            if constexpr (wn_v3_g2_fits<SH>()) { if (g2) lay = WnV3Lds<SH, 2>::floats(ns); }
-            const int head = WnV3Lds<SH, 1>::pre + (SH::K3 > 100 ? SH::K3 : EC) * 256;  // + the head lanes' LDS-resident weights (wn_v3_head)
-            const int smp = WnV3Lds<SH, 1>::pre + 256 * R;    // + start_conv^T in the sampler workgroups (wn_v3_sampler), when it fits
-            int need = lay > head ? lay : head;
-            if (smp * 4 <= WN_LDS_MAX_BYTES && smp > need) need = smp;
-            return need;
-        };
-        e.launch_v3 = [](int form, bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
-            auto go = [&](auto diag_c) {
-                constexpr bool DG = decltype(diag_c)::value;
-                if constexpr (wn_v3_g2_fits<SH>() && SK > 0) {
-                    if (form == 2 && (r.top_k != 0 || r.top_p != 0.f || r.logp != 0)) { wn_v3_cfg3_slots_filter_launch(grid, lds, st, p, r); return; }
-                    if (form == 2) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
-                }
-                if constexpr (wn_v3_g2_fits<SH>()) {
-                    if (form >= 1) { hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, DG>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r); return; }
-                }
-                hipLaunchKernelGGL((wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, DG>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r);
-            };
-            if (diag) go(WnBool<true>{}); else go(WnBool<false>{});
-        };
+    e.fn[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, false>;
+    e.fn_diag[0] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 1, 0, true>;
+    if constexpr (wn_v3_g2_fits<SH>()) {
+        e.fn[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, false>;
+        e.fn_diag[1] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, 0, true>;
+    }
+    // The slot re-use form exists in ONE instantiation, the one that tests r.prof at run time: its product instantiation measured 7 % SLOWER than the
+    // parent's kernel on the jobs the form is for (cfg3 x 128: 1.45 M against 1.57 M; x 96: 1.37 against 1.43), this one 3 % faster (1.61 / 1.47 M) --
+    // the form is throughput bound, what the stamps cost is not on its path, and the compiler's schedule of the kernel without them is the worse one
+    // (profiles/r12_lean_item_loops.txt).
+    // Because unfiltered product jobs run it, its sampler does NOT carry the sampling filters (wn_kernel_v3.h: the kernel is, instruction for instruction,
+    // what it was before they existed): a job of this form with a filter set runs wn_generate_kernel_v3m_filter, compiled in the other unit (wn_stacked_table.h).
+    if constexpr (SK > 0) {
+        e.fn[2] = e.fn_diag[2] = (const void*)wn_generate_kernel_v3m<R, DC, S, EC, PM, 2, SK, true>;
+        static_assert(R == 128 && DC == 32 && S == 512 && EC == 32 && PM == 4 && SK == 4, "the slot form's filter kernel is instantiated for this shape (wn_stacked.hip)");
+        e.fn_filter = wn_v3_cfg3_slots_filter_fn();
     }
     return e;
 }
-
-static const std::vector<WnV2Entry>& wn_v2_table() {
-    static const std::vector<WnV2Entry> t = {
-        wn_v2_entry<128, 32, 512, 32, 4, 4>(),   // cfg3: P=4, PA=8 (a 64-row head slice is the slowest pipeline stage); + the slot re-use form (96 streams and more)
-        wn_v2_entry<64, 64, 256, 64, 1>(),    // cfg2: P=1, PA=4
-        wn_v2_entry<32, 32, 256, 64, 1>(),    // cfg1: P=1, PA=4
-        wn_v2_entry<32, 16, 1024, 32, 2>(),   // train_script.py chaconne shape, split two ways (64 skip weights per lane), PA=16 (end_conv_1 slice in LDS)
-        wn_v2_entry<64, 32, 256, 64, 2>(),    // cfg2 split in two (layer_split=2)
-        wn_v2_entry<16, 16, 256, 32, 1>(),    // small test shape
-        wn_v2_entry<16, 16, 256, 32, 2>(),    // ... and its two-slice form
-    };
+static const std::vector<WnV3Kernels>& wn_v3_kernels() {
+#define WN_X(R, DC, S, EC, PM, SK) wn_v3_kernels_of<R, DC, S, EC, PM, SK>(),
+    static const std::vector<WnV3Kernels> t = {WN_V3_SHAPES(WN_X)};
+#undef WN_X
     return t;
-}
-
-// picks an instantiated shape for this model; returns its index or -1
-static int wn_v2_choose(const WnPlan& pl, int n_cu, int n_smp, int forced_P, int forced_PA, int* outP, int* outPA) {
-    if (pl.k != 2 || pl.C != 256) return -1;
-    const std::vector<WnV2Entry>& t = wn_v2_table();
-    for (size_t i = 0; i < t.size(); ++i) {
-        const WnV2Entry& e = t[i];
-        if (e.R != pl.R || e.S != pl.S || pl.D % e.DC || pl.E % e.EC) continue;
-        const int P = pl.D / e.DC, PA = pl.E / e.EC;
-        if (P != e.Pm || PA > 16) continue;  // the kernel is compiled per layer split
-        if ((forced_P > 0 && forced_P != P) || (forced_PA > 0 && forced_PA != PA)) continue;
-        if (pl.NL * P + PA + n_smp > n_cu) continue;
-        *outP = P; *outPA = PA;
-        return (int)i;
-    }
-    return -1;
-}
-
-// dedicated sampler workgroups of a multi-stream chain (each serves the streams s = j mod n): 4 by default
-static int wn_sampler_count(int n_streams) {
-    int n = 4;
-    const char* e = wn_dev_env("WN_SAMPLERS");
-    if (e && atoi(e) >= 1 && atoi(e) <= 16) n = atoi(e);
-    return n_streams < n ? n_streams : n;
-}
-
-// Throughput form of the wave-specialised kernel (bit 0: two streams per pipeline item of a layer workgroup; bit 1: two replicas
-// of the head workgroups, each serving every other stream).  One stream per item is the latency-optimal form; with more streams
-// than the chain can turn around in one trip the stages' fixed costs per item -- the request round trip, two workgroup barriers,
-// the LDS and DPP latencies of the dot products -- bound the throughput, and two streams per item share them (every weight
-// operand is used twice) at the price of a longer trip through each stage.  WN_V3_MODE = 0..3 pins a form (A/B runs, tests).
-// (the rule itself is host-only arithmetic in wn_plan.h: wn_v3_mode_for, tests/test_plan_host.py)
-static int wn_v3_mode(int n_streams, int n_layers) { return wn_v3_mode_for(n_streams, wn_dev_env("WN_V3_MODE"), n_layers); }
-
-// true iff the wave-specialised kernel (variant 3) serves this configuration with ONE chain: an instantiated shape, at least
-// two streams, the parked tap-0 sums of all streams fit the LDS next to the activations, one CU per workgroup
-static bool wn_v3_applicable(const wn_config* cfg, int n_cu, int* out_vi, int* outP, int* outPA) {
-    const char* force = wn_dev_env("WN_KERNEL");  // "generic" pins the LDS-resident kernel (A/B runs, tests)
-    if (force && !strcmp(force, "generic")) return false;
-    if (cfg->n_streams < WN_V3_MIN_STREAMS) return false;
-    WnPlan pl = {};
-    pl.layers = cfg->layers; pl.blocks = cfg->blocks; pl.NL = cfg->layers * cfg->blocks;
-    pl.R = cfg->residual_channels; pl.D = cfg->dilation_channels; pl.S = cfg->skip_channels; pl.E = cfg->end_channels;
-    pl.C = cfg->classes; pl.k = cfg->kernel_size; pl.n_streams = cfg->n_streams;
-    const int n_smp = wn_sampler_count(cfg->n_streams);
-    int P = 0, PA = 0;
-    const int vi = wn_v2_choose(pl, n_cu, n_smp, cfg->layer_split, cfg->head_split, &P, &PA);
-    if (vi < 0) return false;
-    if (wn_v2_table()[vi].lds_floats_v3(cfg->n_streams, (wn_v3_mode(cfg->n_streams, cfg->layers * cfg->blocks) & 1) && wn_v2_table()[vi].fn_v3[1]) * 4 > WN_LDS_MAX_BYTES) return false;
-    if (out_vi) *out_vi = vi;
-    if (outP) *outP = P;
-    if (outPA) *outPA = PA;
-    return true;
-}
-
-// true iff the stacked kernel serves this configuration: an instantiated shape exactly, few streams, no pinned split
-static bool wn_v4_applicable(const wn_config* cfg, int n_cu, int* out_vi, int* outPA) {
-    const char* force = wn_dev_env("WN_KERNEL");  // "v3" / "generic" pin another kernel (A/B runs, tests); "v4" lifts the stream limit
-    if (force && (!strcmp(force, "generic") || !strcmp(force, "v3"))) return false;
-    const bool forced = force && !strcmp(force, "v4");
-    if (cfg->kernel_size != 2 || cfg->classes != 256 || cfg->layer_split > 0 || cfg->head_split > 0) return false;
-    if (cfg->n_streams < 1 || cfg->n_streams > 16) return false;
-    const std::vector<WnV4Entry>& t = wn_v4_table();
-    for (size_t i = 0; i < t.size(); ++i) {
-        const WnV4Entry& e = t[i];
-        if (e.R != cfg->residual_channels || e.D != cfg->dilation_channels || e.S != cfg->skip_channels || cfg->end_channels % e.EC) continue;
-        const int PA = cfg->end_channels / e.EC, NL = cfg->layers * cfg->blocks, n_stack = (NL + e.LPW - 1) / e.LPW;
-        if (PA > 16) continue;
-        // The stacked chain is a short pipeline (n_stack + 2 stages, each busy ~3 us per item): it saturates at about half a token per stage,
-        // beyond that the one-layer-per-workgroup pipeline of variant 3 wins (measured, profiles/r04_v4_vs_v3_streams.txt: cfg2 -- 10 stack
-        // workgroups -- up to 6 streams, cfg1 -- 2 -- up to 2, the train_script shape -- 15 -- up to 8).
-        if (!forced && cfg->n_streams > wn_v4_stream_limit(n_stack)) continue;
-        const int n_smp = wn_sampler_count(cfg->n_streams);
-        if (n_stack + PA + n_smp > n_cu) continue;
-        if (e.lds_floats(cfg->n_streams) * 4 > WN_LDS_MAX_BYTES) continue;
-        if (out_vi) *out_vi = (int)i;
-        if (outPA) *outPA = PA;
-        return true;
-    }
-    return false;
 }
 
 // ------------------------------------------------------------------------------------------------ handle
@@ -334,6 +212,11 @@ struct WnTrainLay {
     bool bf16;  // the saved forward ran with bf16 operands: so does its backward
 };
 struct WnDetWs { float* buf = nullptr; size_t floats = 0; };
+// The one-shot armings of the NEXT job on a handle: the log-probability output (wn_set_logprob_output) and the forced samples (wn_set_forced_samples)
+struct WnArming {
+    float* logp_out = nullptr; int64_t logp_capacity = 0; int32_t logp_mode = 0;
+    const int32_t* forced_in = nullptr; int64_t forced_capacity = 0;
+};
 // What the rounds of a multi-round handle share (wn_load_weights): the chain's weight images, start_conv and the GEMM-ready banks of wn_banks.h
 struct WnWeights {
     float *d_blobs = nullptr, *d_start_t = nullptr, *d_start_b = nullptr;
@@ -354,9 +237,11 @@ struct wn_handle {
     long long t_base = 0;  // evaluations since the last reset
     int n_cu = 0, wall_khz = 0;
     int variant = 1;   // 1 = generic LDS-resident kernel, 3 = wave-specialised register-resident kernel (2: the 256-thread kernels of rounds 1-2, removed), 4 = stacked kernel
-    int v2_index = -1; // row of wn_v2_table() / wn_v4_table()
+    int shape = -1;    // row of wn_chain_shapes() (-1: the generic kernel)
+    const void* kern[3] = {nullptr, nullptr, nullptr};   // the chain kernels by wn_kernel_slot (product, diag, extras), resolved at creation (wn_resolve_kernels)
+    int threads = 0;   // ... and their workgroup size
     int lds_bytes = 0;
-    int v3_mode = 0;    // variant 3: streams per pipeline item (wn_v3_mode)
+    int v3_mode = 0;    // variant 3: streams per pipeline item (wn_v3_mode_for)
     int v3_slots = 0;   // variant 3: skip-lane slots re-used per in-flight item (wn_v3_slots_for; 0 = one slot per stream)
     int dev_overrides = 0;  // a development override was in effect when this handle was planned (wn_dev_env)
     // Zero padding: a channel shape the wave-specialised kernel is not compiled for runs as the next instantiated shape that holds it,
@@ -387,8 +272,7 @@ struct wn_handle {
     int fw_bf16_taps = 0;                          //   kernel_size 3 and 4: bf16 operands for wn_forward / wn_score alone (WN_PRECISION_BF16_TAPS)
     int prof_items = 0;      // stamps requested for the next job (0 = off)
     int32_t smp_top_k = 0; float smp_top_p = 0.f;   // sampling filters of every later job (wn_set_sampling; as given: wn_generate normalises the off values)
-    float* logp_out = nullptr; int64_t logp_capacity = 0; int32_t logp_mode = 0;   // log-probability output of the NEXT job alone (wn_set_logprob_output; wn_generate consumes it)
-    const int32_t* forced_in = nullptr; int64_t forced_capacity = 0;               // forced samples of the NEXT job alone (wn_set_forced_samples; likewise)
+    WnArming arm;   // what the NEXT job alone is armed with (wn_generate takes it)
     int prof_recorded = 0;   // stamps held in d_prof
     std::vector<int64_t> ring_off;
     std::vector<int32_t> dil;
@@ -416,26 +300,20 @@ static void wn_free_weights(wn_handle* h) {   // (members i > 0 of a rounds fron
     if (!h->shares_weights) { rt_free(h->w.d_blobs); rt_free(h->w.d_start_t); rt_free(h->w.d_start_b); rt_free(h->w.d_fw); rt_free(h->w.d_fwb); }
 }
 
-// The chain kernel a handle runs: its function (for the attribute and occupancy queries of wn_create), its workgroup size, its launch
-// (variants 3 and 4 exist twice: the product instantiation and the DIAG one -- wall-clock stamps, logits dump -- that a job with wn_profile_next or
-//  dbg_logits or a sampling filter, a log-probability output or forced samples runs; the generic kernel tests at run time)
-struct WnChainKernel { const void* fn; int threads; };
-static WnChainKernel wn_chain_kernel(const wn_handle* h, bool diag) {
-    if (h->variant == 4) return WnChainKernel{diag ? wn_v4_table()[h->v2_index].fn_diag : wn_v4_table()[h->v2_index].fn, WN_THREADS_V4};
-    if (h->variant == 3) {
-        const WnV2Entry& e = wn_v2_table()[h->v2_index];
-        return WnChainKernel{(diag ? e.fn_v3_diag : e.fn_v3)[h->v3_slots ? 2 : (h->v3_mode & 1)], WN_THREADS_V3};
+// The chain kernels a handle runs, resolved ONCE at creation into the three slots of wn_kernel_slot (wn_plan.h has the truth table): wn_create sets their
+// attributes and checks their occupancy, wn_generate launches the slot of what the job needs (wn_job_slot)
+static void wn_resolve_kernels(wn_handle* h) {
+    const void* col[3] = {(const void*)wn_generate_kernel, nullptr, nullptr};   // the table's columns: product, DIAG, the slot form's filter kernel
+    h->threads = WN_THREADS;
+    if (h->variant == 4) {
+        const WnV4Kernels& k = wn_v4_kernels()[wn_chain_shapes()[h->shape].index];
+        col[0] = k.fn; col[1] = k.fn_diag; h->threads = WN_THREADS_V4;
+    } else if (h->variant == 3) {
+        const WnV3Kernels& k = wn_v3_kernels()[wn_chain_shapes()[h->shape].index];
+        const int form = h->v3_slots ? 2 : (h->v3_mode & 1);
+        col[0] = k.fn[form]; col[1] = k.fn_diag[form]; col[2] = k.fn_filter; h->threads = WN_THREADS_V3;
     }
-    return WnChainKernel{(const void*)wn_generate_kernel, WN_THREADS};
-}
-static void wn_chain_launch(const wn_handle* h, hipStream_t st, const WnRun& r) {
-    const bool diag = r.prof != nullptr || r.dbg_logits != nullptr || r.top_k != 0 || r.top_p != 0.f || r.logp != 0;   // (the sampling filters, the log-probabilities and the forced fork live in the DIAG samplers: r.logp carries both flags)
-    if (h->variant == 4)
-        wn_v4_table()[h->v2_index].launch(diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
-    else if (h->variant == 3)
-        wn_v2_table()[h->v2_index].launch_v3(h->v3_slots ? 2 : (h->v3_mode & 1), diag, h->plan.n_blocks, (size_t)h->lds_bytes, st, h->plan, r);
-    else
-        hipLaunchKernelGGL(wn_generate_kernel, dim3(h->plan.n_blocks), dim3(WN_THREADS), (size_t)h->lds_bytes, st, h->plan, r);
+    for (int s = 0; s < 3; ++s) h->kern[s] = col[wn_slot_column(h->variant, h->variant == 3 && h->v3_slots, s)];
 }
 
 // CUs per XCD a job of this handle needs -- the workgroups that stay resident on the fullest XCD (blocks are dispatched round-robin over
@@ -477,234 +355,44 @@ extern "C" void wn_destroy(wn_handle* h) {
     delete h;
 }
 
-static int wn_create_impl(const wn_config* cfg, wn_handle** out);
-
-// Zero padding of the channel counts.  Extra residual channels stay 0 for ever (zero rows in start_conv and the residual convs), extra
-// dilation channels give tanh(0) * sigmoid(0) = 0, extra skip / end channels give relu(0) = 0 against zero weights: the padded network
-// computes the same logits, and every product only gains exact zeros.  So a kernel_size-2, 256-class model whose channel shape is not
-// in the table of the wave-specialised kernel (e.g. 48 / 48 / 300 / 200) runs as the cheapest instantiated shape that holds it instead
-// of on the generic LDS-resident kernel (last measured 6-13x slower).  Not applied when the caller pins layer_split / head_split.
-static bool wn_pad_config(const wn_config* cfg, int n_cu, wn_config* padded) {
-    if (cfg->kernel_size != 2 || cfg->classes != 256 || cfg->layer_split > 0 || cfg->head_split > 0 || (cfg->reserved[0] & WN_CFG_NO_PADDING)) return false;
-    wn_config probe = *cfg;
-    if (probe.n_streams > WN_V3_ROUND_STREAMS) probe.n_streams = WN_V3_ROUND_STREAMS;
-    if (wn_v4_applicable(&probe, n_cu, nullptr, nullptr) || wn_v3_applicable(&probe, n_cu, nullptr, nullptr, nullptr)) return false;   // served as it is
-    std::vector<WnShapeRow> rows;
-    for (const WnV2Entry& e : wn_v2_table()) rows.push_back(WnShapeRow{e.R, e.DC, e.S, e.EC, e.Pm});
-    int dims[4];
-    const int pick = wn_pad_pick(rows.data(), (int)rows.size(), cfg->residual_channels, cfg->dilation_channels, cfg->skip_channels, cfg->end_channels,
-                                 cfg->layers * cfg->blocks, [&](int R2, int D2, int S2, int E2) {
-                                     wn_config c = probe;
-                                     c.residual_channels = R2; c.dilation_channels = D2; c.skip_channels = S2; c.end_channels = E2;
-                                     return wn_v3_applicable(&c, n_cu, nullptr, nullptr, nullptr);
-                                 }, dims);
-    if (pick < 0) return false;
-    *padded = *cfg;
-    padded->residual_channels = dims[0]; padded->dilation_channels = dims[1]; padded->skip_channels = dims[2]; padded->end_channels = dims[3];
-    return true;
+// wn_create, step 1 validates the configuration (wn_plan.h: wn_config_refusal); step 2: the device (selected on the way)
+struct WnDevice { int n_cu = 256, wall_khz = 100000; char busid[32] = ""; };
+static int wn_query_device(int device_id, WnDevice* d) {
+    int ndev = 0;
+    int rc = rt_hip(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
+    if (rc) return rc;
+    if (device_id < 0 || device_id >= ndev) return wn_fail(WN_E_BADARG, "wn_create: device_id %d of %d", device_id, ndev);
+    if ((rc = rt_hip(hipSetDevice(device_id), "hipSetDevice"))) return rc;
+    hipDeviceProp_t prop;
+    if ((rc = rt_hip(hipGetDeviceProperties(&prop, device_id), "hipGetDeviceProperties"))) return rc;
+    d->n_cu = prop.multiProcessorCount;
+    if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
+        return wn_fail(WN_E_UNSUPPORTED, "wn_create: device %d is %s; this library is built for gfx950 (MI355X) only", device_id, prop.gcnArchName);
+    int khz = 0;
+    if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, device_id) == hipSuccess && khz > 0) d->wall_khz = khz;
+    if (hipDeviceGetPCIBusId(d->busid, (int)sizeof(d->busid), device_id) != hipSuccess || !d->busid[0]) snprintf(d->busid, sizeof(d->busid), "dev%d", device_id);
+    return WN_OK;
+}
+// step 3 plans (wn_plan.h: wn_chain_plan, pure) under the development switches, read here once per wn_create
+static WnPins wn_read_pins() {
+    WnPins p = {};
+    p.kernel = wn_dev_env("WN_KERNEL"); p.samplers = wn_dev_env("WN_SAMPLERS"); p.v3_mode = wn_dev_env("WN_V3_MODE"); p.v3_slots = wn_dev_env("WN_V3_SLOTS");
+    p.no_rounds = wn_dev_flag("WN_CHAINS"); p.no_local_stores = wn_dev_flag("WN_NO_LOCAL_STORES");
+    (void)wn_dev_env("WN_NO_FUSED_SCORE");   // (wn_score reads it per call; a handle created under it says so from the start)
+    return p;
 }
 
-extern "C" int wn_create(const wn_config* cfg, wn_handle** out) {
-    g_err[0] = 0;
-    if (!cfg || !out) return wn_fail(WN_E_BADARG, "wn_create: NULL argument");
-    *out = nullptr;
-    if (!g_create_depth) g_dev_env_used = 0;
-    if (!g_create_depth && cfg->layers >= 1 && cfg->blocks >= 1 && cfg->dilation_channels >= 1 && cfg->residual_channels >= 1 && cfg->skip_channels >= 1 &&
-        cfg->end_channels >= 1 && cfg->n_streams >= 1 && cfg->layers <= 24) {
-        int ndev = 0, n_cu = 0;
-        if (hipGetDeviceCount(&ndev) == hipSuccess && cfg->device_id >= 0 && cfg->device_id < ndev &&
-            hipDeviceGetAttribute(&n_cu, hipDeviceAttributeMultiprocessorCount, cfg->device_id) == hipSuccess) {
-            wn_config eff;
-            if (wn_pad_config(cfg, n_cu, &eff)) {
-                const int rc = wn_create_impl(&eff, out);
-                if (rc == WN_OK && (*out)->variant >= 3) {
-                    wn_handle* h = *out;
-                    h->padded = true;
-                    h->user_R = cfg->residual_channels; h->user_D = cfg->dilation_channels; h->user_S = cfg->skip_channels; h->user_E = cfg->end_channels;
-                    h->export_R = h->user_R;
-                    for (wn_handle* c : h->chains) c->export_R = h->user_R;
-                    return WN_OK;
-                }
-                if (rc == WN_OK) { wn_destroy(*out); *out = nullptr; }   // (not the kernel the padding was for: plan the caller's shape instead)
-                g_err[0] = 0;
-            }
-        }
-    }
-    return wn_create_impl(cfg, out);
-}
-
-static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
-    g_err[0] = 0;
-    if (!cfg || !out) return wn_fail(WN_E_BADARG, "wn_create: NULL argument");
-    *out = nullptr;
-    if (cfg->layers < 1 || cfg->blocks < 1 || cfg->dilation_channels < 1 || cfg->residual_channels < 1 ||
-        cfg->skip_channels < 1 || cfg->end_channels < 1 || cfg->classes < 2 || cfg->n_streams < 1)
-        return wn_fail(WN_E_BADARG, "wn_create: non-positive dimension in wn_config");
-    if (cfg->kernel_size < 1) return wn_fail(WN_E_BADARG, "wn_create: kernel_size must be >= 1");
-    if (cfg->layers > 24) return wn_fail(WN_E_UNSUPPORTED, "wn_create: layers > 24 (dilation 2^layers overflows the queue)");
-    if (cfg->layer_split < 0 || cfg->head_split < 0 || (cfg->reserved[0] & ~WN_CFG_NO_PADDING) || cfg->reserved[1] || cfg->reserved[2])
-        return wn_fail(WN_E_BADARG, "wn_create: negative split / non-zero reserved field");
-    int n_cu = 256, wall_khz = 100000;
-    {
-        int ndev = 0;
-        int rc = rt_hip(hipGetDeviceCount(&ndev), "hipGetDeviceCount");
-        if (rc) return rc;
-        if (cfg->device_id < 0 || cfg->device_id >= ndev) return wn_fail(WN_E_BADARG, "wn_create: device_id %d of %d", cfg->device_id, ndev);
-        if ((rc = rt_hip(hipSetDevice(cfg->device_id), "hipSetDevice"))) return rc;
-        hipDeviceProp_t prop;
-        if ((rc = rt_hip(hipGetDeviceProperties(&prop, cfg->device_id), "hipGetDeviceProperties"))) return rc;
-        n_cu = prop.multiProcessorCount;
-        if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
-            return wn_fail(WN_E_UNSUPPORTED, "wn_create: device %d is %s; this library is built for gfx950 (MI355X) only",
-                           cfg->device_id, prop.gcnArchName);
-        int khz = 0;
-        if (hipDeviceGetAttribute(&khz, hipDeviceAttributeWallClockRate, cfg->device_id) == hipSuccess && khz > 0) wall_khz = khz;
-    }
-    char busid[32] = "";
-    if (hipDeviceGetPCIBusId(busid, (int)sizeof(busid), cfg->device_id) != hipSuccess || !busid[0]) snprintf(busid, sizeof(busid), "dev%d", cfg->device_id);
-    {   // rounds of the wave-specialised chain (see wn_handle::rounds)
-        const bool off = wn_dev_flag("WN_CHAINS");
-        wn_config probe = *cfg;
-        probe.n_streams = WN_V3_ROUND_STREAMS;
-        if (!off && cfg->n_streams > WN_V3_ROUND_STREAMS && !wn_v3_applicable(cfg, n_cu, nullptr, nullptr, nullptr) &&
-            wn_v3_applicable(&probe, n_cu, nullptr, nullptr, nullptr)) {
-            const std::vector<int> sizes = wn_v3_round_sizes(cfg->n_streams, WN_V3_ROUND_STREAMS);
-            std::vector<wn_handle*> cs;
-            std::vector<int> firsts(1, 0);
-            int rc = WN_OK;
-            for (size_t i = 0; i < sizes.size() && rc == WN_OK; ++i) {
-                wn_config part = *cfg;
-                const int n = sizes[i];
-                part.n_streams = n;
-                wn_handle* c = nullptr;
-                ++g_create_depth;
-                rc = wn_create(&part, &c);
-                --g_create_depth;
-                if (rc == WN_OK) {
-                    cs.push_back(c);
-                    firsts.push_back(firsts.back() + n);
-                    if (c->variant != 3) rc = WN_E_UNSUPPORTED;
-                }
-            }
-            if (rc == WN_OK) {
-                wn_handle* c0 = cs[0];
-                wn_handle* f = new wn_handle();
-                f->cfg = *cfg;
-                f->plan = c0->plan;
-                f->plan.n_streams = cfg->n_streams;
-                f->n_cu = n_cu; f->wall_khz = wall_khz; f->variant = c0->variant; f->v2_index = c0->v2_index; f->lds_bytes = c0->lds_bytes;
-                f->v3_mode = c0->v3_mode; f->v3_slots = c0->v3_slots;
-                f->dil = c0->dil;
-                f->chains = cs;
-                f->chain_first = firsts;
-                f->rounds = true;
-                *out = f;
-                return WN_OK;
-            }
-            for (wn_handle* c : cs) wn_destroy(c);
-            if (rc != WN_E_UNSUPPORTED) return rc;
-            g_err[0] = 0;
-        }
-    }
+// steps 4 and 5 for ONE chain: allocate and upload what the plan sizes, resolve the kernels, check their residency
+static int wn_build_chain(const WnChainPlan& cp, const WnDevice& dev, wn_handle** out) {
     wn_handle* h = new wn_handle();
-    h->cfg = *cfg;
+    h->cfg = cp.cfg; h->plan = cp.pl;
     { const char* de = getenv("WN_DETERMINISTIC"); h->deterministic = de && de[0] == '1'; }
-    h->n_cu = n_cu; h->wall_khz = wall_khz;
-    memcpy(h->busid, busid, sizeof(busid));
+    h->n_cu = dev.n_cu; h->wall_khz = dev.wall_khz;
+    memcpy(h->busid, dev.busid, sizeof(h->busid));
+    h->variant = cp.variant; h->shape = cp.row; h->lds_bytes = cp.lds_bytes; h->v3_mode = cp.v3_mode; h->v3_slots = cp.v3_slots; h->gate_need = cp.gate_need;
+    h->dil = cp.dil; h->ring_off = cp.ring_off; h->ring_floats = cp.ring_floats; h->gran_count = cp.gran_count; h->blob_floats = cp.blob_floats;
+    h->dev_overrides = g_dev_env_used;
     WnPlan& pl = h->plan;
-    pl.layers = cfg->layers; pl.blocks = cfg->blocks; pl.NL = cfg->layers * cfg->blocks;
-    pl.R = cfg->residual_channels; pl.D = cfg->dilation_channels; pl.S = cfg->skip_channels; pl.E = cfg->end_channels;
-    pl.C = cfg->classes; pl.k = cfg->kernel_size; pl.has_bias = cfg->bias ? 1 : 0; pl.n_streams = cfg->n_streams;
-    pl.HR = 1;
-    {
-        int P2 = 0, PA2 = 0;
-        int vi3 = -1, vi4 = -1;
-        if (wn_v4_applicable(cfg, n_cu, &vi4, &PA2)) {
-            const WnV4Entry& ve = wn_v4_table()[vi4];
-            h->variant = 4; h->v2_index = vi4;
-            wn_plan_geometry(pl, 1, PA2);
-            pl.LPW = ve.LPW;
-            pl.n_lw = (pl.NL + ve.LPW - 1) / ve.LPW;
-            pl.n_smp = wn_sampler_count(cfg->n_streams);
-            pl.n_wg = pl.n_lw + PA2 + pl.n_smp;
-            pl.start_in_lds = (ve.lds_pre_head + 256 * pl.R) * 4 <= WN_LDS_MAX_BYTES ? 1 : 0;
-            h->lds_bytes = ve.lds_floats(pl.n_streams) * 4;
-            pl.lds_floats = h->lds_bytes / 4;
-        } else if (wn_v3_applicable(cfg, n_cu, &vi3, &P2, &PA2)) {
-            h->variant = 3; h->v2_index = vi3;
-            wn_plan_geometry(pl, P2, PA2);
-            pl.n_smp = wn_sampler_count(cfg->n_streams);  // sampling runs on dedicated workgroups (they also feed layer 0)
-            pl.n_wg += pl.n_smp;
-            pl.start_in_lds = (wn_v2_table()[vi3].lds_pre_v3 + 256 * pl.R) * 4 <= WN_LDS_MAX_BYTES ? 1 : 0;  // the samplers' copy of start_conv^T
-            h->v3_mode = wn_v3_mode(pl.n_streams, pl.NL);
-            if (!wn_v2_table()[vi3].fn_v3[1]) h->v3_mode &= ~1;  // (shapes whose filter/gate slices cannot be halved: one stream per item only)
-            if ((h->v3_mode & 2) && pl.NL * P2 + 2 * PA2 + pl.n_smp <= n_cu) {  // a second set of head workgroups
-                pl.HR = 2;
-                pl.n_wg += PA2;
-            } else {
-                h->v3_mode &= 1;
-            }
-            h->v3_slots = wn_v3_slots_for(pl.n_streams, h->v3_mode, wn_v2_table()[vi3].fn_v3[2] != nullptr, wn_dev_env("WN_V3_SLOTS"), pl.NL);
-            h->lds_bytes = wn_v2_table()[vi3].lds_floats_v3(pl.n_streams, h->v3_mode & 1) * 4;
-            if (pl.n_streams <= 4 && !(h->v3_mode & 1)) h->lds_bytes = WN_LDS_MAX_BYTES;  // 1-4 streams (8: measured level, profiles/archive/r03_few_stream_lds_queues.txt): the layers' dilation queues live in LDS where they fit (wn_v3_layer)
-            pl.lds_floats = h->lds_bytes / 4;
-        }
-    }
-    if (h->variant == 1) {
-        const std::string why = wn_plan_choose(pl, n_cu, cfg->layer_split, cfg->head_split);
-        if (!why.empty()) {
-            delete h;
-            return wn_fail(WN_E_UNSUPPORTED, "wn_create: %s", why.c_str());
-        }
-        h->lds_bytes = (pl.lds_floats + 8) * 4;  // + the fail-flag word (wn_any_failed)
-    }
-    // tables
-    h->dil.resize(pl.NL); h->ring_off.resize(pl.NL);
-    int64_t off = 0;
-    for (int l = 0; l < pl.NL; ++l) {
-        const int d = 1 << (l % pl.layers);  // wavenet_model.py:72,108-110
-        h->dil[l] = d;
-        h->ring_off[l] = off;
-        const int64_t ML = (int64_t)(pl.k - 1) * d + 1;  // wavenet_model.py:78
-        off += (int64_t)pl.P * pl.n_streams * ML * pl.R;
-    }
-    h->ring_floats = (size_t)off;
-    std::vector<int64_t> state_off(pl.NL + 1, 0);
-    for (int l = 0; l < pl.NL; ++l) state_off[l + 1] = state_off[l] + (int64_t)(pl.k - 1) * h->dil[l] + 1;
-    std::vector<int32_t> wg_map;
-    pl.n_blocks = pl.n_wg;
-    pl.allow_plain = 0;
-    if ((h->variant == 3 || h->variant == 4) && n_cu % 8 == 0 &&
-        wn_make_wg_map_layers(h->variant == 4 ? pl.n_lw : pl.NL, pl.P, pl.PA * pl.HR, pl.n_smp, 8, n_cu / 8, wg_map, &pl.n_blocks)) {
-        pl.allow_plain = wn_dev_flag("WN_NO_LOCAL_STORES") ? 0 : 1;
-    } else {
-        wn_make_wg_map(pl.n_wg, 8, wg_map);
-    }
-    {   // what a job of this handle keeps RESIDENT per XCD (block b lands on XCD b % 8; padding blocks exit at once and hold nothing)
-        int per_xcd[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-        const int nx = n_cu % 8 == 0 ? 8 : 1;
-        for (int b = 0; b < pl.n_blocks; ++b)
-            if (wg_map[b] >= 0) per_xcd[b % nx]++;
-        h->gate_need = 0;
-        for (int x = 0; x < nx; ++x) h->gate_need = per_xcd[x] > h->gate_need ? per_xcd[x] : h->gate_need;
-    }
-    const size_t n_lw = h->variant == 4 ? (size_t)pl.n_lw : (size_t)pl.NL * pl.P;
-    const size_t gx_n = n_lw * pl.n_streams * pl.R, gs_n = n_lw * pl.n_streams * pl.S, gl_n = (size_t)pl.PA * pl.n_streams * pl.C;
-    const size_t g0_n = h->variant >= 3 ? (size_t)pl.n_streams * pl.R : 0;
-    h->gran_count = gx_n + gs_n + gl_n + (size_t)pl.n_streams + g0_n;
-    h->blob_floats = n_lw * pl.blob_layer_floats + (size_t)pl.PA * pl.blob_head_floats;
-    pl.n_lw = (int32_t)n_lw; pl.head_blob_off = (int64_t)n_lw * pl.blob_layer_floats;
-    if (h->variant != 4) pl.LPW = 1;
-    if (h->variant == 4) {
-        const WnV4Entry& ve = wn_v4_table()[h->v2_index];
-        pl.head_blob_off = (int64_t)n_lw * ve.LPW * ve.nwpl * WN_THREADS_V4;
-        h->blob_floats = (size_t)pl.head_blob_off + (size_t)pl.PA * ve.nwh * 256;
-    }
-    if (h->variant == 3) {
-        const WnV2Entry& ve = wn_v2_table()[h->v2_index];
-        h->blob_floats = n_lw * (size_t)ve.nwl * 256 + (size_t)pl.PA * ve.nwh * 256;
-        pl.head_blob_off = (int64_t)n_lw * ve.nwl * 256;
-    }
     h->w.d_blobs = (float*)rt_malloc(h->blob_floats * 4);
     h->w.d_start_t = (float*)rt_malloc((size_t)pl.C * pl.R * 4);
     h->w.d_start_b = (float*)rt_malloc((size_t)pl.R * 4);
@@ -717,56 +405,99 @@ static int wn_create_impl(const wn_config* cfg, wn_handle** out) {
     h->d_status = (uint32_t*)rt_malloc((size_t)WN_STATUS_WORDS(pl.n_wg) * 4);
     if (!h->w.d_blobs || !h->w.d_start_t || !h->w.d_start_b || !h->d_rings || !h->d_dil || !h->d_ring_off || !h->d_state_off || !h->d_wg_map ||
         !h->d_gran || !h->d_status) {
-        const double q_mb = h->ring_floats * 4e-6, g_mb = h->gran_count * 8e-6, w_mb = h->blob_floats * 4e-6;
         wn_destroy(h);
-        return wn_fail(WN_E_NOMEM, "wn_create: device allocation failed (queues %.1f MB, hand-off %.1f MB, weights %.1f MB)", q_mb, g_mb, w_mb);
+        return wn_fail(WN_E_NOMEM, "wn_create: device allocation failed (queues %.1f MB, hand-off %.1f MB, weights %.1f MB)", cp.ring_floats * 4e-6,
+                       cp.gran_count * 8e-6, cp.blob_floats * 4e-6);
     }
     int rc = 0;
-    rc = rc ? rc : rt_h2d(h->d_dil, h->dil.data(), (size_t)pl.NL * 4);
-    rc = rc ? rc : rt_h2d(h->d_ring_off, h->ring_off.data(), (size_t)pl.NL * 8);
-    rc = rc ? rc : rt_h2d(h->d_state_off, state_off.data(), (size_t)(pl.NL + 1) * 8);
-    rc = rc ? rc : rt_h2d(h->d_wg_map, wg_map.data(), (size_t)pl.n_blocks * 4);
+    rc = rc ? rc : rt_h2d(h->d_dil, cp.dil.data(), (size_t)pl.NL * 4);
+    rc = rc ? rc : rt_h2d(h->d_ring_off, cp.ring_off.data(), (size_t)pl.NL * 8);
+    rc = rc ? rc : rt_h2d(h->d_state_off, cp.state_off.data(), (size_t)(pl.NL + 1) * 8);
+    rc = rc ? rc : rt_h2d(h->d_wg_map, cp.wg_map.data(), (size_t)pl.n_blocks * 4);
     rc = rc ? rc : rt_memset_async(h->d_rings, 0, h->ring_floats * 4, nullptr);
     rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)WN_STATUS_WORDS(pl.n_wg) * 4, nullptr);
     rc = rc ? rc : rt_sync(nullptr);
-    if (rc) { wn_destroy(h); return rc; }
     pl.blobs = h->w.d_blobs; pl.start_t = h->w.d_start_t; pl.start_b = nullptr;
     pl.dil = h->d_dil; pl.ring_off = h->d_ring_off; pl.wg_map = h->d_wg_map; pl.rings = h->d_rings;
-    pl.gx = h->d_gran; pl.gs = h->d_gran + gx_n; pl.gl = h->d_gran + gx_n + gs_n; pl.gi = h->d_gran + gx_n + gs_n + gl_n;
-    pl.g0 = pl.gi + pl.n_streams;
+    pl.gx = h->d_gran; pl.gs = pl.gx + cp.gx_n; pl.gl = pl.gs + cp.gs_n; pl.gi = pl.gl + cp.gl_n; pl.g0 = pl.gi + pl.n_streams;
     pl.status = h->d_status;
     pl.xcc_tab = h->d_status + 8;
-    WnChainKernel ck = wn_chain_kernel(h, false), ck_diag = wn_chain_kernel(h, true);
-    if (h->variant == 3 && h->v3_slots) {   // the slot re-use form has ONE kernel for plain and diagnostic jobs and a second one for jobs with a sampling filter
-        ck_diag.fn = wn_v2_table()[h->v2_index].fn_v3_filter;
+    // residency is a requirement, not a hope: what the hardware can keep resident of THESE kernels with THIS much LDS (of the distinct functions among the
+    // three slots: the smallest figure), against what the plan needs per XCD
+    wn_resolve_kernels(h);
+    int per_cu = 0;
+    for (int s = 0; s < 3 && !rc; ++s) {
+        if ((s > 0 && h->kern[s] == h->kern[0]) || (s > 1 && h->kern[s] == h->kern[1])) continue;
+        int n = 0;
+        rc = rt_hip(hipFuncSetAttribute(h->kern[s], hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
+        rc = rc ? rc : rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, h->kern[s], h->threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
+        if (s == 0 || n < per_cu) per_cu = n;
     }
-    rc = rt_hip(hipFuncSetAttribute(ck.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
-    if (!rc && ck_diag.fn != ck.fn)
-        rc = rt_hip(hipFuncSetAttribute(ck_diag.fn, hipFuncAttributeMaxDynamicSharedMemorySize, h->lds_bytes), "hipFuncSetAttribute(MaxDynamicSharedMemorySize)");
     if (rc) { wn_destroy(h); return rc; }
-    {   // residency is a requirement, not a hope: what the hardware can keep resident of THIS kernel with THIS much LDS, against what the plan needs per XCD
-        int per_cu = 0;   // (of either instantiation: the smaller figure)
-        rc = rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, ck.fn, ck.threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
-        if (!rc && ck_diag.fn != ck.fn) {
-            int per_cu_diag = 0;
-            rc = rt_hip(hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu_diag, ck_diag.fn, ck_diag.threads, (size_t)h->lds_bytes), "hipOccupancyMaxActiveBlocksPerMultiprocessor");
-            if (per_cu_diag < per_cu) per_cu = per_cu_diag;
-        }
-        if (rc) { wn_destroy(h); return rc; }
-        int need = 0, cap = 0;
-        wn_gate_numbers(h, &need, &cap);
-        h->wg_per_cu = per_cu;
-        if ((long long)per_cu * cap < need) {
-            const int n_wg = pl.n_wg;
-            wn_destroy(h);
-            return wn_fail(WN_E_UNSUPPORTED, "wn_create: the plan keeps %d workgroups resident on one XCD (%d in all), the device holds %d x %d of this kernel there",
-                           need, n_wg, cap, per_cu);
-        }
+    int need = 0, cap = 0;
+    wn_gate_numbers(h, &need, &cap);
+    h->wg_per_cu = per_cu;
+    if ((long long)per_cu * cap < need) {
+        wn_destroy(h);
+        return wn_fail(WN_E_UNSUPPORTED, "wn_create: the plan keeps %d workgroups resident on one XCD (%d in all), the device holds %d x %d of this kernel there",
+                       need, cp.pl.n_wg, cap, per_cu);
     }
-    (void)wn_dev_env("WN_NO_FUSED_SCORE");   // (wn_score reads it per call; a handle created under it says so from the start)
-    h->dev_overrides = g_dev_env_used;
     *out = h;
     return WN_OK;
+}
+// ... and for the plan as a whole: one chain, or the front of a rounds handle over one chain per round (wn_handle::rounds)
+static int wn_build_handle(const WnChainPlan& cp, const WnDevice& dev, wn_handle** out) {
+    if (cp.rounds.empty()) return wn_build_chain(cp, dev, out);
+    wn_handle* f = new wn_handle();
+    f->cfg = cp.cfg;
+    f->n_cu = dev.n_cu; f->wall_khz = dev.wall_khz; f->variant = cp.variant; f->shape = cp.row; f->lds_bytes = cp.lds_bytes;
+    f->v3_mode = cp.v3_mode; f->v3_slots = cp.v3_slots;
+    f->dil = cp.dil;
+    f->rounds = true;
+    f->chain_first.assign(1, 0);
+    for (const WnChainPlan& m : cp.rounds) {
+        wn_handle* c = nullptr;
+        const int rc = wn_build_chain(m, dev, &c);
+        if (rc) { wn_destroy(f); return rc; }
+        f->chains.push_back(c);
+        f->chain_first.push_back(f->chain_first.back() + m.cfg.n_streams);
+    }
+    f->plan = f->chains[0]->plan;
+    f->plan.n_streams = cp.cfg.n_streams;
+    *out = f;
+    return WN_OK;
+}
+
+extern "C" int wn_create(const wn_config* cfg, wn_handle** out) {
+    g_err[0] = 0;
+    if (!cfg || !out) return wn_fail(WN_E_BADARG, "wn_create: NULL argument");
+    *out = nullptr;
+    g_dev_env_used = 0;
+    std::string why;
+    int rc = wn_config_refusal(*cfg, why);
+    if (rc) return wn_fail(rc, "wn_create: %s", why.c_str());
+    WnDevice dev;
+    if ((rc = wn_query_device(cfg->device_id, &dev))) return rc;
+    WnPins pins = wn_read_pins();
+    const std::vector<WnChainShape>& shapes = wn_chain_shapes();
+    for (;;) {
+        WnChainPlan cp;
+        why = wn_chain_plan(*cfg, dev.n_cu, pins, shapes.data(), (int)shapes.size(), cp);
+        if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "wn_create: %s", why.c_str());
+        rc = wn_build_handle(cp, dev, out);
+        if (rc == WN_OK && cp.padded) {   // cfg / plan carry the PADDED channel counts; these are the caller's
+            wn_handle* h = *out;
+            h->padded = true;
+            h->user_R = cfg->residual_channels; h->user_D = cfg->dilation_channels; h->user_S = cfg->skip_channels; h->user_E = cfg->end_channels;
+            h->export_R = h->user_R;
+            for (wn_handle* c : h->chains) c->export_R = h->user_R;
+        }
+        // a plan whose handle the device refuses is planned again one step simpler: one chain instead of rounds, then the caller's shape instead of the padded one
+        if (rc == WN_E_UNSUPPORTED && !cp.rounds.empty()) pins.no_rounds = true;
+        else if (rc != WN_OK && cp.padded) pins.no_padding = true;
+        else return rc;
+        g_err[0] = 0;
+    }
 }
 
 static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w);
@@ -819,7 +550,7 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
         { int rc = wn_load_weights_impl(c0, w); if (rc) return rc; }
         for (size_t i = 1; i < h->chains.size(); ++i) {
             wn_handle* c = h->chains[i];
-            if (c->blob_floats != c0->blob_floats || c->plan.P != c0->plan.P || c->plan.PA != c0->plan.PA || c->variant != c0->variant || c->v2_index != c0->v2_index)
+            if (c->blob_floats != c0->blob_floats || c->plan.P != c0->plan.P || c->plan.PA != c0->plan.PA || c->variant != c0->variant || c->shape != c0->shape)
                 return wn_fail(WN_E_STATE, "wn_load_weights: the rounds of this handle were planned with different geometries");
             { int rc = rt_hip(hipSetDevice(c->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
             if (c->pending) { int rc = wn_wait(c); if (rc) return rc; }
@@ -838,8 +569,8 @@ static int wn_load_weights_impl(wn_handle* h, const wn_weight_ptrs* w) {
     WnHostWeights hw = {w->start_w, w->start_b, w->filter_w, w->filter_b, w->gate_w, w->gate_b, w->res_w,
                         w->res_b, w->skip_w, w->skip_b, w->end1_w, w->end1_b, w->end2_w, w->end2_b};
     std::vector<float> blobs;
-    if (h->variant == 4) wn_v4_table()[h->v2_index].pack(pl, hw, blobs);
-    else if (h->variant == 3) wn_v2_table()[h->v2_index].pack(pl, hw, blobs);
+    if (h->variant == 4) wn_v4_kernels()[wn_chain_shapes()[h->shape].index].pack(pl, hw, blobs);
+    else if (h->variant == 3) wn_v3_kernels()[wn_chain_shapes()[h->shape].index].pack(pl, hw, blobs);
     else
         wn_pack_blobs(pl, hw, blobs);
     if (blobs.size() != h->blob_floats) return wn_fail(WN_E_STATE, "wn_load_weights: internal blob size mismatch");
@@ -905,28 +636,40 @@ extern "C" int wn_reset(wn_handle* h, void* hip_stream) {
 }
 
 
+// ---- the one-shot armings (WnArming).  take: the handle's arming, which the handle then no longer has
+static WnArming wn_arming_take(wn_handle* h) { const WnArming a = h->arm; h->arm = WnArming(); return a; }
+// check: the armed array holds a value per stream and sample of the job (`fmt`: the refusal, with the capacity, the streams and the samples)
+static int wn_arming_check(const void* armed, int64_t capacity, const wn_handle* h, const wn_generate_args* a, const char* fmt) {
+    if (!armed || a->num_samples <= 0 || (long long)h->plan.n_streams * (long long)a->num_samples <= (long long)capacity) return WN_OK;
+    return wn_fail(WN_E_BADARG, fmt, (long long)capacity, h->plan.n_streams, (long long)a->num_samples);
+}
+// slice: what a rounds member that owns `n` streams from stream `first` on is armed with (the whole arrays' capacities have been checked)
+static WnArming wn_arming_slice(const WnArming& a, size_t first, int n, int64_t num_samples) {
+    WnArming m;
+    if (a.logp_out) { m.logp_out = a.logp_out + first * (size_t)num_samples; m.logp_capacity = (int64_t)n * num_samples; m.logp_mode = a.logp_mode; }
+    if (a.forced_in) { m.forced_in = a.forced_in + first * (size_t)num_samples; m.forced_capacity = (int64_t)n * num_samples; }
+    return m;
+}
+// publish: a pointer into two words of the status block, behind the block's memset on the job's stream: two 32-bit fills, no host buffer to keep alive
+static int wn_publish_ptr(uint32_t* at, const void* p, void* stream) {
+    const unsigned long long bits = (unsigned long long)(uintptr_t)p;
+    const int rc = rt_hip(hipMemsetD32Async((hipDeviceptr_t)at, (int)(uint32_t)bits, 1, (hipStream_t)stream), "hipMemsetD32Async");
+    return rc ? rc : rt_hip(hipMemsetD32Async((hipDeviceptr_t)(at + 1), (int)(uint32_t)(bits >> 32), 1, (hipStream_t)stream), "hipMemsetD32Async");
+}
+
 extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     g_err[0] = 0;
     if (!h || !a) return wn_fail(WN_E_BADARG, "wn_generate: NULL argument");
-    // the log-probability output (wn_set_logprob_output) and the forced samples (wn_set_forced_samples) armed for THIS call: BOTH are consumed here, ahead
-    // of either capacity test, whatever becomes of the call -- a job refused for one of them must not leave the other behind for the next job
-    float* const logp_out = h->logp_out;
-    const int64_t logp_capacity = h->logp_capacity;
-    const int32_t logp_mode = h->logp_mode;
-    h->logp_out = nullptr; h->logp_capacity = 0; h->logp_mode = 0;
-    const int32_t* const forced_in = h->forced_in;
-    const int64_t forced_capacity = h->forced_capacity;
-    h->forced_in = nullptr; h->forced_capacity = 0;
-    if (logp_out && a->num_samples > 0 && (long long)h->plan.n_streams * (long long)a->num_samples > (long long)logp_capacity)
-        return wn_fail(WN_E_BADARG, "wn_generate: the log-probability output holds %lld floats, the job writes %d x %lld; nothing was launched",
-                       (long long)logp_capacity, h->plan.n_streams, (long long)a->num_samples);
-    if (forced_in && a->num_samples > 0 && (long long)h->plan.n_streams * (long long)a->num_samples > (long long)forced_capacity)
-        return wn_fail(WN_E_BADARG, "wn_generate: the forced samples hold %lld values, the job reads %d x %lld; nothing was launched",
-                       (long long)forced_capacity, h->plan.n_streams, (long long)a->num_samples);
+    // what THIS call is armed with is taken here, BOTH armings ahead of either capacity test, whatever becomes of the call -- a job refused for one of them
+    // must not leave the other behind for the next job
+    const WnArming arm = wn_arming_take(h);
+    if (wn_arming_check(arm.logp_out, arm.logp_capacity, h, a, "wn_generate: the log-probability output holds %lld floats, the job writes %d x %lld; nothing was launched") ||
+        wn_arming_check(arm.forced_in, arm.forced_capacity, h, a, "wn_generate: the forced samples hold %lld values, the job reads %d x %lld; nothing was launched"))
+        return WN_E_BADARG;
     if (!h->have_weights) return wn_fail(WN_E_STATE, "wn_generate: wn_load_weights has not been called");
+    if (a->n_given < 1 || a->num_samples < 0) return wn_fail(WN_E_BADARG, "wn_generate: n_given must be >= 1 and num_samples >= 0");
+    if (!a->first_samples) return wn_fail(WN_E_BADARG, "wn_generate: first_samples is NULL");
     if (!h->chains.empty()) {   // rounds: member i owns streams [chain_first[i], chain_first[i + 1]); one after the other on the caller's stream
-        if (a->n_given < 1 || a->num_samples < 0) return wn_fail(WN_E_BADARG, "wn_generate: n_given must be >= 1 and num_samples >= 0");
-        if (!a->first_samples) return wn_fail(WN_E_BADARG, "wn_generate: first_samples is NULL");
         { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
         if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
         if (h->broken) return wn_fail(WN_E_STATE, "wn_generate: an earlier job failed half way through its rounds; call wn_reset");
@@ -939,17 +682,7 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
             if (a->out_idx) b.out_idx = a->out_idx + s0 * (size_t)a->num_samples;
             if (a->dbg_logits) b.dbg_logits = a->dbg_logits + s0 * (size_t)a->num_samples * h->plan.C;
             if (a->stream_temperatures) b.stream_temperatures = a->stream_temperatures + s0;
-            if (logp_out) {   // (the member's slice; the whole array's capacity was checked above)
-                wn_handle* m = h->chains[i];
-                m->logp_out = logp_out + s0 * (size_t)a->num_samples;
-                m->logp_capacity = (int64_t)(h->chain_first[i + 1] - h->chain_first[i]) * a->num_samples;
-                m->logp_mode = logp_mode;
-            }
-            if (forced_in) {
-                wn_handle* m = h->chains[i];
-                m->forced_in = forced_in + s0 * (size_t)a->num_samples;
-                m->forced_capacity = (int64_t)(h->chain_first[i + 1] - h->chain_first[i]) * a->num_samples;
-            }
+            h->chains[i]->arm = wn_arming_slice(arm, s0, h->chain_first[i + 1] - h->chain_first[i], a->num_samples);
             if (i == 0 && h->prof_items > 0) { h->chains[0]->prof_items = h->prof_items; h->prof_items = 0; }
             rc = wn_generate(h->chains[i], &b);
             if (rc) {
@@ -969,8 +702,6 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
         h->t_base = h->chains[0]->t_base;
         return WN_OK;
     }
-    if (a->n_given < 1 || a->num_samples < 0) return wn_fail(WN_E_BADARG, "wn_generate: n_given must be >= 1 and num_samples >= 0");
-    if (!a->first_samples) return wn_fail(WN_E_BADARG, "wn_generate: first_samples is NULL");
     if (a->num_samples > 0 && !a->out_idx) return wn_fail(WN_E_BADARG, "wn_generate: out_idx is NULL");
     if (a->flags != 0 || a->reserved != 0) return wn_fail(WN_E_BADARG, "wn_generate: flags/reserved must be 0");
     const bool greedy = (!(a->temperature > 0.f) && !a->stream_temperatures) || a->uniforms == nullptr;
@@ -985,8 +716,8 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     r.first = a->first_samples; r.n_given = a->n_given; r.num_samples = a->num_samples; r.n_eval = n_eval;
     r.t_base = h->t_base; r.temperature = a->temperature; r.greedy = greedy ? 1 : 0; r.reg = a->regularizer;
     r.uniforms = a->uniforms; r.out_idx = a->out_idx; r.dbg_logits = a->dbg_logits; r.stream_temps = a->stream_temperatures;
-    if (forced_in && a->num_samples > 0) r.logp |= WN_RUN_FORCED;   // (its pointer travels behind xcc_tab; the forced fork lives where the log-probabilities live)
-    r.logp |= logp_out ? 1 + logp_mode : 0;   // (the pointer travels in status[6..7], below; an armed job, a greedy one too, runs the instantiation that carries the log-probabilities: wn_chain_launch)
+    if (arm.forced_in && a->num_samples > 0) r.logp |= WN_RUN_FORCED;   // (its pointer travels behind xcc_tab; the forced fork lives where the log-probabilities live)
+    r.logp |= arm.logp_out ? 1 + arm.logp_mode : 0;   // (the pointer travels in status[6..7], below; an armed job, a greedy one too, runs the extras slot: wn_job_slot)
     if (!greedy) {   // (nothing is drawn in a greedy job: no filter applies to it, and unarmed it runs the kernel it always ran)
         r.top_k = h->smp_top_k < h->plan.C ? h->smp_top_k : 0;
         r.top_p = h->smp_top_p < 1.f ? h->smp_top_p : 0.f;
@@ -1043,19 +774,11 @@ extern "C" int wn_generate(wn_handle* h, const wn_generate_args* a) {
     // hand-off words restart at tag 1 every call: zero them (and the status word) ahead of the launch
     int rc = rt_memset_async(h->d_gran, 0, h->gran_count * 8, a->hip_stream);
     rc = rc ? rc : rt_memset_async(h->d_status, 0, (size_t)WN_STATUS_WORDS(h->plan.n_wg) * 4, a->hip_stream);   // (the whole block: no pointer of an earlier armed job stays in its tail)
-    if (!rc && logp_out) {   // the log-probability output pointer, behind the memset: two 32-bit fills, no host buffer to keep alive (wn_logp_out, wn_kernel.h)
-        const unsigned long long bits = (unsigned long long)(uintptr_t)logp_out;
-        rc = rt_hip(hipMemsetD32Async((hipDeviceptr_t)(h->d_status + 6), (int)(uint32_t)bits, 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
-        rc = rc ? rc : rt_hip(hipMemsetD32Async((hipDeviceptr_t)(h->d_status + 7), (int)(uint32_t)(bits >> 32), 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
-    }
-    if (!rc && (r.logp & WN_RUN_FORCED)) {   // the forced samples' pointer, likewise (wn_forced_in, wn_kernel.h)
-        const unsigned long long bits = (unsigned long long)(uintptr_t)forced_in;
-        uint32_t* at = h->d_status + WN_STATUS_FORCED(h->plan.n_wg);
-        rc = rt_hip(hipMemsetD32Async((hipDeviceptr_t)at, (int)(uint32_t)bits, 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
-        rc = rc ? rc : rt_hip(hipMemsetD32Async((hipDeviceptr_t)(at + 1), (int)(uint32_t)(bits >> 32), 1, (hipStream_t)a->hip_stream), "hipMemsetD32Async");
-    }
+    if (!rc && arm.logp_out) rc = wn_publish_ptr(h->d_status + 6, arm.logp_out, a->hip_stream);   // (wn_logp_out, wn_kernel.h)
+    if (!rc && (r.logp & WN_RUN_FORCED)) rc = wn_publish_ptr(h->d_status + WN_STATUS_FORCED(h->plan.n_wg), arm.forced_in, a->hip_stream);   // (wn_forced_in, wn_kernel.h)
     if (rc) { wn_gate_release(h->gate); h->gate.reset(); return rc; }
-    wn_chain_launch(h, (hipStream_t)a->hip_stream, r);
+    void* args[] = {&h->plan, &r};   // the ONE launch of a chain kernel: the slot of what the job needs
+    (void)hipLaunchKernel(h->kern[wn_job_slot(r)], dim3(h->plan.n_blocks), dim3(h->threads), args, (size_t)h->lds_bytes, (hipStream_t)a->hip_stream);
     rc = rt_hip(hipGetLastError(), "launch wn_generate_kernel");
     if (rc) { wn_gate_release(h->gate); h->gate.reset(); return rc; }
     if (h->gate) {   // the booking goes back the moment the kernel is done (a caller that never waits must not keep the device closed)
@@ -1209,7 +932,7 @@ extern "C" int wn_set_logprob_output(wn_handle* h, float* logp, int64_t capacity
     if (mode != WN_LOGP_SAMPLING && mode != WN_LOGP_MODEL)
         return wn_fail(WN_E_BADARG, "wn_set_logprob_output: mode must be WN_LOGP_SAMPLING (0) or WN_LOGP_MODEL (1), got %d", (int)mode);
     if (!h) return wn_fail(WN_E_BADARG, "wn_set_logprob_output: NULL handle");   // (behind the value checks: those are testable without a device)
-    h->logp_out = logp; h->logp_capacity = logp ? capacity : 0; h->logp_mode = logp ? mode : 0;
+    h->arm.logp_out = logp; h->arm.logp_capacity = logp ? capacity : 0; h->arm.logp_mode = logp ? mode : 0;
     return WN_OK;
 }
 
@@ -1218,7 +941,7 @@ extern "C" int wn_set_forced_samples(wn_handle* h, const int32_t* forced, int64_
     g_err[0] = 0;
     if (capacity < 0) return wn_fail(WN_E_BADARG, "wn_set_forced_samples: capacity must be >= 0, got %lld", (long long)capacity);
     if (!h) return wn_fail(WN_E_BADARG, "wn_set_forced_samples: NULL handle");   // (behind the value check: that one is testable without a device)
-    h->forced_in = forced; h->forced_capacity = forced ? capacity : 0;
+    h->arm.forced_in = forced; h->arm.forced_capacity = forced ? capacity : 0;
     return WN_OK;
 }
 

@@ -1,5 +1,5 @@
-// wn_stacked.hip -- translation unit of the stacked-layer generation kernels (variant 4, wn_kernel_v4.h): their instantiations, the host-side
-// packers of their per-lane weight images and their launchers, behind wn_v4_table() (wn_stacked_table.h: why this is a unit of its own).
+// wn_stacked.hip -- translation unit of the stacked-layer generation kernels (variant 4, wn_kernel_v4.h): their instantiations and the host-side
+// packers of their per-lane weight images, behind wn_v4_kernels() (wn_stacked_table.h: why this is a unit of its own).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -69,42 +69,13 @@ static void wn_pack_v4(const WnPlan& pl, const WnHostWeights& w, std::vector<flo
     }
 }
 
-template <int R, int D, int S, int EC, int LPW>
-static WnV4Entry wn_v4_entry() {
-    using V = WnV4Shape<R, D, S>;
-    using SH = WnV2Shape<R, D, S, EC>;
-    WnV4Entry e;
-    e.R = R; e.D = D; e.S = S; e.EC = EC; e.LPW = LPW; e.nwpl = V::NWPL; e.nwh = SH::NWH;
-    e.pack = wn_pack_v4<R, D, S, EC, LPW>;
-    e.fn = (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW, false>;
-    e.fn_diag = (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW, true>;
-    e.lds_pre_head = WnV3Lds<SH, 1>::pre;
-    e.lds_floats = [](int ns) {
-        int need = WnV4Lds<V, LPW>::floats(ns);
-        const int head = WnV3Lds<SH, 1>::pre + (SH::K3 > 100 ? SH::K3 : EC) * 256;   // the head lanes' LDS-resident weights (wn_v3_head)
-        const int smp = WnV3Lds<SH, 1>::pre + 256 * R;                               // start_conv^T in the sampler workgroups
-        if (head > need) need = head;
-        if (smp * 4 <= WN_LDS_MAX_BYTES && smp > need) need = smp;
-        return need;
-    };
-    e.launch = [](bool diag, int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
-        if (diag) hipLaunchKernelGGL((wn_generate_kernel_v4<R, D, S, EC, LPW, true>), dim3(grid), dim3(WN_THREADS_V4), lds, st, p, r);
-        else hipLaunchKernelGGL((wn_generate_kernel_v4<R, D, S, EC, LPW, false>), dim3(grid), dim3(WN_THREADS_V4), lds, st, p, r);
-    };
-    return e;
-}
-
-const std::vector<WnV4Entry>& wn_v4_table() {
-    static const std::vector<WnV4Entry> t = {
-        wn_v4_entry<64, 64, 256, 64, 3>(),     // cfg2 (BASELINE configs[1]): 10 stack workgroups
-        wn_v4_entry<32, 32, 256, 64, 5>(),     // cfg1 (configs[0]): 2
-        wn_v4_entry<32, 32, 1024, 32, 2>(),    // train_script.py:17-25, the reference's only trained model shape: 15
-    };
+const std::vector<WnV4Kernels>& wn_v4_kernels() {
+#define WN_X(R, D, S, EC, LPW) \
+    WnV4Kernels{wn_pack_v4<R, D, S, EC, LPW>, (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW, false>, (const void*)wn_generate_kernel_v4<R, D, S, EC, LPW, true>},
+    static const std::vector<WnV4Kernels> t = {WN_V4_SHAPES(WN_X)};
+#undef WN_X
     return t;
 }
 
 // the slot re-use form of cfg3 with the sampling filters (wn_stacked_table.h: why it is compiled in this unit)
 const void* wn_v3_cfg3_slots_filter_fn() { return (const void*)wn_generate_kernel_v3m_filter<128, 32, 512, 32, 4, 2, 4>; }
-void wn_v3_cfg3_slots_filter_launch(int grid, size_t lds, hipStream_t st, const WnPlan& p, const WnRun& r) {
-    hipLaunchKernelGGL((wn_generate_kernel_v3m_filter<128, 32, 512, 32, 4, 2, 4>), dim3(grid), dim3(WN_THREADS_V3), lds, st, p, r);
-}

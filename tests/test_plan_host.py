@@ -12,6 +12,7 @@ CSRC = os.path.join(ROOT, "pytorch-wavenet_amd", "csrc")
 
 HARNESS = r"""
 #include "wn_plan.h"
+#include "wn_chain_shapes.h"
 #include <cstdio>
 #include <cstdlib>
 int main(int argc, char** argv) {
@@ -42,12 +43,12 @@ int main(int argc, char** argv) {
         return 0;
     }
     if (argc >= 2 && argv[1][0] == 'p') {  // p <R> <D> <S> <E> <n_layers> [max_workgroups]: the compiled shape a model is zero-padded into
-        const WnShapeRow rows[] = {{128, 32, 512, 32, 4}, {64, 64, 256, 64, 1}, {32, 32, 256, 64, 1}, {32, 16, 1024, 32, 2}, {64, 32, 256, 64, 2},
-                                   {16, 16, 256, 32, 1}, {16, 16, 256, 32, 2}};   // csrc/wn_runtime.hip: wn_v2_table()
+#define ROW(R, DC, S, EC, PM, SK) {R, DC, S, EC, PM},
+        const WnShapeRow rows[] = {WN_V3_SHAPES(ROW)};   // the real list: csrc/wn_chain_shapes.h
         const int NL = atoi(argv[6]), cap = argc > 7 ? atoi(argv[7]) : 252;
         int out[4] = {0, 0, 0, 0};
-        const int pick = wn_pad_pick(rows, 7, atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), NL,
-                                     [&](int R2, int D2, int S2, int E2) {   // (stand-in for wn_v3_applicable: the chain must fit the CUs)
+        const int pick = wn_pad_pick(rows, (int)(sizeof(rows) / sizeof(rows[0])), atoi(argv[2]), atoi(argv[3]), atoi(argv[4]), atoi(argv[5]), NL,
+                                     [&](int R2, int D2, int S2, int E2) {   // (stand-in for wn_v3_pick: the chain must fit the CUs)
                                          for (const WnShapeRow& e : rows)
                                              if (e.R == R2 && e.S == S2 && e.DC * e.Pm == D2 && E2 % e.EC == 0) return NL * e.Pm + E2 / e.EC <= cap;
                                          return false;
