@@ -20,6 +20,26 @@ def regularizer_array(classes, regularize):
     return (r.squeeze() * regularize).numpy().astype(np.float32)
 
 
+def checked_forced(forced, num_samples, classes, rows=None):
+    """The ``forced`` argument of Engine.generate and of the facade (generate_fast, generate_fast_streams), checked in this one place: None, or
+    integers shaped like the audio -- (num_samples,) or (streams, num_samples) -- in [-1, classes), -1 being a free position; ValueError for anything
+    else.  rows=None -> an int32 array of the shape given.  rows=n: a 2-D array must have n rows, a 1-D one is shared by them -> a writable C-ordered
+    int32 (n, num_samples) copy."""
+    if forced is None:
+        return None
+    if num_samples < 1:
+        raise ValueError("forced: the job generates no sample")
+    f = np.asarray(forced.detach().cpu() if hasattr(forced, "detach") else forced)
+    if f.dtype.kind not in "iu" or f.ndim not in (1, 2) or f.shape[-1] != num_samples or (f.ndim == 2 and rows is not None and f.shape[0] != rows):
+        raise ValueError("forced must be an integer array shaped like the audio, (%d,) or (%s, %d); got %s %r" % (
+            num_samples, "streams" if rows is None else rows, num_samples, f.dtype, f.shape))
+    if f.min() < -1 or f.max() >= classes:
+        raise ValueError("forced outside [-1, classes): -1 is a free position, 0 .. classes - 1 a forced class")
+    if rows is None:
+        return f.astype(np.int32)
+    return np.array(np.broadcast_to(f.reshape(-1, num_samples), (rows, num_samples)), dtype=np.int32, order="C")
+
+
 class _TorchMem:
     """Device memory, streams and transfers through PyTorch-ROCm (the memory provider of every product Engine)."""
     def __init__(self, device_index):
@@ -91,6 +111,13 @@ class Engine:
             pass
 
     # -- ABI calls
+    def _need(self, symbol, since):
+        """The optional export ``symbol`` (_abi.OPTIONAL_EXPORTS), or the one error for a library built before ``since``."""
+        if not self.lib.has(symbol):
+            raise RuntimeError("mi355_wavenet: %s does not export %s (a library built before %s): rebuild it with pytorch-wavenet_amd/build.py"
+                               % (self.lib.path, symbol, since))
+        return getattr(self.lib.dll, symbol)
+
     def load_weights(self, weights):
         st = params.stacked(weights, self.cfg)   # (host arrays, alive until wn_load_weights has copied them)
         w = _abi.wn_weight_ptrs(*[st[n].ctypes.data if n in st else None for n in _abi.WEIGHT_FIELDS])
@@ -131,12 +158,9 @@ class Engine:
             raise ValueError("top_k must be >= 0 (0 and >= classes: off), got %d" % top_k)
         if not (0.0 <= top_p <= 1.0):
             raise ValueError("top_p must lie in [0, 1] (0 and 1: off), got %r" % top_p)
-        if not self.lib.has("wn_set_sampling"):
-            if top_k == 0 and top_p == 0.0:
-                return   # nothing was ever set on such a library
-            raise RuntimeError("mi355_wavenet: %s does not export wn_set_sampling (a library built before the sampling filters were added): "
-                               "rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
-        self.lib.check(self.lib.dll.wn_set_sampling(self._h, top_k, top_p))
+        if top_k == 0 and top_p == 0.0 and not self.lib.has("wn_set_sampling"):
+            return   # nothing was ever set on such a library
+        self.lib.check(self._need("wn_set_sampling", "the sampling filters were added")(self._h, top_k, top_p))
         self._sampling = (top_k, top_p)
 
     def forward_indices(self, indices, output_length):
@@ -154,9 +178,7 @@ class Engine:
         'sums' (float64 (3,) device tensor: sum of the rows' negative log-likelihoods in nats, rows whose argmax equals the target, rows counted)
         and, on request, 'row_nll' float32 / 'row_pred' int32 of shape (N, output_length).  A target outside [0, classes) gives a NaN row_nll and
         leaves the row out of the sums.  Device tensors, asynchronous: nothing is synchronised here."""
-        if not self.lib.has("wn_score"):
-            raise RuntimeError("mi355_wavenet: %s does not export wn_score (a library built before teacher-forced scoring was added): "
-                               "rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
+        score = self._need("wn_score", "teacher-forced scoring was added")
         import torch
         idx = torch.as_tensor(indices).to(self.mem.device, torch.int32).contiguous()
         N, L = idx.shape
@@ -167,8 +189,8 @@ class Engine:
         sums = torch.empty(3, dtype=torch.float64, device=self.mem.device)
         rows = torch.empty(N, int(output_length), dtype=torch.float32, device=self.mem.device) if want_rows else None
         pred = torch.empty(N, int(output_length), dtype=torch.int32, device=self.mem.device) if want_pred else None
-        self.lib.check(self.lib.dll.wn_score(self._h, idx.data_ptr(), tgt.data_ptr(), N, L, int(output_length), self.mem.ptr(rows), self.mem.ptr(pred),
-                                             sums.data_ptr(), self.mem.stream()))
+        self.lib.check(score(self._h, idx.data_ptr(), tgt.data_ptr(), N, L, int(output_length), self.mem.ptr(rows), self.mem.ptr(pred), sums.data_ptr(),
+                             self.mem.stream()))
         return {"sums": sums, "row_nll": rows, "row_pred": pred}
 
     def profile_next(self, n_items):
@@ -190,38 +212,16 @@ class Engine:
         -- of the step's own logits.  logp_dev None disarms.  A library without the symbol raises."""
         if mode not in self.LOGPROB_MODES:
             raise ValueError('logprobs must be "sampling" or "model", got %r' % (mode,))
-        if not self.lib.has("wn_set_logprob_output"):
-            raise RuntimeError("mi355_wavenet: %s does not export wn_set_logprob_output (a library built before the per-sample log-probabilities were "
-                               "added): rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
-        self.lib.check(self.lib.dll.wn_set_logprob_output(self._h, self.mem.ptr(logp_dev), int(capacity), self.LOGPROB_MODES[mode]))
+        arm = self._need("wn_set_logprob_output", "the per-sample log-probabilities were added")
+        self.lib.check(arm(self._h, self.mem.ptr(logp_dev), int(capacity), self.LOGPROB_MODES[mode]))
 
-    def _need_forced(self):
-        if not self.lib.has("wn_set_forced_samples"):
-            raise RuntimeError("mi355_wavenet: %s does not export wn_set_forced_samples (a library built before forced samples were added): "
-                               "rebuild it with pytorch-wavenet_amd/build.py" % self.lib.path)
+    _FORCED = ("wn_set_forced_samples", "forced samples were added")   # _need()'s arguments
 
     def set_forced_samples(self, forced_dev, capacity):
         """Arms the NEXT job alone to read forced samples from forced_dev, int32 (n_streams, num_samples) on the device: a value in [0, classes) is what
         the stream emits at that position, anything else (canonically -1) leaves the draw alone (C ABI wn_set_forced_samples; the contract is in
         include/wn_abi.h).  forced_dev None disarms.  A library without the symbol raises."""
-        self._need_forced()
-        self.lib.check(self.lib.dll.wn_set_forced_samples(self._h, self.mem.ptr(forced_dev), int(capacity)))
-
-    def _forced_array(self, forced, num_samples):
-        """generate()'s ``forced`` as int32 (n_streams, num_samples), -1 = free; ValueError for anything else"""
-        ns, C = self.n_streams, self.classes
-        if num_samples < 1:
-            raise ValueError("forced: the job generates no sample")
-        f = np.asarray(forced)
-        if f.dtype.kind not in "iu":
-            raise ValueError("forced must be an integer array, got dtype %s" % f.dtype)
-        if f.ndim == 1:
-            f = np.broadcast_to(f[None, :], (ns, f.shape[0]))
-        if f.shape != (ns, num_samples):
-            raise ValueError("forced has shape %r, the job needs %r (or (%d,))" % (np.shape(forced), (ns, num_samples), num_samples))
-        if f.min() < -1 or f.max() >= C:
-            raise ValueError("forced outside [-1, classes): -1 is a free position, 0 .. classes - 1 a forced class")
-        return np.array(f, dtype=np.int32, order="C")   # (a copy: the broadcast view is read-only)
+        self.lib.check(self._need(*self._FORCED)(self._h, self.mem.ptr(forced_dev), int(capacity)))
 
     def launch(self, first_dev, n_given, num_samples, temperature, reg_dev, uni_dev, out_dev, logits_dev, timeout_ms=0,
                temps_dev=None):
@@ -255,22 +255,18 @@ class Engine:
         return self.prime(self.mem.upload(fs), fs.shape[1], fs.shape[1])
 
     # -- the generation state as data (include/wn_abi.h: wn_state_*; mi355_wavenet/state.py holds it on the host)
-    def _need(self, symbol):
-        if not self.lib.has(symbol):
-            raise RuntimeError("mi355_wavenet: %s does not export %s (a library built before the generation state could be saved and loaded): "
-                               "rebuild it with pytorch-wavenet_amd/build.py" % (self.lib.path, symbol))
-        return getattr(self.lib.dll, symbol)
+    _STATE_SINCE = "the generation state could be saved and loaded"
 
     def state_floats(self):
         """float32 values of ONE stream's canonical state: the caller's residual channels x the sum of the layers' queue lengths."""
         n = ctypes.c_int64()
-        self.lib.check(self._need("wn_state_floats")(self._h, ctypes.byref(n)))
+        self.lib.check(self._need("wn_state_floats", self._STATE_SINCE)(self._h, ctypes.byref(n)))
         return int(n.value)
 
     def state_save(self, stream=0):
         """The canonical, time-free state of one stream's dilation queues: float32 ndarray (state_floats(),) -- per layer (k-1)d+1 rows of R values,
         oldest first (wn_state_save).  Waits for the job in flight."""
-        save = self._need("wn_state_save")
+        save = self._need("wn_state_save", self._STATE_SINCE)
         dev = self.mem.empty((self.state_floats(),), np.float32)
         self.lib.check(save(self._h, int(stream), self.mem.ptr(dev), self.mem.stream()))
         return np.ascontiguousarray(self.mem.download(dev), dtype=np.float32)
@@ -278,7 +274,7 @@ class Engine:
     def state_load(self, state, stream_first=0, stream_count=None):
         """Writes ONE canonical state into every stream of [stream_first, stream_first + stream_count) (default: up to the last stream), at the
         engine's present queue time, which it leaves alone (wn_state_load).  The other streams keep their queues."""
-        load = self._need("wn_state_load")
+        load = self._need("wn_state_load", self._STATE_SINCE)
         a = np.ascontiguousarray(np.asarray(state), dtype=np.float32).reshape(-1)
         if a.size != self.state_floats():
             raise ValueError("the state holds %d values, this engine's streams hold %d" % (a.size, self.state_floats()))
@@ -290,7 +286,7 @@ class Engine:
     def prime_shared(self, first_row):
         """prime() for a prompt every stream shares: ONE row of teacher-forced class indices, the stack's products once, the result into every
         stream's queues (wn_prime_shared).  Returns False when the engine cannot (wn_prime's shape limits)."""
-        prime = self._need("wn_prime_shared")
+        prime = self._need("wn_prime_shared", self._STATE_SINCE)
         row = np.ascontiguousarray(np.asarray(first_row), dtype=np.int32).reshape(-1)
         if row.size and (row.min() < 0 or row.max() >= self.classes):
             raise ValueError("first_samples outside [0, classes)")
@@ -333,8 +329,8 @@ class Engine:
         if logprobs is not None and logprobs not in self.LOGPROB_MODES:
             raise ValueError('logprobs must be None, "sampling" or "model", got %r' % (logprobs,))
         if forced is not None:
-            forced = self._forced_array(forced, num_samples)
-            self._need_forced()   # (before anything is reset or enqueued)
+            forced = checked_forced(forced, num_samples, C, rows=ns)
+            self._need(*self._FORCED)   # (before anything is reset or enqueued)
         if top_k is not None or top_p is not None:
             self.set_sampling(self._sampling[0] if top_k is None else top_k, self._sampling[1] if top_p is None else top_p)
         if first_samples is None:

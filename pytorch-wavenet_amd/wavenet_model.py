@@ -6,8 +6,10 @@
 What is different underneath:
   * ``generate_fast()`` does not run the Python per-sample loop.  It hands the whole job to the MI355X
     engine (mi355_wavenet.engine -> C ABI include/wn_abi.h -> HIP kernels csrc/wn_kernel_v3.h / wn_kernel.h): one persistent
-    kernel launch per call (per progress interval when a callback is given).  There is NO CPU fallback: without
-    a gfx950 GPU and the built library it raises.
+    kernel launch per call (per progress interval when a callback is given).  Where the job is cut into such pieces, and what runs between
+    them (callbacks, the timing print, the draws), is decided by mi355_wavenet/generation.py: generation_schedule plans, pure; run_schedule
+    executes.  generate_fast, generate_fast_streams and score_continuation share one prologue and one epilogue (see _finish).  There is NO CPU
+    fallback: without a gfx950 GPU and the built library it raises.
   * the global numpy RNG is consumed exactly as the reference does (one ``random_sample`` per generated
     sample when ``temperature > 0``: ``np.random.choice``, wavenet_model.py:288) -- the draws are made on the
     host and shipped to the kernel, which performs the same float64 inverse-CDF lookup.
@@ -21,6 +23,7 @@ What is different underneath:
     multiples of 32 run natively, zero-padded: with and, since round 6, under autograd), and the input lengths for which the reference itself has no defined result (its error, or its shapes, are reproduced).
 """
 import collections
+import contextlib
 import itertools
 import os
 import os.path
@@ -453,18 +456,10 @@ class WaveNetModel(nn.Module):
         state like a drawn one and gets its log-probability like one; its uniform is drawn and not used, so the RNG's consumption, the callbacks and the
         timing print are those of the call without it.  Ragged prompts: the common prefix as first_samples, the rest of each prompt as a forced prefix."""
         logprobs = self._logprob_mode(return_logprobs)
-        forced = self._forced_arg(forced, num_samples)
-        states = None
-        if continue_from is not None:
-            if first_samples is not None:
-                raise ValueError("generate_fast: continue_from carries the next input (last_index); first_samples must not be given with it")
-            states, first_samples = self._continue_states(continue_from)
-        try:
-            return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                                       states, return_state, logprobs, forced)
-        finally:   # (also when a callback raised between two pieces)
-            if (top_k or top_p) and self._wn_engine is not None:
-                self._wn_engine.set_sampling(0, 0.)
+        forced = self._checked_forced(forced, num_samples)
+        states, first_samples = self._continuation("generate_fast", continue_from, first_samples)
+        return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
+                                   states, return_state, logprobs, forced)
 
     @staticmethod
     def _logprob_mode(return_logprobs):
@@ -477,19 +472,19 @@ class WaveNetModel(nn.Module):
             return return_logprobs
         raise ValueError('return_logprobs must be False, True, "sampling" or "model", got %r' % (return_logprobs,))
 
-    def _forced_arg(self, forced, num_samples):
-        """forced of the facade -> None or an int32 array (num_samples,) / (rows, num_samples) with values in [-1, classes); ValueError otherwise"""
-        if forced is None:
-            return None
-        f = forced.detach().cpu().numpy() if torch.is_tensor(forced) else np.asarray(forced)
-        if f.dtype.kind not in "iu" or f.ndim not in (1, 2) or f.shape[-1] != num_samples or num_samples < 1:
-            raise ValueError("forced must be an integer array shaped like the audio, (%d,) or (streams, %d); got %s %r" % (num_samples, num_samples, f.dtype, f.shape))
-        if f.min() < -1 or f.max() >= self.classes:
-            raise ValueError("forced outside [-1, classes): -1 is a free position, 0 .. classes - 1 a forced class")
-        return f.astype(np.int32)
+    # ---- what generate_fast, generate_fast_streams and score_continuation share: the prologue (arguments -> checked `forced`, states, prompt: every
+    #      argument error before an engine is touched), the filter around the job, and the epilogue (_finish)
+    def _checked_forced(self, forced, num_samples, rows=None):
+        from mi355_wavenet import engine
+        return engine.checked_forced(forced, num_samples, self.classes, rows)
 
-    def _continue_states(self, continue_from):
-        """-> (the states as a list, checked against this model; the first_samples that stand for them: 1-D for a single state, else 2-D)"""
+    def _continuation(self, caller, continue_from, first_samples):
+        """-> (None, first_samples) without continue_from; else (the states as a list, checked against this model; the first_samples that stand for
+        them: 1-D for a single state, else 2-D) -- continue_from and first_samples exclude each other"""
+        if continue_from is None:
+            return None, first_samples
+        if first_samples is not None:
+            raise ValueError("%s: continue_from carries the next input (last_index); first_samples must not be given with it" % caller)
         from mi355_wavenet.state import GenerationState
         single = isinstance(continue_from, GenerationState)
         states = [continue_from] if single else list(continue_from)
@@ -505,124 +500,67 @@ class WaveNetModel(nn.Module):
         return GenerationState(eng.state_save(stream), last_index, evals, layers=self.layers, blocks=self.blocks, residual_channels=self.residual_channels,
                                kernel_size=self.kernel_size, classes=self.classes)
 
-    def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                       states=None, return_state=False, logprobs=None, forced=None, timing_print=True):
-        self.eval()
+    def _prompt(self, first_samples):
+        """first_samples (None: the one sample classes // 2, wavenet_model.py:245-247) -> (int64 (n_streams, num_given), whether it came as 2-D rows)"""
         if first_samples is None:
             first_samples = torch.LongTensor(1).zero_() + (self.classes // 2)
         first = torch.as_tensor(first_samples).detach().cpu().numpy().astype(np.int64)
-        batched = first.ndim == 2
-        first = first.reshape(first.shape[0], -1) if batched else first.reshape(1, -1)
+        return first.reshape(first.shape[0] if first.ndim == 2 else 1, -1), first.ndim == 2
+
+    @contextlib.contextmanager
+    def _sampling_filter(self, eng, top_k, top_p):
+        """top_k / top_p on the engine's handle for the jobs inside (every piece carries it), off again behind them -- also when one raises"""
+        try:
+            if top_k or top_p:
+                eng.set_sampling(top_k, top_p)
+            yield
+        finally:
+            if top_k or top_p:
+                eng.set_sampling(0, 0.)
+
+    def _finish(self, eng, idx, logp, squeeze=False, stream=0, state=None):
+        """The engine's class indices (n_streams, n) -> what the caller gets, audio[, logp][, state()] (a tuple as soon as there is more than the
+        audio; squeeze: the one row of a 1-D call), with model.dilated_queues deferred to ``stream``'s final state and the module back in train()
+        (wavenet_model.py:313)."""
+        self._defer_queues(eng, stream)
+        self.train()
+        result = [self._expand_indices(idx)] + ([logp] if logp is not None else [])  # :296, :314
+        if squeeze:
+            result = [r[0] for r in result]
+        if state is not None:
+            result.append(state())
+        return result[0] if len(result) == 1 else tuple(result)
+
+    def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
+                       states=None, return_state=False, logprobs=None, forced=None, timing_print=True):
+        """normalise, reset, load the states, prime, plan, execute, finish: where the job is cut into pieces and what runs between them is
+        mi355_wavenet/generation.py's"""
+        from mi355_wavenet import generation
+        self.eval()
+        first, batched = self._prompt(first_samples)
         n_streams, num_given = first.shape
-        total_samples = num_given + num_samples
-        if forced is not None:
-            if forced.ndim == 2 and forced.shape[0] != n_streams:
-                raise ValueError("forced has %d rows, the job has %d stream%s" % (forced.shape[0], n_streams, "" if n_streams == 1 else "s"))
-            forced = np.broadcast_to(forced.reshape(-1, num_samples), (n_streams, num_samples))
+        forced = self._checked_forced(forced, num_samples, rows=n_streams)
         for queue in self.dilated_queues:  # :250-251
             queue.reset()
         eng = self._engine(n_streams)
         eng.reset()
-        if states is not None:   # (queue time 0 again: the canonical form does not depend on it)
-            for s, st in enumerate(states):
-                eng.state_load(st.state, s, 1)
-        if top_k or top_p:
-            eng.set_sampling(top_k, top_p)   # (handle state: every piece below carries it)
-        sampled = temperature > 0
+        for s, st in enumerate(states or ()):   # (queue time 0 again: the canonical form does not depend on it)
+            eng.state_load(st.state, s, 1)
+        with self._sampling_filter(eng, top_k, top_p):
+            # priming (:259-269): all n_prime teacher-forced evaluations as ONE batched pass over the given window (C ABI wn_prime: the stack as
+            # matrix-core GEMMs over all positions, queues filled from the result); shapes it does not cover take the per-sample chain
+            n_prime = num_given - 1
+            primed = n_prime if n_prime >= eng.PRIME_BATCH_MIN and eng.prime_host(first[:, :n_prime]) else 0
+            self._wn_last_prime_batched = primed > 0
+            steps = generation.generation_schedule(num_given, num_samples, progress_interval, progress_callback is not None, primed, temperature > 0)
+            idx, logp = generation.run_schedule(steps, eng, first, temperature, regularize, forced, logprobs, progress_callback, timing_print)
 
-        # The job is evaluations ev = 0 .. n_eval-1 (num_given-1 priming + num_samples generating).
-        #   priming (:259-269): all n_prime teacher-forced evaluations run as ONE batched pass over the given window
-        #     (C ABI wn_prime: the stack as matrix-core GEMMs over all positions, queues filled from the result), then the
-        #     callbacks the reference would have fired at i % interval == 0 are delivered in order; shapes the batched
-        #     pass does not cover take the per-sample chain (WN_E_UNSUPPORTED), cut at the callbacks like below.
-        #   generating (:276-311): one persistent launch per piece, cut where the reference would have called back
-        #     ((i + num_given) % interval == 0, :308-311) or printed its timing line (after generating step 99, :304-306).
-        n_prime = num_given - 1
-        n_eval = n_prime + num_samples
-        a = 0
-        primed_upto = 0  # priming evaluations whose callbacks were already delivered (batched priming)
-        if n_prime >= eng.PRIME_BATCH_MIN and eng.prime_host(first[:, :n_prime]):
-            a = primed_upto = n_prime
-            if progress_callback is not None:
-                for i in range(0, n_prime, progress_interval):
-                    progress_callback(i, total_samples)
-        self._wn_last_prime_batched = a > 0
-        cuts = {n_eval}
-        if n_prime > a:
-            cuts.add(n_prime)  # the generating loop (and the reference's stopwatch, :275) starts here
-        if num_samples >= 100:
-            cuts.add(n_prime + 100)
-        if progress_callback is not None:
-            cuts.update(i + 1 for i in range(a, n_prime) if i % progress_interval == 0)
-            cuts.update(n_prime + i + 1 for i in range(num_samples) if (i + num_given) % progress_interval == 0)
-        def callback_due(ev):  # the reference calls back after evaluation ev (:266-269, :308-311)
-            if progress_callback is None or ev < 0:
-                return False
-            if ev < n_prime:
-                return ev >= primed_upto and ev % progress_interval == 0
-            return (ev - n_prime + num_given) % progress_interval == 0
-
-        def n_generated(a0, b0):  # samples the piece [a0, b0) of evaluations generates
-            return (b0 - a0) - max(0, min(b0, n_prime) - a0)
-
-        pieces, logp_pieces = [], []
-        done = 0  # generated samples behind us: where the next piece's slice of `forced` starts
-        last = None
-        tic = time.time()
-        ends = sorted(c for c in cuts if c > a)
-        drawn = None  # the NEXT piece's uniforms, drawn and uploaded while the current piece's kernel ran
-        for k, b in enumerate(sorted(cuts)):
-            if b > a:
-                if a == n_prime:
-                    tic = time.time()  # :275
-                seg_prime = max(0, min(b, n_prime) - a)
-                n_new = (b - a) - seg_prime
-                head = first[:, a:a + seg_prime + 1] if a < num_given else last
-                # one uniform per generated sample from the GLOBAL numpy RNG, drawn right before the piece runs -- or, when nothing
-                # of the caller's runs between two pieces (no callback due at the cut: e.g. the cut behind generating step 99 that only
-                # exists for the reference's timing print), while the PREVIOUS piece's kernel runs: same draws, same order
-                u = drawn if drawn is not None else (np.random.random_sample((n_streams, n_new)) if (sampled and n_new > 0) else None)
-                drawn = None
-                nxt = [c for c in ends if c > b]
-                overlap = None
-                if sampled and nxt and not callback_due(b - 1) and n_generated(b, nxt[0]) > 0:
-                    def overlap(n_next=n_generated(b, nxt[0])):
-                        nonlocal drawn
-                        drawn = eng.upload_uniforms(np.random.random_sample((n_streams, n_next)))
-                out = eng.generate(n_new, head, temperature=temperature, regularize=regularize, uniforms=u, reset=False, while_running=overlap,
-                                   logprobs=logprobs if n_new > 0 else None,
-                                   forced=forced[:, done:done + n_new] if (forced is not None and n_new > 0) else None)
-                done += n_new
-                if n_new > 0 and logprobs is not None:
-                    out, lp = out
-                    logp_pieces.append(lp)
-                if n_new > 0:
-                    pieces.append(out)
-                    last = out[:, -1:].astype(np.int64)
-                a = b
-            ev = b - 1  # the evaluation that just finished
-            if ev < 0:
-                continue
-            if ev >= n_prime and ev - n_prime + 1 == 100 and timing_print:
-                toc = time.time()
-                print("one generating step does take approximately " + str((toc - tic) * 0.01) + " seconds)")
-            if callback_due(ev):  # (priming: not a second time after batched priming)
-                progress_callback(ev if ev < n_prime else ev - n_prime + num_given, total_samples)
-        idx = np.concatenate(pieces, axis=1) if pieces else np.zeros((n_streams, 0), dtype=np.int32)
-        self._defer_queues(eng)
-        self.train()
-        mu_gen = self._expand_indices(idx)  # :296, :314
-        audio = mu_gen if batched else mu_gen[0]
-        result = (audio,)
-        if logprobs is not None:   # (the pieces are concatenated like the indices)
-            logp = np.concatenate(logp_pieces, axis=1) if logp_pieces else np.zeros((n_streams, 0), dtype=np.float32)
-            result += (logp if batched else logp[0],)
-        if not return_state:
-            return result[0] if len(result) == 1 else result
-        nxt = idx[:, -1] if idx.shape[1] else first[:, -1]   # the input of the next step
-        before = [st.evals for st in states] if states is not None else [0] * n_streams
-        out = [self._stream_state(eng, s, int(nxt[s]), before[s] + n_eval) for s in range(n_streams)]
-        return result + (out if batched else out[0],)
+            def state():   # behind the last generated sample, whose index is the input of the next step
+                nxt = idx[:, -1] if idx.shape[1] else first[:, -1]
+                before = [st.evals for st in states] if states is not None else [0] * n_streams
+                out = [self._stream_state(eng, s, int(nxt[s]), before[s] + n_prime + num_samples) for s in range(n_streams)]
+                return out if batched else out[0]
+            return self._finish(eng, idx, logp, squeeze=not batched, state=state if return_state else None)
 
     def _expand_indices(self, idx):
         """Class indices -> float64 audio: ``o = idx / classes * 2 - 1`` (wavenet_model.py:296) then ``mu_law_expansion(o)``
@@ -671,47 +609,29 @@ class WaveNetModel(nn.Module):
         value of its argmax.
         forced as in generate_fast: (num_samples,) shared by all rows, or (len(temperatures), num_samples); -1 is a free position."""
         logprobs = self._logprob_mode(return_logprobs)
-        forced = self._forced_arg(forced, num_samples)
-        if forced is not None and forced.ndim == 2 and forced.shape[0] != len(temperatures):
-            raise ValueError("forced has %d rows for %d temperatures" % (forced.shape[0], len(temperatures)))
-        state = None
-        if continue_from is not None:
-            if first_samples is not None:
-                raise ValueError("generate_fast_streams: continue_from carries the next input (last_index); first_samples must not be given with it")
-            states, first_samples = self._continue_states(continue_from)
-            if len(states) != 1:
-                raise ValueError("generate_fast_streams: continue_from is ONE state that all temperatures share")
-            state = states[0]
+        self._checked_forced(forced, num_samples, rows=len(temperatures))   # (checked here, before an engine is touched; Engine.generate makes the rows)
+        states, first_samples = self._continuation("generate_fast_streams", continue_from, first_samples)
+        if states is not None and len(states) != 1:
+            raise ValueError("generate_fast_streams: continue_from is ONE state that all temperatures share")
         self.eval()
         temps = [float(t) for t in temperatures]
-        if first_samples is None:
-            first_samples = torch.LongTensor(1).zero_() + (self.classes // 2)
-        first = torch.as_tensor(first_samples).detach().cpu().numpy().astype(np.int64).reshape(1, -1)
-        first = np.repeat(first, len(temps), axis=0)
+        first = np.repeat(self._prompt(first_samples)[0].reshape(1, -1), len(temps), axis=0)
         for queue in self.dilated_queues:
             queue.reset()
         eng = self._engine(len(temps))
         uniforms = np.zeros((len(temps), num_samples), dtype=np.float64)
-        for k, t in enumerate(temps):
+        for k, t in enumerate(temps):   # row by row, sampled rows only: the draws of sequential calls
             if t > 0:
                 uniforms[k] = np.random.random_sample(num_samples)
-        if top_k or top_p:
-            eng.set_sampling(top_k, top_p)
-        try:
-            if state is not None:
+        with self._sampling_filter(eng, top_k, top_p):
+            if states is not None:
                 eng.reset()
-                eng.state_load(state.state)   # one state, every stream
-            idx = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
-                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=state is None,
-                               shared_prompt=self.SHARED_PRIME and state is None and eng.lib.has("wn_prime_shared"), logprobs=logprobs, forced=forced)
-            if logprobs is not None:
-                idx, logp = idx
-        finally:
-            if top_k or top_p:
-                eng.set_sampling(0, 0.)
-        self._defer_queues(eng, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
-        self.train()
-        return self._expand_indices(idx) if logprobs is None else (self._expand_indices(idx), logp)
+                eng.state_load(states[0].state)   # one state, every stream
+            out = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
+                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=states is None, logprobs=logprobs, forced=forced,
+                               shared_prompt=self.SHARED_PRIME and states is None and eng.lib.has("wn_prime_shared"))
+        idx, logp = out if logprobs is not None else (out, None)
+        return self._finish(eng, idx, logp, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
 
     def score_continuation(self, indices, continue_from=None, first_samples=None, return_state=False):
         """The model's log-likelihood of audio that CONTINUES a stream: float32 shaped like ``indices`` (class indices, 1-D or 2-D), entry g being
@@ -726,11 +646,8 @@ class WaveNetModel(nn.Module):
             raise ValueError("score_continuation: indices must be a non-empty integer array, 1-D or (streams, n); got %s %r" % (idx.dtype, idx.shape))
         if idx.min() < 0 or idx.max() >= self.classes:
             raise ValueError("score_continuation: indices outside [0, classes)")
-        states = None
-        if continue_from is not None:
-            if first_samples is not None:
-                raise ValueError("score_continuation: continue_from carries the next input (last_index); first_samples must not be given with it")
-            states, first_samples = self._continue_states(continue_from)
+        states, first_samples = self._continuation("score_continuation", continue_from, first_samples)
+        if states is not None:
             if first_samples.ndim != idx.ndim or (idx.ndim == 2 and len(states) != idx.shape[0]):
                 raise ValueError("score_continuation: one GenerationState for 1-D indices, a list of one per row for 2-D indices")
         elif first_samples is not None and idx.ndim == 2:

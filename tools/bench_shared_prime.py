@@ -63,14 +63,14 @@ def main():
             if leg == "wn_prime":
                 took[leg] = _took(lambda: eng.lib.check(eng.lib.dll.wn_prime(eng._h, dev.data_ptr(), n, n, eng.mem.stream())))
             else:
-                prime_shared = eng._need("wn_prime_shared")   # (looked up and bound on first use: _abi.LAZY_EXPORTS)
+                prime_shared = eng._need("wn_prime_shared", eng._STATE_SINCE)   # (looked up and bound on first use: _abi.LAZY_EXPORTS)
                 took[leg] = _took(lambda: eng.lib.check(prime_shared(eng._h, dev.data_ptr(), n, eng.mem.stream())))
             eng.close()
             del dev
             torch.cuda.empty_cache()
         eng = engine.Engine(cfg, W, n_streams=ns)
         rows_dev, row_dev = eng.mem.upload(np.repeat(prompt[None, :n], ns, axis=0)), eng.mem.upload(prompt[:n])
-        dll, h, prime_shared = eng.lib.dll, eng._h, eng._need("wn_prime_shared")
+        dll, h, prime_shared = eng.lib.dll, eng._h, eng._need("wn_prime_shared", eng._STATE_SINCE)
 
         def per_stream():
             eng.reset()
