@@ -6,14 +6,19 @@
 // On 205 parameter tensors (config 5) torch runs this as ~130 multi-tensor launches per step.  Here it is a handful: the tensors'
 // pointers travel in the kernel arguments, up to WN_OPT_TENSORS per launch (no device-side tables to keep in step with gradients that
 // zero_grad(set_to_none=True) re-allocates every step): one pass for the sum of squares of all gradients, one pass that clips and steps.
-// The arithmetic is torch.optim.Adam's single-tensor formulas, operation for operation (torch/optim/adam.py, _single_tensor_adam):
-//     g      = grad * clip_coef                     clip_coef = min(1, max_norm / (total_norm + 1e-6))   (clip_grad_norm_)
-//     g     += weight_decay * p                      (weight_decay != 0)
-//     m      = m + (1 - beta1) * (g - m)             _foreach_lerp_(exp_avgs, grads, 1 - beta1)   [beta1 <= 0.5: g - (g - m) * beta1, ATen's other lerp branch]
-//     v      = v * beta2;  v = v + ((1 - beta2) * g) * g                     _foreach_mul_, _foreach_addcmul_
-//     denom  = sqrt(v) / sqrt(1 - beta2^t) + eps
-//     p      = p + (-(lr / (1 - beta1^t))) * (m / denom)                                           _foreach_addcdiv_
-// with every scalar formed in double (as Python does) and rounded to fp32 once, and the fp32 roundings pinned per torch kernel.
+// The arithmetic is torch.optim.Adam's on the device, rounding for rounding, in the multi-tensor (foreach) form that torch takes by default for
+// device parameters (torch/optim/adam.py, _multi_tensor_adam; tests/test_gpu_adam_kernels.py holds every output to torch's bits):
+//     g      = fl(grad * clip_coef)                  clip_coef = min(1, fl(fl(1 / fl(total_norm + 1e-6)) * max_norm))
+//                                                    (clip_grad_norm_: Python's scalar / tensor is Tensor.__rdiv__, reciprocal() * scalar)
+//     g      = fma(weight_decay, p, g)               (weight_decay != 0)                            _foreach_add_(grads, params, alpha)
+//     m      = fma(w, fl(g - m), m),  w = 1 - beta1  _foreach_lerp_   [w >= 0.5 in fp32: fma(-fl(g - m), fl(1 - w), g), ATen's other lerp branch]
+//     v      = fma(1 - beta2, fl(g * g), fl(v * beta2))                                             _foreach_mul_, _foreach_addcmul_: a + alpha * (b * c)
+//     denom  = fl(fl(sqrt(v) / sqrt(1 - beta2^t)) + eps)                                            _foreach_sqrt, _foreach_div_, _foreach_add_
+//     p      = fma(-(lr / (1 - beta1^t)), fl(m / denom), p)                                         _foreach_addcdiv_
+// with every scalar formed in double (as Python does) and rounded to fp32 once; sqrt and the divisions are the correctly rounded ones.  A
+// multiply-add INSIDE one torch kernel is one FMA in torch's build, every kernel's result is a rounded fp32.  torch's single-tensor form
+// (foreach=False) differs from this in ONE operation: there `tensor / python_scalar` is fl(sqrt(v) * fl32(1 / sqrt(1 - beta2^t))), the reciprocal
+// formed in double -- the two forms of torch disagree with each other in p (about one element in eight), so only one can be matched.
 // The clipped gradient is written back (clip_grad_norm_ works in place; loggers read .grad after the step).
 #ifndef WN_OPTIM_H
 #define WN_OPTIM_H
@@ -75,23 +80,27 @@ __global__ __launch_bounds__(256) void wn_opt_adam(WnOptBatch b, WnAdamScalars k
     float coef = 1.f;
     if (k.max_norm > 0.f) {
         const float total = (float)sqrt(*sumsq);
-        const float c = k.max_norm / (total + 1e-6f);
+        const float c = (1.f / (total + 1e-6f)) * k.max_norm;   // Python's max_norm / tensor is Tensor.__rdiv__: reciprocal() * max_norm (no multiply-add to fuse)
         coef = !(c >= 1.f) ? c : 1.f;   // torch.clamp(c, max=1.0): a NaN norm stays NaN and poisons every gradient, as clip_grad_norm_ does
         if (norm_out && blockIdx.x == 0 && threadIdx.x == 0) *norm_out = total;
     }
     float* p = b.p[t]; float* g = b.g[t]; float* m = b.m[t]; float* v = b.v[t];
-    // (each line is one of torch's foreach kernels; the intrinsics pin the roundings: every kernel's result is a rounded fp32, a multiply-add INSIDE one
-    //  kernel contracts to an FMA in torch's build as it does here)
+    // (each line is one of torch's foreach kernels.  Contraction is OFF in this block: __fmul_rn / __fadd_rn / __fsub_rn are plain operators in
+    //  this toolchain's headers, which the compiler would otherwise be free to fuse across torch's kernel boundaries -- g * coef into the lerp's
+    //  g - m, for one; the FMAs torch's kernels contain are written out.  __fsqrt_rn is the hardware's approximate root there: sqrtf is the
+    //  correctly rounded one.)
     auto one = [&](float pi, float gi, float& mi, float& vi, float& go) -> float {
-        gi = __fmul_rn(gi, coef);                                        // _foreach_mul_(grads, clip_coef)
+#pragma clang fp contract(off)
+        gi = gi * coef;                                                  // _foreach_mul_(grads, clip_coef)
         go = gi;
-        if (k.weight_decay != 0.f) gi = __fmaf_rn(k.weight_decay, pi, gi);  // _foreach_add(grads, params, alpha=weight_decay)
+        if (k.weight_decay != 0.f) gi = __builtin_fmaf(k.weight_decay, pi, gi);  // _foreach_add_(grads, params, alpha=weight_decay)
         // _foreach_lerp_(exp_avgs, grads, w = 1 - beta1): ATen's lerp is a + w * (b - a) for w < 0.5 and b - (b - a) * (1 - w) from 0.5 up
-        mi = k.lerp_hi ? __fmaf_rn(-__fsub_rn(gi, mi), __fsub_rn(1.f, k.one_minus_b1), gi) : __fmaf_rn(k.one_minus_b1, __fsub_rn(gi, mi), mi);
-        vi = __fmul_rn(vi, k.b2);                                        // _foreach_mul_(exp_avg_sqs, beta2)
-        vi = __fmaf_rn(__fmul_rn(k.one_minus_b2, gi), gi, vi);           // _foreach_addcmul_(exp_avg_sqs, grads, grads, 1 - beta2)
-        const float denom = __fadd_rn(__fdiv_rn(__fsqrt_rn(vi), k.sqrt_bc2), k.eps);   // sqrt, div by sqrt(1 - beta2^t), add eps
-        return __fmaf_rn(k.neg_step, __fdiv_rn(mi, denom), pi);          // _foreach_addcdiv_(params, exp_avgs, denom, -step_size)
+        const float d = gi - mi;
+        mi = k.lerp_hi ? __builtin_fmaf(-d, 1.f - k.one_minus_b1, gi) : __builtin_fmaf(k.one_minus_b1, d, mi);
+        vi = vi * k.b2;                                                  // _foreach_mul_(exp_avg_sqs, beta2)
+        vi = __builtin_fmaf(k.one_minus_b2, gi * gi, vi);                // _foreach_addcmul_(exp_avg_sqs, grads, grads, 1 - beta2): a + alpha * (b * c)
+        const float denom = sqrtf(vi) / k.sqrt_bc2 + k.eps;              // _foreach_sqrt, _foreach_div_(sqrt(1 - beta2^t)), _foreach_add_(eps)
+        return __builtin_fmaf(k.neg_step, mi / denom, pi);               // _foreach_addcdiv_(params, exp_avgs, denom, -step_size)
     };
     const bool vec = ((reinterpret_cast<uintptr_t>(p) | reinterpret_cast<uintptr_t>(g) | reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v)) & 15u) == 0 && i0 + WN_OPT_CHUNK <= n;
     if (vec) {

@@ -4,8 +4,10 @@ optimiser kernels (C ABI ``wn_adam_step``, csrc/wn_optim.h): the optimiser half 
 
 A torch.optim.Optimizer subclass with Adam's constructor and state layout (``state[p] = {"step", "exp_avg", "exp_avg_sq"}``, so
 ``state_dict()`` / ``load_state_dict()`` interchange with torch.optim.Adam), stepping ALL parameters of a group in a handful of launches
-(two per 48 tensors) instead of torch's ~130 multi-tensor launches on config 5's 205 parameters.  The update formulas are torch's, operation
-for operation; results agree with torch.optim.Adam to rounding (tests/test_gpu_training.py).  fp32 CUDA parameters only (anything else
+(two per 48 tensors) instead of torch's ~130 multi-tensor launches on config 5's 205 parameters.  The update is torch's, rounding for
+rounding: a step gives the bits of torch.optim.Adam's multi-tensor (foreach) form on the device, torch's default there, and clipping those of
+clip_grad_norm_ given the norm (tests/test_gpu_adam_kernels.py; torch's single-tensor form differs from its own foreach form in one operation,
+see csrc/wn_optim.h).  fp32 CUDA parameters only (anything else
 raises: no silent fallback); ``amsgrad`` / ``maximize`` / ``capturable`` are not offered.
 """
 import ctypes

@@ -62,13 +62,25 @@ class Harness:
             fn.argtypes = args
             fn.restype = None if name == "kh_tn_grid" else _I
         self.dll.kh_release.restype = None
+        # the product's own exports (the harness includes the runtime unit whole): the fused Adam step, called with a wn_adam_args the test fills
+        self.dll.wn_adam_step.argtypes = [_P]
+        self.dll.wn_adam_step.restype = _I
+        self.dll.wn_last_error.argtypes = []
+        self.dll.wn_last_error.restype = ctypes.c_char_p
         assert self.dll.kh_version() == 3, "stale kernel harness (tests/kernels/build_harness.py --force)"
 
     def call(self, name, *args):
-        rc = getattr(self.dll, name)(*args)
+        rc = self.rc(name, *args)
         if rc:
             raise RuntimeError("%s: HIP error %d" % (name, rc))
         return rc
+
+    def rc(self, name, *args):
+        """the call's return code, whatever it is (the tests of the argument checks inspect it)"""
+        return getattr(self.dll, name)(*args)
+
+    def last_error(self):
+        return (self.dll.wn_last_error() or b"").decode("utf-8", "replace")
 
     def tn_grid(self, M, Ka, Nb, tile_nb, want):
         out = (_LL * 2)()
