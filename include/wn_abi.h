@@ -351,6 +351,19 @@ int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_
  * bit for bit what wn_prime leaves on n_streams copies of the row.  Asynchronous on hip_stream.  (Added without a new WN_ABI_VERSION, like wn_score.) */
 int wn_prime_shared(wn_handle* h, const int32_t* first_samples, int64_t n_prime, void* hip_stream);
 
+/* wn_prime for prompts of DIFFERENT lengths: `first_samples` is a DEVICE pointer to int32 [n_streams][row_stride], row s holding stream s's n_prime[s]
+ * teacher-forced samples from column 0 on; `n_prime` is a HOST pointer to n_streams lengths, 0 <= n_prime[s] <= row_stride (a negative or longer one,
+ * or a NULL argument: WN_E_BADARG).  wn_prime's contract otherwise -- freshly reset queues (else WN_E_STATE), the same shape limits (else
+ * WN_E_UNSUPPORTED), asynchronous on hip_stream; on any error nothing is written and the queue time is unchanged.  The streams are right-aligned in
+ * time: the queue time afterwards is n = max n_prime[s], stream s starts at time n - n_prime[s], and before that its activations are zero at every
+ * layer, like a reset queue's.  wn_state_save(h, s) afterwards is bit for bit what it returns on a one-stream handle after wn_prime over row s alone
+ * (the canonical form does not depend on the queue time); a stream of length 0 has the all-zero state.  All lengths 0: WN_OK, nothing is launched,
+ * the queue time stays 0.  All lengths equal: wn_prime's result, bit for bit.  Follow with wn_generate(n_given = 1, first_samples = every stream's
+ * last given sample).  The products run over sum n_prime[s] rows, not n_streams * n (the matrix-core tiles take their rows through a table of
+ * per-stream prefix sums), and the start gather is one launch for all streams.  On a handle of several rounds every member gets its slice of rows and
+ * lengths and ends at the n of ALL streams.  (Added without a new WN_ABI_VERSION, like wn_prime_shared.) */
+int wn_prime_ragged(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, void* hip_stream);
+
 /* ---- a stream's generation state as data ----
  * Between two wn_generate calls a stream IS the input rings of its layers (plus the queue time and the last drawn index, which the caller holds).  The
  * canonical form of those rings is independent of queue time, layer split, channel padding, kernel variant and rounds: for the layers l = 0 .. NL-1 in

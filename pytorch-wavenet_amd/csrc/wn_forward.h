@@ -86,6 +86,32 @@ static __device__ __forceinline__ const float* wn_row_at(const WnRowMap& r, unsi
     return r.base + (long long)q * r.batch_stride + (r.t0 + (long long)rem) * r.row_stride;
 }
 
+// The ragged row map of wn_prime_ragged (the *_ragged kernels below): the M rows of a product are the streams' trailing rows one behind the other, stream s
+// owning rows [start[s], start[s + 1]) -- prefix sums the host computes and bounds (wn_prime_ragged_plan_host, wn_plan.h); a stream without rows repeats
+// a start.  Row m belongs to the LAST stream s with start[s] <= m and stands for the time t_end - rows_s + (m - start[s]) of that stream: (s, time)
+// take the place of (m / rows_per_batch, m % rows_per_batch) in every row map of the product, whose t0 then counts from the stream's time 0.
+struct WnRagged {
+    const int32_t* start;   // [n_streams + 1], non-decreasing, start[0] = 0, start[n_streams] = M
+    int n_streams;
+    int t_end;              // the queue time every stream ends at
+};
+// m < start[n_streams].  -> the stream, its first row and its row count (a binary search: ceil(log2 n_streams) dependent loads of a table that stays in cache)
+static __device__ __forceinline__ void wn_ragged_find(const WnRagged& rg, unsigned m, unsigned& s, unsigned& first, unsigned& rows) {
+    int lo = 0, hi = rg.n_streams;
+    while (hi - lo > 1) {
+        const int mid = (lo + hi) >> 1;
+        if ((unsigned)rg.start[mid] <= m) lo = mid; else hi = mid;
+    }
+    s = (unsigned)lo;
+    first = (unsigned)rg.start[lo];
+    rows = (unsigned)rg.start[lo + 1] - first;
+}
+static __device__ __forceinline__ void wn_ragged_row(const WnRagged& rg, unsigned m, unsigned& q, unsigned& rem) {
+    unsigned first, rows;
+    wn_ragged_find(rg, m, q, first, rows);
+    rem = (unsigned)rg.t_end - rows + (m - first);
+}
+
 static __device__ __forceinline__ unsigned wn_pack_bf16(float lo, float hi) {  // two RNE-rounded bf16 in one dword
     unsigned a = __float_as_uint(lo), b = __float_as_uint(hi);
     a += 0x7fffu + ((a >> 16) & 1u);
@@ -123,15 +149,19 @@ static __device__ __forceinline__ uint4 wn_pack_bf16x8(float4 a, float4 b) {
 // is STORED as bf16 like every other product output that only feeds the next stage ([dF|dG], z, the gate pair): 8.9 GB of fp32 written and 8.9 GB read per
 // config-5 step become 4.45 + 4.45 (-1.4 ms: profiles/r05_training_step_byte_cuts.txt).  One more rounding point of the bf16 step (oracle/bf16_step.py carries it).
 static __device__ __forceinline__ float wn_gate_clamp(float x) { return x > 100.f ? 100.f : (x < -100.f ? -100.f : x); }
-template <int EPI, int NTILES = 4, bool CB16 = false>
+// RAGGED: (batch entry, row) of the strip's rows come from rmap[row - mw] (what the kernel's loaders found with wn_ragged_row) instead of the division.
+template <int EPI, int NTILES = 4, bool CB16 = false, bool RAGGED = false>
 static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, const wn_f16v (&acc)[NTILES], long long mw, int nw, int lane, float* stage,
-                                                        unsigned short* zl = nullptr, int zld = 0) {
+                                                        unsigned short* zl = nullptr, int zld = 0, const uint2* rmap = nullptr) {
     const int col = lane & 31;
     // row-wise lane roles: 4 columns per lane, 8 rows per pass (fp32 rows);  8 columns per lane, 16 rows per pass (bf16-stored rows)
     const int r4 = lane >> 3, c4 = 4 * (lane & 7);
     const int r8 = lane >> 2, c8 = 8 * (lane & 3);
     // (q, rem) of row m: M < 2^31 (checked on the host): 32-bit division, a 64-bit one is ~100 instructions
-    auto split = [&](long long m, unsigned& q, unsigned& rem) { q = (unsigned)m / (unsigned)g.rows_per_batch; rem = (unsigned)m - q * (unsigned)g.rows_per_batch; };
+    auto split = [&](long long m, unsigned& q, unsigned& rem) {
+        if constexpr (RAGGED) { const uint2 e = rmap[(int)(m - mw)]; q = e.x; rem = e.y; }
+        else { q = (unsigned)m / (unsigned)g.rows_per_batch; rem = (unsigned)m - q * (unsigned)g.rows_per_batch; }
+    };
     static_assert(EPI != WN_EPI_GATE || NTILES == 4, "the gate epilogue takes the whole 128-column strip");
     if constexpr (EPI == WN_EPI_GATE && NTILES == 4) {
         const int NH = g.N >> 1;   // channels per row of z / the gate pair
@@ -355,89 +385,19 @@ static __device__ __forceinline__ void wn_gemm_epilogue(const WnGemmArgs& g, con
 #define WN_GEMM_KC 16   // K chunk of the fp32 GEMMs.  Measured on the config-5 forward: 32 (65.8 KB LDS, 2 workgroups per CU)
                         // 89.4 ms; 16 (32.9 KB) with 3 per CU 78.4 ms, with 4 per CU (119 VGPRs) 71.2 ms; 8: 70.9 ms
 #define WN_GEMM_MINB 4  // (workgroups per CU: the 71.2 ms of the line above)
+// The body is ONE text, wn_fwd_gemm_body.inl, for two kernels; RAGGED = the row map of wn_prime_ragged (rg; g.rows_per_batch and the row windows
+// a_skip_* / cin_skip_lo are not used: a row before a stream's start is never computed and reads as the zero the cleared workspace holds).  The
+// loaders leave every row's (stream, time) in LDS for the epilogue: one search per row and tile.
 template <int EPI>
 __global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm(WnGemmArgs g) {
-    constexpr int TM = 128, TN = 128, KC = WN_GEMM_KC, AP = TM + 1;  // AP: padded row length of the transposed A chunk
-    constexpr int NQ = KC / 8;          // float4 per thread per operand and chunk
-    constexpr int BT = 256 / KC;        // threads per B row
-    // (ONE block: the epilogue re-uses it as the waves' staging tiles once the K loop is done)
-    __shared__ __attribute__((aligned(16))) float smem_f[2 * KC * AP + 2 * KC * TN + (2 * KC * AP) % 4];
-    static_assert(2 * KC * AP + 2 * KC * TN >= 4 * WN_EPI_TILE_FLOATS, "the operand buffers hold the four waves' staging tiles");
-    float (*a_t)[KC * AP] = reinterpret_cast<float (*)[KC * AP]>(smem_f);                                        // [2][k][row]
-    float (*b_s)[KC * TN] = reinterpret_cast<float (*)[KC * TN]>(smem_f + ((2 * KC * AP + 3) & ~3));               // [2][k][col]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const unsigned mtiles = (unsigned)((g.M + TM - 1) / TM), tm_i = blockIdx.x % mtiles, tn_i = blockIdx.x / mtiles;  // row tiles fastest
-    const long long m0 = (long long)tm_i * TM;
-    const int n0 = (int)tn_i * TN;
-    wn_f16v acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-
-    // loader roles: A chunk = 128 rows x 32 floats: thread -> row tid/2, 16 floats (4 float4) ; B chunk = 32 x 128: 4 float4 each
-    const int arow = tid >> 1, ahalf = tid & 1;
-    const long long am = m0 + arow;
-    const bool arow_ok = am < g.M;
-    const unsigned aq = arow_ok ? (unsigned)am / (unsigned)g.rows_per_batch : 0u, arem = arow_ok ? (unsigned)am - aq * (unsigned)g.rows_per_batch : 0u;
-    const bool ok0 = arow_ok && (int)arem >= g.a_skip_lo[0] && (int)arem < g.rows_per_batch - g.a_skip_hi[0];
-    const bool ok1 = arow_ok && (int)arem >= g.a_skip_lo[1] && (int)arem < g.rows_per_batch - g.a_skip_hi[1];
-    const float* a0p = wn_row_at(g.a0, aq, arem);
-    const float* a1p = wn_row_at(g.a1, aq, arem);
-    const int brow = tid / BT, bcol = (tid % BT) * (KC / 2);
-
-    float4 va[NQ], vb[NQ];  // staging registers of the chunk in flight
-    auto fetch = [&](int kc) {  // global -> registers (issued before the multiply of the current chunk)
-        const int k0 = kc * KC;
-        const bool first = k0 < g.k_split, ok = first ? ok0 : ok1;
-        const float* src = first ? a0p + k0 : a1p + (k0 - g.k_split);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) va[q] = ok ? *reinterpret_cast<const float4*>(src + ahalf * (KC / 2) + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        const float* bsrc = ((first || !g.bt1) ? g.bt + (size_t)(k0 + brow) * g.N : g.bt1 + (size_t)(k0 - g.k_split + brow) * g.N) + n0 + bcol;
-        // (ONE predicate for the thread's NQ loads -- N % 32 == 0 and bcol is a multiple of KC / 2 = 4 NQ floats, so they are in range together: with a
-        //  predicate per load each one sat in a block of its own with a full wait behind it.  Round 6, profiles/r06_tn_loads.txt.)
-        const bool okb = n0 + bcol < g.N;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) vb[q] = okb ? *reinterpret_cast<const float4*>(bsrc + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-    };
-    auto stash = [&](int buf) {  // registers -> LDS (A transposed to [k][row])
-        float* at = a_t[buf];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            float4 x = va[q];
-            if (g.relu_a) { x.x = fmaxf(x.x, 0.f); x.y = fmaxf(x.y, 0.f); x.z = fmaxf(x.z, 0.f); x.w = fmaxf(x.w, 0.f); }
-            const int k = ahalf * (KC / 2) + q * 4;
-            at[(k + 0) * AP + arow] = x.x; at[(k + 1) * AP + arow] = x.y; at[(k + 2) * AP + arow] = x.z; at[(k + 3) * AP + arow] = x.w;
-        }
-        float* bs = b_s[buf] + brow * TN + bcol;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) *reinterpret_cast<float4*>(bs + q * 4) = vb[q];
-    };
-
-    const int nchunks = g.K / KC;
-    fetch(0);
-    stash(0);
-    __syncthreads();
-    for (int kc = 0; kc < nchunks; ++kc) {
-        const int buf = kc & 1;
-        if (kc + 1 < nchunks) fetch(kc + 1);  // lands while this chunk is multiplied
-        const float* at = a_t[buf] + 32 * wv + (lane & 31);
-        const float* bs = b_s[buf] + (lane & 31);
-        const int kh = lane >> 5;
-#pragma unroll
-        for (int ks = 0; ks < KC / 2; ++ks) {
-            const float a = at[(2 * ks + kh) * AP];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float b = bs[(2 * ks + kh) * TN + 32 * j];
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
-            }
-        }
-        if (kc + 1 < nchunks) stash(buf ^ 1);
-        __syncthreads();
-    }
-
-    wn_gemm_epilogue<EPI>(g, acc, m0 + 32 * wv, n0, lane, smem_f + wv * WN_EPI_TILE_FLOATS);   // (the loop's last barrier: nobody reads the operand buffers any more)
+    constexpr bool RAGGED = false;
+    const WnRagged rg = {nullptr, 0, 0};
+#include "wn_fwd_gemm_body.inl"
+}
+template <int EPI>
+__global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm_ragged(WnGemmArgs g, WnRagged rg) {
+    constexpr bool RAGGED = true;
+#include "wn_fwd_gemm_body.inl"
 }
 
 // ---- The filter/gate product of a layer with kernel_size TAPS = 3 or 4 (inference: wn_forward / wn_score / wn_prime, fp32 operands):
@@ -456,90 +416,14 @@ struct WnTapsArgs {
 };
 template <int TAPS>
 __global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm_taps(WnTapsArgs ta) {
-    static_assert(TAPS == 3 || TAPS == 4, "kernel_size 3 and 4 (2 is wn_fwd_gemm's two-view form)");
-    const WnGemmArgs& g = ta.g;
-    constexpr int TM = 128, TN = 128, KC = WN_GEMM_KC, AP = TM + 1;
-    constexpr int NQ = KC / 8;
-    constexpr int BT = 256 / KC;
-    __shared__ __attribute__((aligned(16))) float smem_f[2 * KC * AP + 2 * KC * TN + (2 * KC * AP) % 4];
-    static_assert(2 * KC * AP + 2 * KC * TN >= 4 * WN_EPI_TILE_FLOATS, "the operand buffers hold the four waves' staging tiles");
-    float (*a_t)[KC * AP] = reinterpret_cast<float (*)[KC * AP]>(smem_f);                                        // [2][k][row]
-    float (*b_s)[KC * TN] = reinterpret_cast<float (*)[KC * TN]>(smem_f + ((2 * KC * AP + 3) & ~3));               // [2][k][col]
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const unsigned mtiles = (unsigned)((g.M + TM - 1) / TM), tm_i = blockIdx.x % mtiles, tn_i = blockIdx.x / mtiles;  // row tiles fastest
-    const long long m0 = (long long)tm_i * TM;
-    const int n0 = (int)tn_i * TN;
-    wn_f16v acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j)
-#pragma unroll
-        for (int i = 0; i < 16; ++i) acc[j][i] = 0.f;
-
-    // loader roles as in wn_fwd_gemm: A chunk = 128 rows x KC floats, two threads per row; B chunk = KC x 128
-    const int arow = tid >> 1, ahalf = tid & 1;
-    const long long am = m0 + arow;
-    const bool arow_ok = am < g.M;
-    const unsigned aq = arow_ok ? (unsigned)am / (unsigned)g.rows_per_batch : 0u, arem = arow_ok ? (unsigned)am - aq * (unsigned)g.rows_per_batch : 0u;
-    const float* a1p = wn_row_at(g.a1, aq, arem) + ahalf * (KC / 2);   // the row of x(t)
-    const long long tap_fl = ta.tap_rows * g.a1.row_stride;              // floats between two neighbouring taps
-    const long long t_row = g.a1.t0 + (long long)arem;                    // the row's time inside its batch entry
-    unsigned okmask = 0;                                                 // bit j: view j of this row exists
-#pragma unroll
-    for (int j = 0; j < TAPS; ++j) okmask |= (arow_ok && t_row - (TAPS - 1 - j) * ta.tap_rows >= ta.t_min) ? (1u << j) : 0u;
-    const int brow = tid / BT, bcol = (tid % BT) * (KC / 2);
-    const float* bp = g.bt + (size_t)brow * g.N + n0 + bcol;
-    const bool okb = n0 + bcol < g.N;   // (one predicate for the thread's NQ loads: see wn_fwd_gemm)
-
-    float4 va[NQ], vb[NQ];
-    int f_tap = 0, f_off = 0;   // the view and the column inside it of the next chunk to fetch
-    auto fetch = [&]() {
-        const bool ok = (okmask >> f_tap) & 1u;
-        const float* src = a1p - (long long)(TAPS - 1 - f_tap) * tap_fl + f_off;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) va[q] = ok ? *reinterpret_cast<const float4*>(src + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) vb[q] = okb ? *reinterpret_cast<const float4*>(bp + q * 4) : make_float4(0.f, 0.f, 0.f, 0.f);
-        bp += (size_t)KC * g.N;
-        f_off += KC;
-        if (f_off == g.k_split) { f_off = 0; ++f_tap; }
-    };
-    auto stash = [&](int buf) {  // registers -> LDS (A transposed to [k][row])
-        float* at = a_t[buf];
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) {
-            const float4 x = va[q];
-            const int k = ahalf * (KC / 2) + q * 4;
-            at[(k + 0) * AP + arow] = x.x; at[(k + 1) * AP + arow] = x.y; at[(k + 2) * AP + arow] = x.z; at[(k + 3) * AP + arow] = x.w;
-        }
-        float* bs = b_s[buf] + brow * TN + bcol;
-#pragma unroll
-        for (int q = 0; q < NQ; ++q) *reinterpret_cast<float4*>(bs + q * 4) = vb[q];
-    };
-
-    const int nchunks = TAPS * (g.k_split / KC);
-    fetch();
-    stash(0);
-    __syncthreads();
-    for (int kc = 0; kc < nchunks; ++kc) {
-        const int buf = kc & 1;
-        if (kc + 1 < nchunks) fetch();  // lands while this chunk is multiplied
-        const float* at = a_t[buf] + 32 * wv + (lane & 31);
-        const float* bs = b_s[buf] + (lane & 31);
-        const int kh = lane >> 5;
-#pragma unroll
-        for (int ks = 0; ks < KC / 2; ++ks) {
-            const float a = at[(2 * ks + kh) * AP];
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                const float b = bs[(2 * ks + kh) * TN + 32 * j];
-                acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc[j], 0, 0, 0);
-            }
-        }
-        if (kc + 1 < nchunks) stash(buf ^ 1);
-        __syncthreads();
-    }
-
-    wn_gemm_epilogue<WN_EPI_GATE>(g, acc, m0 + 32 * wv, n0, lane, smem_f + wv * WN_EPI_TILE_FLOATS);   // (the loop's last barrier: nobody reads the operand buffers any more)
+    constexpr bool RAGGED = false;
+    const WnRagged rg = {nullptr, 0, 0};
+#include "wn_fwd_gemm_taps_body.inl"
+}
+template <int TAPS>
+__global__ __launch_bounds__(256, WN_GEMM_MINB) void wn_fwd_gemm_taps_ragged(WnTapsArgs ta, WnRagged rg) {
+    constexpr bool RAGGED = true;
+#include "wn_fwd_gemm_taps_body.inl"
 }
 
 // ---- The input gradient of that product (training step, kernel_size TAPS = 3 or 4, fp32 operands): with dfg = [dF|dG] of the layer on the rows
@@ -1215,6 +1099,23 @@ __global__ void wn_fwd_start(const int32_t* idx, const float* start_t, const flo
     if (xh) *reinterpret_cast<uint2*>(xh + row * R + q * 4) = wn_pack_bf16x4(v);   // (the bf16 step's shadow of x, see WnGemmArgs::c_h)
 }
 
+// wn_fwd_start for wn_prime_ragged, ONE launch for all streams: row m of rg (table 0: stream s owns n_prime[s] rows) is sample m - start[s] of stream s's
+// prompt (idx: rows idx_stride apart) and lands at the stream's time t_end - n_prime[s] + (m - start[s]); x points at time 0 of stream 0, streams
+// x_stream_stride floats apart.
+__global__ void wn_fwd_start_ragged(const int32_t* idx, long long idx_stride, const float* start_t, const float* start_b, float* x, long long x_stream_stride,
+                                    WnRagged rg, long long rows, int R) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const long long row = i / (R / 4);
+    const int q = (int)(i % (R / 4));
+    if (row >= rows) return;
+    unsigned s, first, cnt;
+    wn_ragged_find(rg, (unsigned)row, s, first, cnt);
+    const unsigned j = (unsigned)row - first;
+    const long long t = (long long)rg.t_end - cnt + j;
+    float4 v = *reinterpret_cast<const float4*>(start_t + (size_t)idx[(long long)s * idx_stride + j] * R + q * 4);
+    if (start_b) { v.x += start_b[q * 4]; v.y += start_b[q * 4 + 1]; v.z += start_b[q * 4 + 2]; v.w += start_b[q * 4 + 3]; }
+    *reinterpret_cast<float4*>(x + (long long)s * x_stream_stride + t * R + q * 4) = v;
+}
 
 // ------------------------------------------------------------------------------------------------ backward pass
 // Weight gradients: C[Ka][Nb] += sum_m A[m][ka] * B[m][nb]  ("TN": the contraction runs over the rows).  Grid

@@ -35,6 +35,18 @@ static void wn_launch_taps(hipStream_t st, int taps, const WnTapsArgs& a) {
     else hipLaunchKernelGGL(wn_fwd_gemm_taps<4>, grid, dim3(256), 0, st, a);
 }
 
+// The fp32 products of wn_prime_ragged: the same tiles under the ragged row map `rg` (wn_forward.h: WnRagged; a.M = the table's total, a.rows_per_batch unused)
+static void wn_launch_nn_ragged(hipStream_t st, int epi, const WnGemmArgs& a, const WnRagged& rg) {
+    const dim3 grid((unsigned)((a.M + 127) / 128) * (unsigned)((a.N + 127) / 128));
+    if (epi == WN_EPI_GATE) hipLaunchKernelGGL(wn_fwd_gemm_ragged<WN_EPI_GATE>, grid, dim3(256), 0, st, a, rg);
+    else hipLaunchKernelGGL(wn_fwd_gemm_ragged<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a, rg);
+}
+static void wn_launch_taps_ragged(hipStream_t st, int taps, const WnTapsArgs& a, const WnRagged& rg) {
+    const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)((a.g.N + 127) / 128));
+    if (taps == 3) hipLaunchKernelGGL(wn_fwd_gemm_taps_ragged<3>, grid, dim3(256), 0, st, a, rg);
+    else hipLaunchKernelGGL(wn_fwd_gemm_taps_ragged<4>, grid, dim3(256), 0, st, a, rg);
+}
+
 // The same product on bf16 operands (wn_fwd_gemm_taps_bf16): bn = the layer's block of the bf16 bank, [N][taps * R]; N % 256 == 0 takes the
 // 128 x 256 tile (wn_launch_nn's rule)
 static void wn_launch_taps_bf16(hipStream_t st, int taps, const WnTapsArgs& a, const unsigned short* bn) {
@@ -446,6 +458,121 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
         return WN_OK;
     }
     return wn_prime_run(h, first_samples, n_prime, row_stride, false, &h, 1, hip_stream, "wn_prime");
+}
+
+// ---- wn_prime_ragged: prompts of unequal length in one batched pass, right-aligned at the queue time n (include/wn_abi.h has the contract).
+// What one handle with rings must satisfy before anything is launched -- a front checks EVERY member first, so that an error leaves all of them untouched.
+static int wn_prime_ragged_check(wn_handle* h, const char* who) {
+    if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
+    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
+    if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+    if (h->t_base != 0) return wn_fail(WN_E_STATE, "%s: queues must be freshly reset (queue time is %lld)", who, h->t_base);
+    return WN_OK;
+}
+// One handle's streams (checked: wn_prime_ragged_check; lengths in [0, row_stride], n = the queue time all streams of the job end at, >= every length).
+// wn_prime_run's pass with three differences: ONE start launch for all streams, the products run over the streams' own rows only (the row plan of
+// wn_prime_ragged_plan_host, uploaded once for all layers), z is addressed by (stream, time) like x.  A row before a stream's start is never computed:
+// both halves of the cleared workspace read as zero there at every layer, which is what a reset queue holds -- nothing is computed and zeroed afterwards.
+static int wn_prime_ragged_run(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, long long n, void* hip_stream, const char* who) {
+    const WnPlan& pl = h->plan;
+    const int R = pl.R, D = pl.D, NL = pl.NL, ns = pl.n_streams;
+    bool equal = true;
+    for (int s = 0; s < ns; ++s) equal = equal && n_prime[s] == n;
+    if (equal) return wn_prime_run(h, first_samples, n, row_stride, false, &h, 1, hip_stream, who);   // (the rectangle: wn_prime's own pass, bit for bit)
+    WnRaggedPlan rp;
+    const std::string why = wn_prime_ragged_plan_host(h->dil.data(), NL, pl.k, n_prime, ns, n, rp);
+    if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
+    { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
+    const long long k1 = pl.k - 1;
+    long long max_d = 1;
+    for (int l = 0; l < NL; ++l) max_d = h->dil[l] > max_d ? h->dil[l] : max_d;
+    const long long Lp = k1 * max_d, Lt = Lp + n;   // (wn_prime_run's rectangle: Lp rows of zeros in front of every stream's time 0)
+    const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
+    const size_t total = 2 * x_fl + z_fl;
+    if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
+    // the row tables: pinned staging that the copy before this one may still be reading (the event says when it is done), one device image
+    const size_t n_tab = rp.start.size();
+    if (!h->ragged_ev) { int rc = rt_hip(hipEventCreateWithFlags(&h->ragged_ev, hipEventDisableTiming), "hipEventCreate"); if (rc) { h->ragged_ev = nullptr; return rc; } }
+    else { int rc = rt_hip(hipEventSynchronize(h->ragged_ev), "hipEventSynchronize(row tables)"); if (rc) return rc; }
+    if (h->ragged_ints < n_tab) {
+        { int rc = rt_hip(hipDeviceSynchronize(), "hipDeviceSynchronize"); if (rc) return rc; }   // (kernels of an earlier pass may still read the old image)
+        if (h->ragged_host) (void)hipHostFree(h->ragged_host);
+        h->ragged_host = nullptr;
+        if (hipHostMalloc((void**)&h->ragged_host, n_tab * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { h->ragged_host = nullptr; h->ragged_ints = 0; return wn_fail(WN_E_NOMEM, "%s: row tables", who); }
+        if (!rt_grow(h->d_ragged, h->ragged_ints, n_tab)) return wn_fail(WN_E_NOMEM, "%s: row tables", who);
+    }
+    memcpy(h->ragged_host, rp.start.data(), n_tab * sizeof(int32_t));
+    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl;
+    hipStream_t st = (hipStream_t)hip_stream;
+    int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * x_fl * 4, st), "hipMemsetAsync(prime workspace)");
+    if (rc) return rc;
+    rc = rt_hip(hipMemcpyAsync(h->d_ragged, h->ragged_host, n_tab * sizeof(int32_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(row tables)");
+    if (rc) return rc;
+    rc = rt_hip(hipEventRecord(h->ragged_ev, st), "hipEventRecord(row tables)");
+    if (rc) return rc;
+    auto table = [&](int t) { return WnRagged{h->d_ragged + (size_t)t * (ns + 1), ns, (int)n}; };
+    if (rp.total[0] > 0) {   // x0 = the start_conv column gather over every stream's given positions
+        const long long work = rp.total[0] * (R / 4);
+        hipLaunchKernelGGL(wn_fwd_start_ragged, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, first_samples, (long long)row_stride, h->w.d_start_t,
+                           pl.has_bias ? h->w.d_start_b : nullptr, xa + Lp * R, Lt * R, table(0), rp.total[0], R);
+    }
+    const float* fw = h->w.d_fw;
+    float* xin = xa; float* xout = xb;
+    for (int l = 0; l < NL; ++l) {
+        const long long d = h->dil[l];
+        const int ML = (int)(k1 * d) + 1;
+        {   // queue of layer l <- newest min(k1*d+1, n) columns of its input: zeros where the stream had not started
+            const int count = (int)(ML < n ? ML : n);
+            const long long work = (long long)ns * count * (R / 4);
+            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, Lt * R, h->d_rings + h->ring_off[l], R, ML, ns, pl.P, n, count);
+        }
+        if (l == NL - 1) break;
+        const long long M = rp.total[1 + l];
+        if (M > 0) {
+            // every map counts rows from the stream's time 0 (t0 = 0): the kernels put (stream, time) where (batch entry, row) stand
+            const WnRowMap zmap = wn_rows(z, n, D), x = WnRowMap{xin + Lp * R, Lt * R, R, 0}, xo = WnRowMap{xout + Lp * R, Lt * R, R, 0};
+            const WnRagged rg = table(1 + l);
+            if (pl.k == 2) {
+                WnGemmArgs a = wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, 1, M);
+                wn_launch_nn_ragged(st, WN_EPI_GATE, a, rg);
+            } else {
+                wn_launch_taps_ragged(st, pl.k, wn_layer_fg_taps(pl, h->w.fw, fw, l, x, d, zmap, 1, M, -Lp), rg);
+            }
+            wn_launch_nn_ragged(st, WN_EPI_PLAIN, wn_layer_res(pl, h->w.fw, fw, l, zmap, x, xo, 1, M), rg);
+        }
+        float* t = xin; xin = xout; xout = t;
+    }
+    rc = rt_hip(hipGetLastError(), "wn_prime_ragged launches");
+    if (rc) return rc;
+    h->t_base = n;
+    return WN_OK;
+}
+
+extern "C" int wn_prime_ragged(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, void* hip_stream) {
+    g_err[0] = 0;
+    if (!h || !first_samples || !n_prime) return wn_fail(WN_E_BADARG, "wn_prime_ragged: NULL argument");
+    const int ns = h->chains.empty() ? h->plan.n_streams : h->chain_first.back();
+    long long n = 0;
+    for (int s = 0; s < ns; ++s) {
+        if (n_prime[s] < 0 || n_prime[s] > row_stride) return wn_fail(WN_E_BADARG, "wn_prime_ragged: stream %d: length %lld outside [0, row_stride = %lld]", s, (long long)n_prime[s], (long long)row_stride);
+        n = n_prime[s] > n ? n_prime[s] : n;
+    }
+    if (!h->chains.empty()) {
+        if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+        if (h->broken) return wn_fail(WN_E_STATE, "wn_prime_ragged: an earlier job failed half way through its rounds; call wn_reset");
+        for (wn_handle* c : h->chains) { int rc = wn_prime_ragged_check(c, "wn_prime_ragged"); if (rc) return rc; }
+        if (n == 0) return WN_OK;
+        for (size_t i = 0; i < h->chains.size(); ++i) {   // every member ends at the front's n, also one whose own streams are all shorter
+            const size_t s0 = (size_t)h->chain_first[i];
+            int rc = wn_prime_ragged_run(h->chains[i], first_samples + s0 * (size_t)row_stride, n_prime + s0, row_stride, n, hip_stream, "wn_prime_ragged");
+            if (rc) { if (i) h->broken = true; return rc; }   // (members before this one have moved on: as after a job that failed between its rounds)
+        }
+        h->t_base = h->chains[0]->t_base;
+        return WN_OK;
+    }
+    { int rc = wn_prime_ragged_check(h, "wn_prime_ragged"); if (rc) return rc; }
+    if (n == 0) return WN_OK;
+    return wn_prime_ragged_run(h, first_samples, n_prime, row_stride, n, hip_stream, "wn_prime_ragged");
 }
 
 // wn_prime for a prompt that every stream shares: ONE row of given samples, the stack's products once over it (the workspace of a 1-stream prime), the ring

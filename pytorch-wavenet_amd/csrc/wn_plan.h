@@ -740,6 +740,54 @@ static inline std::string wn_forward_geometry_host(const int32_t* dil, int NL, l
     }
     return std::string();
 }
+// ---- row plan of wn_prime_ragged (wn_forward.inl): batched priming of streams whose prompts differ in length, right-aligned at queue time n.
+// Stream s holds n_prime[s] given samples at the times [n - n_prime[s], n); before its start its activations are zero at every layer (rows that are
+// never computed, in a workspace that is cleared first).  Table 0 describes the start_conv gather (n_prime[s] rows per stream), table 1 + l the two
+// products of layer l (l = 0 .. NL - 2; the last layer's output is never consumed): stream s computes the trailing min(need[l + 1], n_prime[s]) rows,
+// need[i] = trailing positions of layer i's input that the queues above can still see (wn_prime's q before its clamp to n).  A table is the prefix
+// sums of its streams' row counts, start[0 .. ns] (start[ns] = the product's M); a stream without rows repeats a start.  Row m of a product belongs
+// to the LAST stream s with start[s] <= m and stands for the time n - rows_s + (m - start[s]) of that stream (wn_ragged_find, wn_forward.h).
+// THIS is what keeps the kernels' addresses inside the workspace: every time lies in [n - n_prime[s], n), every stream in [0, ns).
+struct WnRaggedPlan {
+    int ns = 0, n_tables = 0;           // n_tables = NL (>= 1)
+    long long n = 0;                    // the queue time behind the call
+    std::vector<long long> need;        // [NL + 1]
+    std::vector<int32_t> start;         // [n_tables][ns + 1]
+    std::vector<long long> total;       // [n_tables] = start[t][ns]
+    const int32_t* table(int t) const { return start.data() + (size_t)t * (ns + 1); }
+    long long rows(int t, int s) const { return (long long)table(t)[s + 1] - table(t)[s]; }
+    long long first_time(int t, int s) const { return n - rows(t, s); }
+};
+// Returns "" and fills p, or why not: a length outside [0, n], or ns * n at / above 2^31 rows (the bound of wn_prime: rows are 32-bit in the kernels).
+static inline std::string wn_prime_ragged_plan_host(const int32_t* dil, int NL, int kernel_size, const int64_t* n_prime, int ns, long long n, WnRaggedPlan& p) {
+    const long long k1 = kernel_size - 1;
+    if (NL < 1 || ns < 1 || n < 0) return "no layers, no streams or a negative queue time";
+    for (int s = 0; s < ns; ++s)
+        if (n_prime[s] < 0 || n_prime[s] > n) return "stream " + std::to_string(s) + ": length " + std::to_string((long long)n_prime[s]) + " outside [0, " + std::to_string(n) + "]";
+    if ((long long)ns * n >= 0x7fffffffll) return "too many rows (n_streams * n must stay below 2^31)";
+    p.ns = ns; p.n_tables = NL; p.n = n;
+    p.need.assign(NL + 1, 0);
+    for (int l = NL - 1; l >= 0; --l) {   // (wn_prime's q, not clamped: the clamp is per stream here)
+        const long long d = dil[l];
+        long long v = p.need[l + 1] > 0 ? p.need[l + 1] + k1 * d : 0;
+        if (v < k1 * d + 1) v = k1 * d + 1;
+        p.need[l] = v;
+    }
+    p.start.assign((size_t)NL * (ns + 1), 0);
+    p.total.assign(NL, 0);
+    for (int t = 0; t < NL; ++t) {
+        int32_t* st = p.start.data() + (size_t)t * (ns + 1);
+        long long sum = 0;
+        for (int s = 0; s < ns; ++s) {
+            const long long want = t == 0 ? (long long)n_prime[s] : p.need[t], rows = want < (long long)n_prime[s] ? want : (long long)n_prime[s];
+            st[s] = (int32_t)sum;
+            sum += rows;   // (<= ns * n < 2^31)
+        }
+        st[ns] = (int32_t)sum;
+        p.total[t] = sum;
+    }
+    return std::string();
+}
 // ---- row windows of the k-tap backward's input-gradient product (wn_bwd_gemm_taps, wn_forward.h).  dx_l lives on the rows_out = g.rows[l] trailing rows of a
 // clip, [dF|dG] of the layer on the rows_dfg = g.rows[l + 1] trailing ones: output row i (time L - rows_out + i) is row i - shift of dfg.
 static inline long long wn_taps_bwd_shift(long long rows_out, long long rows_dfg) { return rows_out - rows_dfg; }

@@ -279,6 +279,8 @@ struct wn_handle {
     float* d_tws = nullptr; size_t tws_floats = 0;  // training workspace (saved activations + backward temporaries)
     float* d_xent = nullptr; size_t xent_rows = 0;  // wn_train_loss: per-row losses
     double* d_score_part = nullptr; size_t score_parts = 0;  // wn_score: one {sum nll, hits, rows} triple per workgroup
+    int32_t* d_ragged = nullptr; size_t ragged_ints = 0;     // wn_prime_ragged: the row tables of all layers, their pinned staging copy, and the event behind
+    int32_t* ragged_host = nullptr; hipEvent_t ragged_ev = nullptr;   //   the last upload (the staging copy is rewritten only once that upload has been read)
     WnTrainLay train = {}; bool train_valid = false;
     // wn_train_backward: the weight-gradient products run on a second stream next to the activation-gradient chain (wn_train.inl)
     hipStream_t side_stream = nullptr;
@@ -351,6 +353,9 @@ extern "C" void wn_destroy(wn_handle* h) {
     rt_free(h->d_tws);
     rt_free(h->d_xent);
     rt_free(h->d_score_part);
+    rt_free(h->d_ragged);
+    if (h->ragged_host) (void)hipHostFree(h->ragged_host);
+    if (h->ragged_ev) (void)hipEventDestroy(h->ragged_ev);
     rt_free(h->det_ws[0].buf); rt_free(h->det_ws[1].buf);
     delete h;
 }

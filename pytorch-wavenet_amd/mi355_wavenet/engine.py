@@ -40,6 +40,48 @@ def checked_forced(forced, num_samples, classes, rows=None):
     return np.array(np.broadcast_to(f.reshape(-1, num_samples), (rows, num_samples)), dtype=np.int32, order="C")
 
 
+def _host_array(v):
+    return np.asarray(v.detach().cpu() if hasattr(v, "detach") else v)
+
+
+def is_ragged_prompt(first_samples):
+    """True for a non-empty list / tuple of ROWS (sequences, arrays, tensors): one prompt per stream, of any lengths.  A list of plain integers is
+    the 1-D prompt it always was; arrays and tensors are never ragged."""
+    if not isinstance(first_samples, (list, tuple)) or not first_samples:
+        return False
+    return not all(_host_array(v).ndim == 0 for v in first_samples)
+
+
+def ragged_rows(prompts, classes, min_length=1):
+    """A list / tuple of 1-D integer sequences or tensors -> ([int64 arrays], int64 array of their lengths).  ValueError for anything else: a row
+    that is not 1-D or not of integers, one shorter than min_length, a class index outside [0, classes)."""
+    if not isinstance(prompts, (list, tuple)):
+        raise ValueError("prompts must be a list or tuple of 1-D integer sequences, got %s" % type(prompts).__name__)
+    rows = []
+    for s, p in enumerate(prompts):
+        a = _host_array(p)
+        if a.ndim != 1:
+            raise ValueError("prompt %d is not a 1-D sequence (shape %r)" % (s, a.shape))
+        if a.size and a.dtype.kind not in "iu":
+            raise ValueError("prompt %d holds %s values, class indices are integers" % (s, a.dtype))
+        if a.size < min_length:
+            raise ValueError("prompt %d holds %d sample(s), at least %d needed" % (s, a.size, min_length))
+        a = a.astype(np.int64)
+        if a.size and (a.min() < 0 or a.max() >= classes):
+            raise ValueError("prompt %d outside [0, classes)" % s)
+        rows.append(a)
+    return rows, np.asarray([r.size for r in rows], dtype=np.int64)
+
+
+def right_aligned(rows):
+    """The rows as an int64 (len(rows), longest) matrix, each row ending in the last column (zeros in front of it)"""
+    out = np.zeros((len(rows), max(r.size for r in rows)), dtype=np.int64)
+    for s, r in enumerate(rows):
+        if r.size:
+            out[s, out.shape[1] - r.size:] = r
+    return out
+
+
 class _TorchMem:
     """Device memory, streams and transfers through PyTorch-ROCm (the memory provider of every product Engine)."""
     def __init__(self, device_index):
@@ -294,6 +336,28 @@ class Engine:
             return True
         dev = self.mem.upload(row)
         rc = prime(self._h, self.mem.ptr(dev), int(row.size), self.mem.stream())
+        if rc == _abi.WN_E_UNSUPPORTED:
+            return False
+        self.lib.check(rc)
+        return True
+
+    def prime_ragged(self, prompts):
+        """prime() for prompts of DIFFERENT lengths (wn_prime_ragged): ``prompts`` is a list of n_streams 1-D integer sequences, all of them
+        teacher-forced inputs (a stream may have none).  One batched pass over the streams' own rows; the streams are right-aligned in time, the queue
+        time afterwards is the longest length.  Returns False when the library lacks the symbol or the engine cannot (wn_prime's shape limits): the
+        caller primes some other way.  ValueError, before any call: not n_streams rows, a row that is not 1-D, a class index out of range."""
+        rows, lengths = ragged_rows(prompts, self.classes, min_length=0)
+        if len(rows) != self.n_streams:
+            raise ValueError("prompts must hold one row per stream (%d), got %d" % (self.n_streams, len(rows)))
+        if not self.lib.has("wn_prime_ragged"):
+            return False
+        stride = max(1, int(lengths.max()))
+        fs = np.zeros((self.n_streams, stride), dtype=np.int32)
+        for s, row in enumerate(rows):
+            fs[s, :row.size] = row
+        dev = self.mem.upload(fs)   # (held until the launches are enqueued: the stream orders the rest)
+        n = (ctypes.c_int64 * self.n_streams)(*[int(v) for v in lengths])
+        rc = self.lib.dll.wn_prime_ragged(self._h, self.mem.ptr(dev), n, stride, self.mem.stream())
         if rc == _abi.WN_E_UNSUPPORTED:
             return False
         self.lib.check(rc)

@@ -454,7 +454,15 @@ class WaveNetModel(nn.Module):
         forced: an int array shaped like the audio (1-D, or 2-D with the prompt's rows) -- a class index in [0, classes) is what the stream emits at
         that position, -1 leaves the position to the draw (include/wn_abi.h: wn_set_forced_samples).  A forced sample enters the network and the
         state like a drawn one and gets its log-probability like one; its uniform is drawn and not used, so the RNG's consumption, the callbacks and the
-        timing print are those of the call without it.  Ragged prompts: the common prefix as first_samples, the rest of each prompt as a forced prefix."""
+        timing print are those of the call without it.
+        Ragged prompts: first_samples may be a list or tuple of 1-D sequences or tensors, one prompt per stream, of ANY lengths >= 1 (a list of plain
+        integers stays one 1-D prompt).  The result is (len(prompts), num_samples), row s being generate_fast(num_samples, first_samples=prompts[s]) of
+        a one-stream call given the same uniforms; the RNG's consumption is that of the 2-D call, (streams, n_new) uniforms per piece, and rows of
+        equal length ARE the 2-D call.  All prompts are primed in one batched pass over the streams' own samples (Engine.prime_ragged: no length
+        threshold), the streams right-aligned in time; callbacks, the timing print and the piece cuts are those of a call with num_given = the longest
+        prompt whose priming the batched pass covered.  return_state: state s counts evals = len(prompts[s]) - 1 + num_samples.  forced stays
+        (streams, num_samples).  Where the batched pass does not apply (kernel_size above 4, the unpadded kernel_size 3 and 4 shapes, an older
+        library) every prompt is primed ALONE on a one-stream engine and its state loaded into the job's engine: correct for every shape, and slow."""
         logprobs = self._logprob_mode(return_logprobs)
         forced = self._checked_forced(forced, num_samples)
         states, first_samples = self._continuation("generate_fast", continue_from, first_samples)
@@ -500,6 +508,39 @@ class WaveNetModel(nn.Module):
         return GenerationState(eng.state_save(stream), last_index, evals, layers=self.layers, blocks=self.blocks, residual_channels=self.residual_channels,
                                kernel_size=self.kernel_size, classes=self.classes)
 
+    def _ragged_prompt(self, first_samples):
+        """A list / tuple of rows (one prompt per stream) -> its checked rows, int64 arrays of length >= 1; None for every other first_samples.  Such a
+        list never reaches torch.as_tensor."""
+        from mi355_wavenet import engine
+        if not engine.is_ragged_prompt(first_samples):
+            return None
+        return engine.ragged_rows(first_samples, self.classes, min_length=1)[0]
+
+    def _prime_ragged(self, eng, rows):
+        """Fresh queues on ``eng``, then every stream primed with all but the last sample of its row: ONE batched pass (Engine.prime_ragged), or --
+        where the engine cannot -- every prompt alone on a one-stream engine (its batched pass or its chain, whichever it takes) whose saved state is
+        loaded into the stream; slow, and right for every shape.  Returns the right-aligned (streams, longest) matrix of the rows: its last column is
+        every stream's next input."""
+        from mi355_wavenet import engine
+        eng.reset()
+        batched = eng.prime_ragged([r[:-1] for r in rows])
+        if not batched:
+            states = []
+            if any(r.size > 1 for r in rows):
+                one = engine.Engine(self._config(), dict(self.state_dict()), n_streams=1, device_index=self._parameters_key()[0])
+                try:
+                    for r in rows:
+                        if r.size > 1:
+                            one.generate(0, r[None, :], reset=True)   # (num_samples 0: the priming evaluations alone)
+                        states.append(one.state_save(0) if r.size > 1 else None)
+                finally:
+                    one.close()
+            for s, st in enumerate(states):
+                if st is not None:
+                    eng.state_load(st, s, 1)
+        self._wn_last_prime_batched = bool(batched)
+        return engine.right_aligned(rows)
+
     def _prompt(self, first_samples):
         """first_samples (None: the one sample classes // 2, wavenet_model.py:245-247) -> (int64 (n_streams, num_given), whether it came as 2-D rows)"""
         if first_samples is None:
@@ -537,8 +578,15 @@ class WaveNetModel(nn.Module):
         mi355_wavenet/generation.py's"""
         from mi355_wavenet import generation
         self.eval()
-        first, batched = self._prompt(first_samples)
-        n_streams, num_given = first.shape
+        ragged = self._ragged_prompt(first_samples)
+        if ragged is not None and len({r.size for r in ragged}) == 1:   # rows of one length: the 2-D call
+            first_samples, ragged = torch.from_numpy(np.stack(ragged)), None
+        if ragged is not None:
+            first, batched = None, True
+            n_streams, num_given = len(ragged), max(r.size for r in ragged)
+        else:
+            first, batched = self._prompt(first_samples)
+            n_streams, num_given = first.shape
         forced = self._checked_forced(forced, num_samples, rows=n_streams)
         for queue in self.dilated_queues:  # :250-251
             queue.reset()
@@ -550,15 +598,20 @@ class WaveNetModel(nn.Module):
             # priming (:259-269): all n_prime teacher-forced evaluations as ONE batched pass over the given window (C ABI wn_prime: the stack as
             # matrix-core GEMMs over all positions, queues filled from the result); shapes it does not cover take the per-sample chain
             n_prime = num_given - 1
-            primed = n_prime if n_prime >= eng.PRIME_BATCH_MIN and eng.prime_host(first[:, :n_prime]) else 0
-            self._wn_last_prime_batched = primed > 0
+            if ragged is not None:   # prompts of unequal length: all of the priming is behind us either way, the job starts from the last column
+                first = self._prime_ragged(eng, ragged)
+                primed = n_prime
+            else:
+                primed = n_prime if n_prime >= eng.PRIME_BATCH_MIN and eng.prime_host(first[:, :n_prime]) else 0
+                self._wn_last_prime_batched = primed > 0
             steps = generation.generation_schedule(num_given, num_samples, progress_interval, progress_callback is not None, primed, temperature > 0)
             idx, logp = generation.run_schedule(steps, eng, first, temperature, regularize, forced, logprobs, progress_callback, timing_print)
 
             def state():   # behind the last generated sample, whose index is the input of the next step
                 nxt = idx[:, -1] if idx.shape[1] else first[:, -1]
                 before = [st.evals for st in states] if states is not None else [0] * n_streams
-                out = [self._stream_state(eng, s, int(nxt[s]), before[s] + n_prime + num_samples) for s in range(n_streams)]
+                given = [r.size - 1 for r in ragged] if ragged is not None else [n_prime] * n_streams   # (a stream's own priming evaluations)
+                out = [self._stream_state(eng, s, int(nxt[s]), before[s] + given[s] + num_samples) for s in range(n_streams)]
                 return out if batched else out[0]
             return self._finish(eng, idx, logp, squeeze=not batched, state=state if return_state else None)
 
@@ -607,15 +660,21 @@ class WaveNetModel(nn.Module):
         with the queues loaded into every stream instead of reset; together with first_samples it is a ValueError.
         return_logprobs as in generate_fast: returns (audio, logp), logp float32 (len(temperatures), num_samples); a greedy row holds the log-softmax
         value of its argmax.
-        forced as in generate_fast: (num_samples,) shared by all rows, or (len(temperatures), num_samples); -1 is a free position."""
+        forced as in generate_fast: (num_samples,) shared by all rows, or (len(temperatures), num_samples); -1 is a free position.
+        first_samples as a list or tuple of len(temperatures) 1-D sequences (of any lengths >= 1): one prompt per temperature, all primed in one batched
+        pass (generate_fast's ragged prompts); a 1-D prompt stays shared and is primed once.  The rows' draws and the deferred dilated_queues (the
+        last stream's) are as without it."""
         logprobs = self._logprob_mode(return_logprobs)
         self._checked_forced(forced, num_samples, rows=len(temperatures))   # (checked here, before an engine is touched; Engine.generate makes the rows)
         states, first_samples = self._continuation("generate_fast_streams", continue_from, first_samples)
         if states is not None and len(states) != 1:
             raise ValueError("generate_fast_streams: continue_from is ONE state that all temperatures share")
+        ragged = self._ragged_prompt(first_samples)
+        if ragged is not None and len(ragged) != len(temperatures):
+            raise ValueError("generate_fast_streams: a list of prompts holds one per temperature (%d), got %d" % (len(temperatures), len(ragged)))
         self.eval()
         temps = [float(t) for t in temperatures]
-        first = np.repeat(self._prompt(first_samples)[0].reshape(1, -1), len(temps), axis=0)
+        first = None if ragged is not None else np.repeat(self._prompt(first_samples)[0].reshape(1, -1), len(temps), axis=0)
         for queue in self.dilated_queues:
             queue.reset()
         eng = self._engine(len(temps))
@@ -627,9 +686,11 @@ class WaveNetModel(nn.Module):
             if states is not None:
                 eng.reset()
                 eng.state_load(states[0].state)   # one state, every stream
+            if ragged is not None:   # one prompt per temperature: primed here, the job starts from every stream's last given sample
+                first = self._prime_ragged(eng, ragged)[:, -1:]
             out = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
-                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=states is None, logprobs=logprobs, forced=forced,
-                               shared_prompt=self.SHARED_PRIME and states is None and eng.lib.has("wn_prime_shared"))
+                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=states is None and ragged is None, logprobs=logprobs,
+                               forced=forced, shared_prompt=self.SHARED_PRIME and states is None and ragged is None and eng.lib.has("wn_prime_shared"))
         idx, logp = out if logprobs is not None else (out, None)
         return self._finish(eng, idx, logp, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
 
@@ -650,6 +711,9 @@ class WaveNetModel(nn.Module):
         if states is not None:
             if first_samples.ndim != idx.ndim or (idx.ndim == 2 and len(states) != idx.shape[0]):
                 raise ValueError("score_continuation: one GenerationState for 1-D indices, a list of one per row for 2-D indices")
+        elif self._ragged_prompt(first_samples) is not None:   # one prompt per row, of any lengths
+            if idx.ndim != 2 or len(first_samples) != idx.shape[0]:
+                raise ValueError("score_continuation: a list of prompts needs 2-D indices with one row per prompt")
         elif first_samples is not None and idx.ndim == 2:
             rows = torch.as_tensor(first_samples)
             if rows.ndim != 2 or rows.shape[0] != idx.shape[0]:
