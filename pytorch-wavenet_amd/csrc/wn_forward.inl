@@ -1,12 +1,22 @@
 // wn_forward.inl -- host side of the batched forward (included by wn_runtime.hip; GPU build only): the launchers of the matrix products of
 // wn_forward.h, wn_forward / wn_score (WaveNetModel.forward() for one-hot inputs), wn_prime (batched priming of the generation queues).
+#include <assert.h>
 
 // One "NN" product C = A . B^T of wn_forward.h.  bn != NULL: bf16 operands (B given as [N][K] bf16 -- or as two [N][ldb] halves
 // bn / bn1 --, A rounded while staged), fp32 accumulation; else fp32 operands.  Products with N % 256 == 0 take the 128 x 256 tile.
-static void wn_launch_nn(hipStream_t st, int epi, const WnGemmArgs& a, const unsigned short* bn = nullptr, const unsigned short* bn1 = nullptr, int ldb = 0) {
+// rg != NULL: the same tiles under the ragged row map (wn_forward.h: WnRagged; a.M = the table's total, a.rows_per_batch unused) -- kernels that exist
+// for fp32 operands and the GATE / PLAIN epilogues only.
+static void wn_launch_nn(hipStream_t st, int epi, const WnGemmArgs& a, const unsigned short* bn = nullptr, const unsigned short* bn1 = nullptr, int ldb = 0,
+                         const WnRagged* rg = nullptr) {
     const bool wide = bn && a.N % 256 == 0 && epi != WN_EPI_GATE_BWD;
     const unsigned mt = (unsigned)((a.M + 127) / 128), nt = (unsigned)(wide ? a.N / 256 : (a.N + 127) / 128);
     const dim3 grid(mt * nt);   // 1-D (M / 128 can exceed a grid's y limit): row tiles fastest, then column tiles
+    if (rg) {
+        assert(!bn && (epi == WN_EPI_GATE || epi == WN_EPI_PLAIN));
+        if (epi == WN_EPI_GATE) hipLaunchKernelGGL(wn_fwd_gemm_ragged<WN_EPI_GATE>, grid, dim3(256), 0, st, a, *rg);
+        else hipLaunchKernelGGL(wn_fwd_gemm_ragged<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a, *rg);
+        return;
+    }
     if (bn) {
         WnGemmArgsBf16 b;
         b.g = a; b.bn = bn; b.bn1 = bn1; b.ldb = ldb;
@@ -28,23 +38,13 @@ static void wn_launch_nn(hipStream_t st, int epi, const WnGemmArgs& a, const uns
     else hipLaunchKernelGGL(wn_fwd_gemm<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a);
 }
 
-// The filter/gate product of a layer with kernel_size 3 or 4 (wn_fwd_gemm_taps: fp32 operands, the 128 x 128 tile)
-static void wn_launch_taps(hipStream_t st, int taps, const WnTapsArgs& a) {
+// The filter/gate product of a layer with kernel_size 3 or 4 (wn_fwd_gemm_taps: fp32 operands, the 128 x 128 tile), under the ragged row map where rg != NULL
+static void wn_launch_taps(hipStream_t st, int taps, const WnTapsArgs& a, const WnRagged* rg = nullptr) {
     const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)((a.g.N + 127) / 128));
-    if (taps == 3) hipLaunchKernelGGL(wn_fwd_gemm_taps<3>, grid, dim3(256), 0, st, a);
+    if (rg && taps == 3) hipLaunchKernelGGL(wn_fwd_gemm_taps_ragged<3>, grid, dim3(256), 0, st, a, *rg);
+    else if (rg) hipLaunchKernelGGL(wn_fwd_gemm_taps_ragged<4>, grid, dim3(256), 0, st, a, *rg);
+    else if (taps == 3) hipLaunchKernelGGL(wn_fwd_gemm_taps<3>, grid, dim3(256), 0, st, a);
     else hipLaunchKernelGGL(wn_fwd_gemm_taps<4>, grid, dim3(256), 0, st, a);
-}
-
-// The fp32 products of wn_prime_ragged: the same tiles under the ragged row map `rg` (wn_forward.h: WnRagged; a.M = the table's total, a.rows_per_batch unused)
-static void wn_launch_nn_ragged(hipStream_t st, int epi, const WnGemmArgs& a, const WnRagged& rg) {
-    const dim3 grid((unsigned)((a.M + 127) / 128) * (unsigned)((a.N + 127) / 128));
-    if (epi == WN_EPI_GATE) hipLaunchKernelGGL(wn_fwd_gemm_ragged<WN_EPI_GATE>, grid, dim3(256), 0, st, a, rg);
-    else hipLaunchKernelGGL(wn_fwd_gemm_ragged<WN_EPI_PLAIN>, grid, dim3(256), 0, st, a, rg);
-}
-static void wn_launch_taps_ragged(hipStream_t st, int taps, const WnTapsArgs& a, const WnRagged& rg) {
-    const dim3 grid((unsigned)((a.g.M + 127) / 128) * (unsigned)((a.g.N + 127) / 128));
-    if (taps == 3) hipLaunchKernelGGL(wn_fwd_gemm_taps_ragged<3>, grid, dim3(256), 0, st, a, rg);
-    else hipLaunchKernelGGL(wn_fwd_gemm_taps_ragged<4>, grid, dim3(256), 0, st, a, rg);
 }
 
 // The same product on bf16 operands (wn_fwd_gemm_taps_bf16): bn = the layer's block of the bf16 bank, [N][taps * R]; N % 256 == 0 takes the
@@ -370,78 +370,117 @@ extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* tar
 // outputs) and the newest (k-1)*d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
 // (queue time 0); activations before the stream start are zero at every layer, like DilatedQueue.reset().
 //
-// The body of wn_prime and wn_prime_shared.  `h` (a handle with rings, not a front of rounds) runs the products on its weights and in its workspace, over
-// the rows of `first_samples`: one per stream of h (wn_prime: fill = {h}), or ONE row whose result the ring fill hands to every stream and copy of every
-// handle of `fill` (shared: h's own rings are filled only if it is listed; the members of a front share their weights, so member 0 computes for all).
-static int wn_prime_run(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, bool shared, wn_handle* const* fill, size_t n_fill,
-                        void* hip_stream, const char* who) {
+// Three entry points, one pass.  What a pass does is decided on the host by wn_prime_plan_host (wn_plan.h: WnPrimePlan, plain arithmetic, tested with g++);
+// wn_prime_pass carries the plan out.  The forms differ in what they plan and in their checks, which stay with the entry points:
+//   wn_prime         one row of samples per stream, all of one length: the rectangle
+//   wn_prime_shared  ONE row for all streams: the rectangle of one stream, whose result the ring fill hands to every stream and copy of every handle listed
+//   wn_prime_ragged  one row per stream, right-aligned at the queue time n = the longest: the ragged row tables -- or the rectangle where all lengths are n
+static int wn_need_forward_kernels(const wn_handle* h, const char* who) {
+    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
+    return WN_OK;
+}
+
+// The ragged form's row tables, host side: pinned staging that the copy before this one may still be reading (the event says when it is done), one device image
+static int wn_prime_stage_tables(wn_handle* h, const WnRaggedPlan& rp, const char* who) {
+    const size_t n_tab = rp.start.size();
+    if (!h->ragged_ev) { int rc = rt_hip(hipEventCreateWithFlags(&h->ragged_ev, hipEventDisableTiming), "hipEventCreate"); if (rc) { h->ragged_ev = nullptr; return rc; } }
+    else { int rc = rt_hip(hipEventSynchronize(h->ragged_ev), "hipEventSynchronize(row tables)"); if (rc) return rc; }
+    if (h->ragged_ints < n_tab) {
+        { int rc = rt_hip(hipDeviceSynchronize(), "hipDeviceSynchronize"); if (rc) return rc; }   // (kernels of an earlier pass may still read the old image)
+        if (h->ragged_host) (void)hipHostFree(h->ragged_host);
+        h->ragged_host = nullptr;
+        if (hipHostMalloc((void**)&h->ragged_host, n_tab * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { h->ragged_host = nullptr; h->ragged_ints = 0; return wn_fail(WN_E_NOMEM, "%s: row tables", who); }
+        if (!rt_grow(h->d_ragged, h->ragged_ints, n_tab)) return wn_fail(WN_E_NOMEM, "%s: row tables", who);
+    }
+    memcpy(h->ragged_host, rp.start.data(), n_tab * sizeof(int32_t));
+    return WN_OK;
+}
+
+// One planned pass.  `h` (a handle with rings, not a front of rounds; checked by the entry point, its device current) runs the products on its weights and in
+// its workspace over the rows of `samples` (row_stride apart), and the ring fill writes every layer's newest columns into the rings of the handles of `fill`:
+// {h}, or (shared: the plan is one stream's, read with a stream stride of 0) every handle that takes the one row's result -- the members of a front share
+// their weights, so member 0 computes for all, and h's own rings are filled only if it is listed.  A row before a stream's start is never computed: both
+// halves of the cleared workspace read as zero there at every layer, which is what a reset queue holds.
+static int wn_prime_pass(const WnPrimePlan& pp, wn_handle* h, const int32_t* samples, int64_t row_stride, bool shared, wn_handle* const* fill, size_t n_fill,
+                         void* hip_stream, const char* who) {
+    const WnPlan& pl = h->plan;
+    const int R = pl.R, D = pl.D, ns = pp.ns;
+    const long long n = pp.n, Lp = pp.Lp, Lt = pp.Lt;   // every stream's activation rows are preceded by Lp rows of zeros (t < 0): the oldest tap's reach
+    const bool ragged = !pp.rectangle;
+    if (h->ws_floats < pp.total_floats && !rt_grow(h->d_ws, h->ws_floats, pp.total_floats)) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, pp.total_floats * 4e-6);
+    if (ragged) { int rc = wn_prime_stage_tables(h, pp.ragged, who); if (rc) return rc; }
+    float* xa = h->d_ws; float* xb = xa + pp.x_floats; float* z = xb + pp.x_floats;
+    hipStream_t st = (hipStream_t)hip_stream;
+    int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * pp.x_floats * 4, st), "hipMemsetAsync(prime workspace)");
+    if (rc) return rc;
+    if (ragged) {   // the row tables of all layers, uploaded once
+        rc = rt_hip(hipMemcpyAsync(h->d_ragged, h->ragged_host, pp.ragged.start.size() * sizeof(int32_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(row tables)");
+        if (rc) return rc;
+        rc = rt_hip(hipEventRecord(h->ragged_ev, st), "hipEventRecord(row tables)");
+        if (rc) return rc;
+    }
+    auto table = [&](int t) { return WnRagged{h->d_ragged + (size_t)t * (ns + 1), ns, (int)n}; };
+    // x0 = the start_conv column gather over all given positions; rows of stream s start at xa + s*Lt*R + Lp*R
+    if (ragged) {   // ONE launch over every stream's own rows
+        const long long work = pp.start_rows * (R / 4);
+        if (work > 0)
+            hipLaunchKernelGGL(wn_fwd_start_ragged, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, samples, (long long)row_stride, h->w.d_start_t,
+                               pl.has_bias ? h->w.d_start_b : nullptr, xa + Lp * R, Lt * R, table(0), pp.start_rows, R);
+    } else {
+        for (int s = 0; s < ns; ++s) {
+            const long long work = n * (R / 4);
+            hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, samples + (size_t)s * row_stride,
+                               h->w.d_start_t, pl.has_bias ? h->w.d_start_b : nullptr, xa + ((size_t)s * Lt + Lp) * R, n, R);
+        }
+    }
+    const float* fw = h->w.d_fw;
+    float* xin = xa; float* xout = xb;
+    for (int l = 0; l < pp.NL; ++l) {
+        const WnPrimeLayer& y = pp.layer[l];
+        for (size_t i = 0; i < n_fill; ++i) {   // queue of layer l <- newest min(k1*d+1, n) columns of its input: zeros where a stream had not started
+            const wn_handle* f = fill[i];
+            const int nf = f->plan.n_streams;
+            const long long work = (long long)nf * y.fill_cols * (R / 4);
+            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, shared ? 0 : Lt * R,
+                               f->d_rings + f->ring_off[l], R, y.ML, nf, f->plan.P, n, y.fill_cols);
+        }
+        if (l == pp.NL - 1) break;
+        if (y.M > 0) {
+            // the plan's row maps (x: t - d may be negative: those rows are the zero prefix).  Ragged: every map counts rows from the stream's time 0, the
+            // kernels put (stream, time) where (batch entry, row) stand
+            const long long d = h->dil[l];
+            const WnRowMap zmap = wn_rows(z, y.z_rows, D), x = WnRowMap{xin + Lp * R, Lt * R, R, y.t0}, xo = WnRowMap{xout + Lp * R, Lt * R, R, y.t0};
+            const WnRagged tab = ragged ? table(1 + l) : WnRagged{nullptr, 0, 0};
+            const WnRagged* rg = ragged ? &tab : nullptr;
+            if (pl.k == 2) wn_launch_nn(st, WN_EPI_GATE, wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, y.entries, y.rows), nullptr, nullptr, 0, rg);
+            else wn_launch_taps(st, pl.k, wn_layer_fg_taps(pl, h->w.fw, fw, l, x, d, zmap, y.entries, y.rows, -Lp), rg);
+            wn_launch_nn(st, WN_EPI_PLAIN, wn_layer_res(pl, h->w.fw, fw, l, zmap, x, xo, y.entries, y.rows), nullptr, nullptr, 0, rg);
+        }
+        float* t = xin; xin = xout; xout = t;
+    }
+    rc = rt_hip(hipGetLastError(), ragged ? "wn_prime_ragged launches" : "wn_prime launches");
+    if (rc) return rc;
+    for (size_t i = 0; i < n_fill; ++i) fill[i]->t_base = n;
+    return WN_OK;
+}
+
+// The checks and the plan of wn_prime and wn_prime_shared (ns = 1), in their order: nothing to do for n_prime == 0 before the kernels or the queue time matter
+static int wn_prime_rectangle(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, bool shared, wn_handle* const* fill, size_t n_fill,
+                              void* hip_stream, const char* who) {
     if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
     if (n_prime < 0 || row_stride < n_prime) return wn_fail(WN_E_BADARG, "%s: bad n_prime / row_stride", who);
     if (n_prime == 0) return WN_OK;
-    const WnPlan& pl = h->plan;
-    const int R = pl.R, D = pl.D, NL = pl.NL, ns = shared ? 1 : pl.n_streams;
-    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
-    const long long k1 = pl.k - 1;   // a layer's queue holds k1 * d + 1 columns, its conv reaches k1 * d positions back
+    { int rc = wn_need_forward_kernels(h, who); if (rc) return rc; }
     if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
     for (size_t i = 0; i < n_fill; ++i) {
         if (fill[i]->pending) { int rc = wn_wait(fill[i]); if (rc) return rc; }
         if (fill[i]->t_base != 0) return wn_fail(WN_E_STATE, "%s: queues must be freshly reset (queue time is %lld)", who, fill[i]->t_base);
     }
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
-    const long long n = n_prime;
-    if ((long long)ns * n >= 0x7fffffffll) return wn_fail(WN_E_UNSUPPORTED, "%s: too many rows", who);
-    // q[i] = trailing positions of layer i's input that are needed (its own queue: k1*d+1, and what the layers above need)
-    std::vector<long long> q(NL + 1, 0);
-    for (int l = NL - 1; l >= 0; --l) {
-        const long long d = h->dil[l];
-        long long v = q[l + 1] > 0 ? q[l + 1] + k1 * d : 0;
-        if (v < k1 * d + 1) v = k1 * d + 1;
-        q[l] = v < n ? v : n;
-    }
-    long long max_d = 1;
-    for (int l = 0; l < NL; ++l) max_d = h->dil[l] > max_d ? h->dil[l] : max_d;
-    const long long Lp = k1 * max_d, Lt = Lp + n;  // every stream's activation rows are preceded by Lp rows of zeros (t < 0): the oldest tap's reach
-    const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
-    const size_t total = 2 * x_fl + z_fl;
-    if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
-    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl;
-    hipStream_t st = (hipStream_t)hip_stream;
-    int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * x_fl * 4, st), "hipMemsetAsync(prime workspace)");
-    if (rc) return rc;
-    // x0 = start_conv column gather over all given positions; rows of stream s start at xa + s*Lt*R + Lp*R
-    for (int s = 0; s < ns; ++s) {
-        const long long work = n * (R / 4);
-        hipLaunchKernelGGL(wn_fwd_start, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, first_samples + (size_t)s * row_stride,
-                           h->w.d_start_t, pl.has_bias ? h->w.d_start_b : nullptr, xa + ((size_t)s * Lt + Lp) * R, n, R);
-    }
-    const float* fw = h->w.d_fw;
-    float* xin = xa; float* xout = xb;
-    for (int l = 0; l < NL; ++l) {
-        const long long d = h->dil[l];
-        const int ML = (int)(k1 * d) + 1;
-        {   // queue of layer l <- newest min(k1*d+1, n) columns of its input
-            const int count = (int)(ML < n ? ML : n);
-            for (size_t i = 0; i < n_fill; ++i) {   // (shared: a stream stride of 0 -- every stream of the target reads the one row of activations)
-                const wn_handle* f = fill[i];
-                const int nf = f->plan.n_streams;
-                const long long work = (long long)nf * count * (R / 4);
-                hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, shared ? 0 : Lt * R,
-                                   f->d_rings + f->ring_off[l], R, ML, nf, f->plan.P, n, count);
-            }
-        }
-        const long long rows = q[l + 1];
-        if (l == NL - 1 || rows <= 0) break;
-        const long long t0 = n - rows;
-        const WnRowMap zmap = wn_rows(z, rows, D), x = WnRowMap{xin + Lp * R, Lt * R, R, t0};   // (x: t - d may be negative: those rows are the zero prefix)
-        if (pl.k == 2) wn_launch_nn(st, WN_EPI_GATE, wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, ns, rows));
-        else wn_launch_taps(st, pl.k, wn_layer_fg_taps(pl, h->w.fw, fw, l, x, d, zmap, ns, rows, -Lp));
-        wn_launch_nn(st, WN_EPI_PLAIN, wn_layer_res(pl, h->w.fw, fw, l, zmap, x, WnRowMap{xout + Lp * R, Lt * R, R, t0}, ns, rows));
-        float* t = xin; xin = xout; xout = t;
-    }
-    rc = rt_hip(hipGetLastError(), "wn_prime launches");
-    if (rc) return rc;
-    for (size_t i = 0; i < n_fill; ++i) fill[i]->t_base = n;
-    return WN_OK;
+    WnPrimePlan pp;
+    const std::string why = wn_prime_plan_host(h->dil.data(), h->plan.NL, h->plan.k, h->plan.R, h->plan.D, nullptr, shared ? 1 : h->plan.n_streams, n_prime, pp);
+    if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
+    return wn_prime_pass(pp, h, first_samples, row_stride, shared, fill, n_fill, hip_stream, who);
 }
 
 extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_prime, int64_t row_stride, void* hip_stream) {
@@ -457,95 +496,26 @@ extern "C" int wn_prime(wn_handle* h, const int32_t* first_samples, int64_t n_pr
         h->t_base = h->chains[0]->t_base;
         return WN_OK;
     }
-    return wn_prime_run(h, first_samples, n_prime, row_stride, false, &h, 1, hip_stream, "wn_prime");
+    return wn_prime_rectangle(h, first_samples, n_prime, row_stride, false, &h, 1, hip_stream, "wn_prime");
 }
 
 // ---- wn_prime_ragged: prompts of unequal length in one batched pass, right-aligned at the queue time n (include/wn_abi.h has the contract).
 // What one handle with rings must satisfy before anything is launched -- a front checks EVERY member first, so that an error leaves all of them untouched.
 static int wn_prime_ragged_check(wn_handle* h, const char* who) {
     if (!h->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
-    if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
+    { int rc = wn_need_forward_kernels(h, who); if (rc) return rc; }
     if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
     if (h->t_base != 0) return wn_fail(WN_E_STATE, "%s: queues must be freshly reset (queue time is %lld)", who, h->t_base);
     return WN_OK;
 }
-// One handle's streams (checked: wn_prime_ragged_check; lengths in [0, row_stride], n = the queue time all streams of the job end at, >= every length).
-// wn_prime_run's pass with three differences: ONE start launch for all streams, the products run over the streams' own rows only (the row plan of
-// wn_prime_ragged_plan_host, uploaded once for all layers), z is addressed by (stream, time) like x.  A row before a stream's start is never computed:
-// both halves of the cleared workspace read as zero there at every layer, which is what a reset queue holds -- nothing is computed and zeroed afterwards.
-static int wn_prime_ragged_run(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, long long n, void* hip_stream, const char* who) {
-    const WnPlan& pl = h->plan;
-    const int R = pl.R, D = pl.D, NL = pl.NL, ns = pl.n_streams;
-    bool equal = true;
-    for (int s = 0; s < ns; ++s) equal = equal && n_prime[s] == n;
-    if (equal) return wn_prime_run(h, first_samples, n, row_stride, false, &h, 1, hip_stream, who);   // (the rectangle: wn_prime's own pass, bit for bit)
-    WnRaggedPlan rp;
-    const std::string why = wn_prime_ragged_plan_host(h->dil.data(), NL, pl.k, n_prime, ns, n, rp);
+// One handle's streams (checked: wn_prime_ragged_check; lengths in [0, row_stride], n = the queue time all streams of the job end at, > 0 and >= every length).
+// Streams of one length n plan as the rectangle: wn_prime's own launches, bit for bit, no row tables.
+static int wn_prime_ragged_member(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, long long n, void* hip_stream, const char* who) {
+    WnPrimePlan pp;
+    const std::string why = wn_prime_plan_host(h->dil.data(), h->plan.NL, h->plan.k, h->plan.R, h->plan.D, n_prime, h->plan.n_streams, n, pp);
     if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
     { int rc = rt_hip(hipSetDevice(h->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
-    const long long k1 = pl.k - 1;
-    long long max_d = 1;
-    for (int l = 0; l < NL; ++l) max_d = h->dil[l] > max_d ? h->dil[l] : max_d;
-    const long long Lp = k1 * max_d, Lt = Lp + n;   // (wn_prime_run's rectangle: Lp rows of zeros in front of every stream's time 0)
-    const size_t x_fl = (size_t)ns * Lt * R, z_fl = (size_t)ns * n * D;
-    const size_t total = 2 * x_fl + z_fl;
-    if (h->ws_floats < total && !rt_grow(h->d_ws, h->ws_floats, total)) return wn_fail(WN_E_NOMEM, "%s: workspace of %.1f MB", who, total * 4e-6);
-    // the row tables: pinned staging that the copy before this one may still be reading (the event says when it is done), one device image
-    const size_t n_tab = rp.start.size();
-    if (!h->ragged_ev) { int rc = rt_hip(hipEventCreateWithFlags(&h->ragged_ev, hipEventDisableTiming), "hipEventCreate"); if (rc) { h->ragged_ev = nullptr; return rc; } }
-    else { int rc = rt_hip(hipEventSynchronize(h->ragged_ev), "hipEventSynchronize(row tables)"); if (rc) return rc; }
-    if (h->ragged_ints < n_tab) {
-        { int rc = rt_hip(hipDeviceSynchronize(), "hipDeviceSynchronize"); if (rc) return rc; }   // (kernels of an earlier pass may still read the old image)
-        if (h->ragged_host) (void)hipHostFree(h->ragged_host);
-        h->ragged_host = nullptr;
-        if (hipHostMalloc((void**)&h->ragged_host, n_tab * sizeof(int32_t), hipHostMallocDefault) != hipSuccess) { h->ragged_host = nullptr; h->ragged_ints = 0; return wn_fail(WN_E_NOMEM, "%s: row tables", who); }
-        if (!rt_grow(h->d_ragged, h->ragged_ints, n_tab)) return wn_fail(WN_E_NOMEM, "%s: row tables", who);
-    }
-    memcpy(h->ragged_host, rp.start.data(), n_tab * sizeof(int32_t));
-    float* xa = h->d_ws; float* xb = xa + x_fl; float* z = xb + x_fl;
-    hipStream_t st = (hipStream_t)hip_stream;
-    int rc = rt_hip(hipMemsetAsync(xa, 0, 2 * x_fl * 4, st), "hipMemsetAsync(prime workspace)");
-    if (rc) return rc;
-    rc = rt_hip(hipMemcpyAsync(h->d_ragged, h->ragged_host, n_tab * sizeof(int32_t), hipMemcpyHostToDevice, st), "hipMemcpyAsync(row tables)");
-    if (rc) return rc;
-    rc = rt_hip(hipEventRecord(h->ragged_ev, st), "hipEventRecord(row tables)");
-    if (rc) return rc;
-    auto table = [&](int t) { return WnRagged{h->d_ragged + (size_t)t * (ns + 1), ns, (int)n}; };
-    if (rp.total[0] > 0) {   // x0 = the start_conv column gather over every stream's given positions
-        const long long work = rp.total[0] * (R / 4);
-        hipLaunchKernelGGL(wn_fwd_start_ragged, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, first_samples, (long long)row_stride, h->w.d_start_t,
-                           pl.has_bias ? h->w.d_start_b : nullptr, xa + Lp * R, Lt * R, table(0), rp.total[0], R);
-    }
-    const float* fw = h->w.d_fw;
-    float* xin = xa; float* xout = xb;
-    for (int l = 0; l < NL; ++l) {
-        const long long d = h->dil[l];
-        const int ML = (int)(k1 * d) + 1;
-        {   // queue of layer l <- newest min(k1*d+1, n) columns of its input: zeros where the stream had not started
-            const int count = (int)(ML < n ? ML : n);
-            const long long work = (long long)ns * count * (R / 4);
-            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, Lt * R, h->d_rings + h->ring_off[l], R, ML, ns, pl.P, n, count);
-        }
-        if (l == NL - 1) break;
-        const long long M = rp.total[1 + l];
-        if (M > 0) {
-            // every map counts rows from the stream's time 0 (t0 = 0): the kernels put (stream, time) where (batch entry, row) stand
-            const WnRowMap zmap = wn_rows(z, n, D), x = WnRowMap{xin + Lp * R, Lt * R, R, 0}, xo = WnRowMap{xout + Lp * R, Lt * R, R, 0};
-            const WnRagged rg = table(1 + l);
-            if (pl.k == 2) {
-                WnGemmArgs a = wn_layer_fg(pl, h->w.fw, fw, l, x, d, zmap, 1, M);
-                wn_launch_nn_ragged(st, WN_EPI_GATE, a, rg);
-            } else {
-                wn_launch_taps_ragged(st, pl.k, wn_layer_fg_taps(pl, h->w.fw, fw, l, x, d, zmap, 1, M, -Lp), rg);
-            }
-            wn_launch_nn_ragged(st, WN_EPI_PLAIN, wn_layer_res(pl, h->w.fw, fw, l, zmap, x, xo, 1, M), rg);
-        }
-        float* t = xin; xin = xout; xout = t;
-    }
-    rc = rt_hip(hipGetLastError(), "wn_prime_ragged launches");
-    if (rc) return rc;
-    h->t_base = n;
-    return WN_OK;
+    return wn_prime_pass(pp, h, first_samples, row_stride, false, &h, 1, hip_stream, who);
 }
 
 extern "C" int wn_prime_ragged(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, void* hip_stream) {
@@ -564,7 +534,7 @@ extern "C" int wn_prime_ragged(wn_handle* h, const int32_t* first_samples, const
         if (n == 0) return WN_OK;
         for (size_t i = 0; i < h->chains.size(); ++i) {   // every member ends at the front's n, also one whose own streams are all shorter
             const size_t s0 = (size_t)h->chain_first[i];
-            int rc = wn_prime_ragged_run(h->chains[i], first_samples + s0 * (size_t)row_stride, n_prime + s0, row_stride, n, hip_stream, "wn_prime_ragged");
+            int rc = wn_prime_ragged_member(h->chains[i], first_samples + s0 * (size_t)row_stride, n_prime + s0, row_stride, n, hip_stream, "wn_prime_ragged");
             if (rc) { if (i) h->broken = true; return rc; }   // (members before this one have moved on: as after a job that failed between its rounds)
         }
         h->t_base = h->chains[0]->t_base;
@@ -572,7 +542,7 @@ extern "C" int wn_prime_ragged(wn_handle* h, const int32_t* first_samples, const
     }
     { int rc = wn_prime_ragged_check(h, "wn_prime_ragged"); if (rc) return rc; }
     if (n == 0) return WN_OK;
-    return wn_prime_ragged_run(h, first_samples, n_prime, row_stride, n, hip_stream, "wn_prime_ragged");
+    return wn_prime_ragged_member(h, first_samples, n_prime, row_stride, n, hip_stream, "wn_prime_ragged");
 }
 
 // wn_prime for a prompt that every stream shares: ONE row of given samples, the stack's products once over it (the workspace of a 1-stream prime), the ring
@@ -583,12 +553,12 @@ extern "C" int wn_prime_shared(wn_handle* h, const int32_t* first_samples, int64
     if (!h->chains.empty()) {
         if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
         if (h->broken) return wn_fail(WN_E_STATE, "wn_prime_shared: an earlier job failed half way through its rounds; call wn_reset");
-        int rc = wn_prime_run(h->chains[0], first_samples, n_prime, n_prime, true, h->chains.data(), h->chains.size(), hip_stream, "wn_prime_shared");
+        int rc = wn_prime_rectangle(h->chains[0], first_samples, n_prime, n_prime, true, h->chains.data(), h->chains.size(), hip_stream, "wn_prime_shared");
         if (rc) return rc;
         h->t_base = h->chains[0]->t_base;
         return WN_OK;
     }
-    return wn_prime_run(h, first_samples, n_prime, n_prime, true, &h, 1, hip_stream, "wn_prime_shared");
+    return wn_prime_rectangle(h, first_samples, n_prime, n_prime, true, &h, 1, hip_stream, "wn_prime_shared");
 }
 
 // Operand precision of wn_forward's / wn_score's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),

@@ -740,11 +740,19 @@ static inline std::string wn_forward_geometry_host(const int32_t* dil, int NL, l
     }
     return std::string();
 }
-// ---- row plan of wn_prime_ragged (wn_forward.inl): batched priming of streams whose prompts differ in length, right-aligned at queue time n.
+// ---- batched priming (wn_forward.inl: wn_prime, wn_prime_shared, wn_prime_ragged).  need[i] = trailing positions of layer i's input that the queues above
+// can still see: its own queue's (k - 1) d + 1 columns, and (k - 1) d positions behind what layer i + 1 needs.  need[0] is the receptive field, need[NL] = 0
+// (the last layer's output is never consumed).  A stream of n samples computes min(need[i], n) of them.
+static inline std::vector<long long> wn_prime_need(const int32_t* dil, int NL, int kernel_size) {
+    const long long k1 = kernel_size - 1;
+    std::vector<long long> need(NL + 1, 0);
+    for (int l = NL - 1; l >= 0; --l) need[l] = need[l + 1] > 0 ? need[l + 1] + k1 * dil[l] : k1 * dil[l] + 1;
+    return need;
+}
+// ---- row plan of the ragged form: batched priming of streams whose prompts differ in length, right-aligned at queue time n.
 // Stream s holds n_prime[s] given samples at the times [n - n_prime[s], n); before its start its activations are zero at every layer (rows that are
 // never computed, in a workspace that is cleared first).  Table 0 describes the start_conv gather (n_prime[s] rows per stream), table 1 + l the two
-// products of layer l (l = 0 .. NL - 2; the last layer's output is never consumed): stream s computes the trailing min(need[l + 1], n_prime[s]) rows,
-// need[i] = trailing positions of layer i's input that the queues above can still see (wn_prime's q before its clamp to n).  A table is the prefix
+// products of layer l (l = 0 .. NL - 2): stream s computes the trailing min(need[l + 1], n_prime[s]) rows.  A table is the prefix
 // sums of its streams' row counts, start[0 .. ns] (start[ns] = the product's M); a stream without rows repeats a start.  Row m of a product belongs
 // to the LAST stream s with start[s] <= m and stands for the time n - rows_s + (m - start[s]) of that stream (wn_ragged_find, wn_forward.h).
 // THIS is what keeps the kernels' addresses inside the workspace: every time lies in [n - n_prime[s], n), every stream in [0, ns).
@@ -760,19 +768,12 @@ struct WnRaggedPlan {
 };
 // Returns "" and fills p, or why not: a length outside [0, n], or ns * n at / above 2^31 rows (the bound of wn_prime: rows are 32-bit in the kernels).
 static inline std::string wn_prime_ragged_plan_host(const int32_t* dil, int NL, int kernel_size, const int64_t* n_prime, int ns, long long n, WnRaggedPlan& p) {
-    const long long k1 = kernel_size - 1;
     if (NL < 1 || ns < 1 || n < 0) return "no layers, no streams or a negative queue time";
     for (int s = 0; s < ns; ++s)
         if (n_prime[s] < 0 || n_prime[s] > n) return "stream " + std::to_string(s) + ": length " + std::to_string((long long)n_prime[s]) + " outside [0, " + std::to_string(n) + "]";
     if ((long long)ns * n >= 0x7fffffffll) return "too many rows (n_streams * n must stay below 2^31)";
     p.ns = ns; p.n_tables = NL; p.n = n;
-    p.need.assign(NL + 1, 0);
-    for (int l = NL - 1; l >= 0; --l) {   // (wn_prime's q, not clamped: the clamp is per stream here)
-        const long long d = dil[l];
-        long long v = p.need[l + 1] > 0 ? p.need[l + 1] + k1 * d : 0;
-        if (v < k1 * d + 1) v = k1 * d + 1;
-        p.need[l] = v;
-    }
+    p.need = wn_prime_need(dil, NL, kernel_size);
     p.start.assign((size_t)NL * (ns + 1), 0);
     p.total.assign(NL, 0);
     for (int t = 0; t < NL; ++t) {
@@ -785,6 +786,67 @@ static inline std::string wn_prime_ragged_plan_host(const int32_t* dil, int NL, 
         }
         st[ns] = (int32_t)sum;
         p.total[t] = sum;
+    }
+    return std::string();
+}
+// ---- the pass plan: everything wn_prime_pass (wn_forward.inl) does for one handle's streams, as numbers.  Every stream owns Lt = Lp + n rows of the two
+// ping-pong activation buffers: Lp = (k - 1) max_d rows of zeros (the oldest tap's reach below time 0), then the times [0, n).  Layer l's queue takes the
+// newest fill_cols = min(ML, n) columns of its input; its two products (l < NL - 1) run over M = entries * rows rows:
+//   the rectangle (n_prime == NULL, or every length == n):  one batch entry per stream, its trailing rows = min(need[l + 1], n) from t0 = n - rows; z is dense,
+//       `rows` high per entry;
+//   the ragged form:  ONE batch entry of total[1 + l] rows under the row tables of `ragged` (stream s: its trailing min(need[l + 1], n_prime[s]) rows, at the
+//       times from first_time on), t0 = 0; z is addressed by (stream, time) like x, n high.
+// Either way every row a product reads or writes lies in [-Lp, n) of its stream, which is what keeps the kernels inside the 2 x + z workspace
+// (tests/ragged_cases.py: check_pass_plan).
+struct WnPrimeLayer {
+    int ML, fill_cols;
+    long long M, entries, rows, t0, z_rows;   // M == 0: no product
+};
+struct WnPrimePlan {
+    int ns = 0, NL = 0;
+    long long n = 0, Lp = 0, Lt = 0;
+    size_t x_floats = 0, z_floats = 0, total_floats = 0;   // one activation buffer, z, and the workspace 2 x + z
+    bool rectangle = true;
+    long long start_rows = 0;             // rows of the start_conv gather: the rectangle's ns launches of n rows, or the ragged form's one launch of total[0]
+    std::vector<long long> need;          // [NL + 1]
+    std::vector<WnPrimeLayer> layer;      // [NL]
+    WnRaggedPlan ragged;                  // filled iff !rectangle
+};
+// n_prime == NULL: every stream has n samples.  Returns "" and fills p, or why not: the rectangle's "too many rows" (ns * n at / above 2^31), or the ragged
+// row plan's refusal.
+static inline std::string wn_prime_plan_host(const int32_t* dil, int NL, int kernel_size, int R, int D, const int64_t* n_prime, int ns, long long n, WnPrimePlan& p) {
+    if (NL < 1 || ns < 1 || n < 0) return "no layers, no streams or a negative queue time";
+    p = WnPrimePlan();
+    for (int s = 0; n_prime && s < ns; ++s) p.rectangle = p.rectangle && n_prime[s] == n;
+    if (p.rectangle) {
+        if ((long long)ns * n >= 0x7fffffffll) return "too many rows";
+    } else {
+        const std::string why = wn_prime_ragged_plan_host(dil, NL, kernel_size, n_prime, ns, n, p.ragged);
+        if (!why.empty()) return why;
+    }
+    const long long k1 = kernel_size - 1;
+    long long max_d = 1;
+    for (int l = 0; l < NL; ++l) max_d = dil[l] > max_d ? dil[l] : max_d;
+    p.ns = ns; p.NL = NL; p.n = n;
+    p.Lp = k1 * max_d; p.Lt = p.Lp + n;
+    p.x_floats = (size_t)ns * p.Lt * R; p.z_floats = (size_t)ns * n * D;
+    p.total_floats = 2 * p.x_floats + p.z_floats;
+    p.start_rows = p.rectangle ? (long long)ns * n : p.ragged.total[0];
+    p.need = wn_prime_need(dil, NL, kernel_size);
+    p.layer.assign(NL, WnPrimeLayer());
+    for (int l = 0; l < NL; ++l) {
+        WnPrimeLayer& y = p.layer[l];
+        y.ML = (int)(k1 * dil[l]) + 1;
+        y.fill_cols = (int)(y.ML < n ? y.ML : n);
+        if (l == NL - 1) continue;
+        if (p.rectangle) {
+            y.entries = ns; y.rows = p.need[l + 1] < n ? p.need[l + 1] : n;
+            y.t0 = n - y.rows; y.z_rows = y.rows;
+        } else {
+            y.entries = 1; y.rows = p.ragged.total[1 + l];
+            y.t0 = 0; y.z_rows = n;
+        }
+        y.M = y.entries * y.rows;
     }
     return std::string();
 }

@@ -1,9 +1,10 @@
-"""The row plan of wn_prime_ragged restated in Python (csrc/wn_plan.h: wn_prime_ragged_plan_host), the properties it must have, and the length sets
-of tests/test_ragged_host.py and tests/test_gpu_ragged_prime.py.  No torch, no engine.
+"""The pass plan of batched priming restated in Python (csrc/wn_plan.h: wn_prime_plan_host, and the ragged form's row plan in it,
+wn_prime_ragged_plan_host), the properties it must have, and the length sets of tests/test_ragged_host.py and tests/test_gpu_ragged_prime.py.
+No torch, no engine.
 
 Streams are right-aligned at the queue time n.  Stream s holds n_prime[s] samples at the times [n - n_prime[s], n).  Table 0 is the start_conv gather
 (n_prime[s] rows), table 1 + l the products of layer l (l = 0 .. NL - 2): the trailing min(need[l + 1], n_prime[s]) rows, need[i] = the trailing
-positions of layer i's input that the queues above can still see."""
+positions of layer i's input that the queues above can still see.  Streams of one length n are the rectangle: no tables, min(need[l + 1], n) rows each."""
 import numpy as np
 
 
@@ -12,16 +13,15 @@ def dilations(layers, blocks):
 
 
 def need_rows(dil, k):
-    """need[0 .. NL]: wn_prime's q before its clamp to n"""
+    """need[0 .. NL] (wn_prime_need): the layer's own queue, (k - 1) d + 1 columns, and (k - 1) d positions behind what the layer above needs"""
     k1, need = k - 1, [0] * (len(dil) + 1)
     for l in range(len(dil) - 1, -1, -1):
-        v = need[l + 1] + k1 * dil[l] if need[l + 1] > 0 else 0
-        need[l] = max(v, k1 * dil[l] + 1)
+        need[l] = need[l + 1] + k1 * dil[l] if need[l + 1] > 0 else k1 * dil[l] + 1
     return need
 
 
 def plan(dil, k, n_prime, n=None):
-    """-> dict(n, need, rows [NL][ns], start [NL][ns + 1], total [NL])"""
+    """the ragged row plan -> dict(n, need, rows [NL][ns], start [NL][ns + 1], total [NL])"""
     n = max(n_prime) if n is None else n
     assert all(0 <= v <= n for v in n_prime)
     need = need_rows(dil, k)
@@ -31,12 +31,57 @@ def plan(dil, k, n_prime, n=None):
 
 
 def prime_rows(dil, k, n):
-    """wn_prime's own rows per layer product (its q[l + 1], clamped to n) for streams of one length n"""
-    k1, q = k - 1, [0] * (len(dil) + 1)
-    for l in range(len(dil) - 1, -1, -1):
-        v = q[l + 1] + k1 * dil[l] if q[l + 1] > 0 else 0
-        q[l] = min(max(v, k1 * dil[l] + 1), n)
-    return q
+    """the rectangle's rows per layer product for streams of one length n: need, clamped to n"""
+    return [min(v, n) for v in need_rows(dil, k)]
+
+
+def pass_plan(dil, k, R, D, n_prime, ns, n):
+    """wn_prime_plan_host (n_prime None: every stream has n) -> dict(ns, n, Lp, Lt, x_floats, z_floats, total_floats, rectangle, start_rows, need,
+    layer [NL] of dict(ML, fill_cols, M, entries, rows, t0, z_rows), ragged: plan() or None)"""
+    NL, k1 = len(dil), k - 1
+    rectangle = n_prime is None or all(v == n for v in n_prime)
+    ragged = None if rectangle else plan(dil, k, n_prime, n)
+    assert ns * n < 2 ** 31 - 1
+    need, Lp = need_rows(dil, k), k1 * max(dil)
+    layer = []
+    for l, d in enumerate(dil):
+        y = dict(ML=k1 * d + 1, fill_cols=min(k1 * d + 1, n), M=0, entries=0, rows=0, t0=0, z_rows=0)
+        if l < NL - 1 and rectangle:
+            rows = min(need[l + 1], n)
+            y.update(entries=ns, rows=rows, t0=n - rows, z_rows=rows)
+        elif l < NL - 1:
+            y.update(entries=1, rows=ragged["total"][1 + l], t0=0, z_rows=n)
+        y["M"] = y["entries"] * y["rows"]
+        layer.append(y)
+    x_floats, z_floats = ns * (Lp + n) * R, ns * n * D
+    return dict(ns=ns, n=n, Lp=Lp, Lt=Lp + n, x_floats=x_floats, z_floats=z_floats, total_floats=2 * x_floats + z_floats, rectangle=rectangle,
+                start_rows=ns * n if rectangle else ragged["total"][0], need=need, layer=layer, ragged=ragged)
+
+
+def check_pass_plan(p, dil, k, R, D):
+    """What keeps the kernels inside the allocation: every row a product touches lies in [-Lp, n) of its stream, in a workspace of 2 x + z; raises
+    AssertionError.  (The ragged tables' own properties: check_plan.)"""
+    n, ns, NL, k1 = p["n"], p["ns"], len(dil), k - 1
+    assert p["Lp"] == k1 * max(dil) and p["Lt"] == p["Lp"] + n
+    assert p["total_floats"] == 2 * ns * p["Lt"] * R + ns * n * D and p["x_floats"] == ns * p["Lt"] * R and p["z_floats"] == ns * n * D
+    assert 0 <= p["start_rows"] <= ns * n
+    for l, y in enumerate(p["layer"]):
+        assert y["ML"] == k1 * dil[l] + 1 and 0 <= y["fill_cols"] <= min(y["ML"], n), "the ring fill reads the times [n - fill_cols, n)"
+        if l == NL - 1:
+            assert y["M"] == 0, "the last layer's output is never consumed"
+            continue
+        assert y["M"] == y["entries"] * y["rows"] < 2 ** 31
+        for s in range(ns):   # stream s: `count` rows from `first` on, counted from t0 of its batch entry (ragged: its time n - count, wn_ragged_find)
+            count = y["rows"] if p["rectangle"] else p["ragged"]["rows"][1 + l][s]
+            first = 0 if p["rectangle"] else n - count
+            if count == 0:
+                continue
+            for tap in range(k):   # tap 0 = the oldest
+                assert y["t0"] + first - (k1 - tap) * dil[l] >= -p["Lp"], (l, s, tap, "reads in front of the zero prefix")
+            assert y["t0"] + first >= 0, (l, s, "writes into the zero prefix")
+            assert y["t0"] + first + count - 1 < n, (l, s, "touches a row behind the stream")
+            assert first + count - 1 < y["z_rows"] and y["entries"] * y["z_rows"] <= ns * n, (l, s, "z row outside z")
+        assert p["rectangle"] or sum(p["ragged"]["rows"][1 + l]) == y["M"]
 
 
 def find(start, m):

@@ -1,6 +1,7 @@
-"""CPU: ragged prompts without a GPU.  The row plan of wn_prime_ragged (csrc/wn_plan.h: wn_prime_ragged_plan_host) compiled with g++ and held to
-its Python restatement (tests/ragged_cases.py) over a sweep of length sets, once more under AddressSanitizer / UBSan; the binding; and how the
-engine and the facade normalise a list of prompts (on the test double of the C ABI, which has no wn_prime_ragged and stays as it is)."""
+"""CPU: batched priming without a GPU.  The row plan of wn_prime_ragged (csrc/wn_plan.h: wn_prime_ragged_plan_host) and the pass plan of all three
+priming forms (wn_prime_plan_host) compiled with g++ and held to their Python restatement (tests/ragged_cases.py) over a sweep of length sets, once
+more under AddressSanitizer / UBSan; the binding; and how the engine and the facade normalise a list of prompts (on the test double of the C ABI,
+which has no wn_prime_ragged and stays as it is)."""
 import os
 import re
 import subprocess
@@ -48,10 +49,41 @@ int main(int argc, char** argv) {
 }
 """
 
+PASS_HARNESS = r"""
+#include "wn_plan.h"
+#include <cstdio>
+#include <cstdlib>
+// <kernel_size> <layers> <blocks> <R> <D> <ns> <n> [<length> x ns: the ragged form's argument; none: NULL] -> "pass Lp Lt x_floats z_floats total_floats
+// rectangle start_rows", "need ...", one line per layer "ML fill_cols M entries rows t0 z_rows", then (ragged) the tables as above; or "REFUSED why"
+int main(int argc, char** argv) {
+    const int k = atoi(argv[1]), layers = atoi(argv[2]), blocks = atoi(argv[3]), R = atoi(argv[4]), D = atoi(argv[5]), ns = atoi(argv[6]);
+    const long long n = atoll(argv[7]);
+    std::vector<int32_t> dil;
+    for (int b = 0; b < blocks; ++b) for (int i = 0; i < layers; ++i) dil.push_back(1 << i);
+    std::vector<int64_t> len;
+    for (int i = 8; i < argc; ++i) len.push_back(atoll(argv[i]));
+    if (!len.empty() && (int)len.size() != ns) { printf("USAGE\n"); return 1; }
+    WnPrimePlan p;
+    const std::string why = wn_prime_plan_host(dil.data(), (int)dil.size(), k, R, D, len.empty() ? nullptr : len.data(), ns, n, p);
+    if (!why.empty()) { printf("REFUSED %s\n", why.c_str()); return 0; }
+    if (p.ns != ns || p.NL != (int)dil.size() || p.n != n || (int)p.layer.size() != p.NL) { printf("FIELDS\n"); return 1; }
+    printf("pass %lld %lld %zu %zu %zu %d %lld\nneed", p.Lp, p.Lt, p.x_floats, p.z_floats, p.total_floats, p.rectangle ? 1 : 0, p.start_rows);
+    for (long long v : p.need) printf(" %lld", v);
+    printf("\n");
+    for (const WnPrimeLayer& y : p.layer) printf("%d %d %lld %lld %lld %lld %lld\n", y.ML, y.fill_cols, y.M, y.entries, y.rows, y.t0, y.z_rows);
+    for (int t = 0; !p.rectangle && t < p.ragged.n_tables; ++t) {
+        printf("%lld |", p.ragged.total[t]);
+        for (int s = 0; s <= p.ragged.ns; ++s) printf(" %d", p.ragged.table(t)[s]);
+        printf("\n");
+    }
+    return 0;
+}
+"""
 
-def _build(tmp, flags, name):
-    src = tmp / "ragged_harness.cpp"
-    src.write_text(HARNESS)
+
+def _build(tmp, flags, name, source=HARNESS):
+    src = tmp / (name + ".cpp")
+    src.write_text(source)
     exe = tmp / name
     subprocess.check_call(["g++", "-std=c++17", "-O1", *flags, "-I", CSRC, str(src), "-o", str(exe)])
     return str(exe)
@@ -115,6 +147,100 @@ def test_row_plan_under_the_sanitizers(tmp_path):
     exe = _build(tmp_path, ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "ragged_harness_san")
     _hold_to_restatement(exe)
     assert "2^31" in _run(exe, 2, 3, 2, [2 ** 30, 2 ** 30, 5])
+
+
+# ---------------------------------------------------------------- the pass plan of all three forms
+LAYER_KEYS = ("ML", "fill_cols", "M", "entries", "rows", "t0", "z_rows")
+
+
+@pytest.fixture(scope="module")
+def pass_harness(tmp_path_factory):
+    return _build(tmp_path_factory.mktemp("prime_pass"), [], "pass_harness", PASS_HARNESS)
+
+
+def _run_pass(exe, k, layers, blocks, R, D, ns, n, lengths=None):
+    """-> the plan in the form of rc.pass_plan (ragged: its start and total), or the refusal line"""
+    out = subprocess.check_output([exe] + [str(v) for v in (k, layers, blocks, R, D, ns, n)] + [str(v) for v in lengths or ()]).decode().splitlines()
+    if out[0].startswith("REFUSED"):
+        return out[0]
+    head, NL = [int(v) for v in out[0].split()[1:]], layers * blocks
+    p = dict(zip(("Lp", "Lt", "x_floats", "z_floats", "total_floats", "rectangle", "start_rows"), head), ns=ns, n=n)
+    p["rectangle"] = bool(p["rectangle"])
+    p["need"] = [int(v) for v in out[1].split()[1:]]
+    p["layer"] = [dict(zip(LAYER_KEYS, (int(v) for v in line.split()))) for line in out[2:2 + NL]]
+    tables = out[2 + NL:]
+    assert len(tables) == (0 if p["rectangle"] else NL)
+    p["ragged"] = None if p["rectangle"] else dict(start=[[int(v) for v in line.split("|")[1].split()] for line in tables], total=[int(line.split("|")[0]) for line in tables])
+    return p
+
+
+def _hold_pass(exe, k, layers, blocks, R, D, ns, n, lengths=None):
+    dil = rc.dilations(layers, blocks)
+    want, got = rc.pass_plan(dil, k, R, D, lengths, ns, n), _run_pass(exe, k, layers, blocks, R, D, ns, n, lengths)
+    case = (k, layers, blocks, R, D, ns, n, lengths)
+    assert not isinstance(got, str), (case, got)
+    for key in got:
+        if key != "ragged":
+            assert got[key] == want[key], (case, key)
+    assert (got["ragged"] is None) == (want["ragged"] is None) == want["rectangle"], case
+    if not want["rectangle"]:
+        assert got["ragged"]["start"] == want["ragged"]["start"] and got["ragged"]["total"] == want["ragged"]["total"], case
+        rc.check_plan(want["ragged"], dil, k, lengths)
+    rc.check_pass_plan(want, dil, k, R, D)
+    return want
+
+
+# (k, layers, blocks, ns, n, lengths): the shared form and wn_prime (no lengths) at n = 1 and below / at / above the largest ring (MINI3's: 5, 9, 13 for
+# k = 2, 3, 4) and the receptive field; wn_prime_ragged with equal lengths, with a stream of every kind, and as a front member whose streams are all shorter
+PASS_CASES = [(k, 3, 2, ns, n, None) for k in (2, 3, 4) for ns in (1, 3) for n in (1, 4 * (k - 1), 4 * (k - 1) + 1, 4 * (k - 1) + 2, 14 * (k - 1) + 1, 300)]
+PASS_CASES += [(k, 3, 2, 3, n, [n] * 3) for k in (2, 3, 4) for n in (1, 4 * (k - 1) + 1, 300)]
+PASS_CASES += [(k, 3, 2, len(rc.MINI3_LENGTHS), 300, rc.MINI3_LENGTHS) for k in (2, 3, 4)]
+PASS_CASES += [(k, 3, 2, len(v), n, v) for k in (2, 3, 4) for v, n in (([1, 4, 0, 9], 300), ([0, 0], 5), ([7, 7], 8), ([0, 1], 1))]
+PASS_CASES += [(2, 10, 5, 64, 5115, None), (2, 10, 5, 1, 5115, None), (2, 1, 1, 2, 7, None), (4, 1, 1, 2, 3, [3, 2])]
+
+
+def _hold_pass_to_restatement(exe):
+    for k, layers, blocks, ns, n, lengths in PASS_CASES:
+        _hold_pass(exe, k, layers, blocks, 32, 64, ns, n, lengths)
+    for k, layers, blocks, lengths in rc.host_sweep():   # every length set as the ragged form's argument, and its rectangle (every stream at the longest length)
+        n = max(lengths)
+        _hold_pass(exe, k, layers, blocks, 128, 128, len(lengths), n, lengths)
+        _hold_pass(exe, k, layers, blocks, 128, 128, len(lengths), n)
+
+
+def test_pass_plan_against_the_restatement(pass_harness):
+    _hold_pass_to_restatement(pass_harness)
+
+
+def test_pass_plan_in_numbers(pass_harness):
+    """MINI3 (rings 2, 3, 5): the rectangle's trailing rows, the ragged form's (stream, time) maps, the same workspace"""
+    rect = _hold_pass(pass_harness, 2, 3, 2, 128, 128, 9, 300)
+    assert (rect["Lp"], rect["Lt"], rect["total_floats"]) == (4, 304, 2 * 9 * 304 * 128 + 9 * 300 * 128) and rect["need"] == [15, 14, 12, 8, 7, 5, 0]
+    assert [(y["fill_cols"], y["entries"], y["rows"], y["t0"], y["z_rows"]) for y in rect["layer"]] == [
+        (2, 9, 14, 286, 14), (3, 9, 12, 288, 12), (5, 9, 8, 292, 8), (2, 9, 7, 293, 7), (3, 9, 5, 295, 5), (5, 0, 0, 0, 0)]
+    rag = _hold_pass(pass_harness, 2, 3, 2, 128, 128, 9, 300, rc.MINI3_LENGTHS)
+    assert not rag["rectangle"] and rag["start_rows"] == sum(rc.MINI3_LENGTHS) and rag["total_floats"] == rect["total_floats"]
+    assert [(y["entries"], y["rows"], y["t0"], y["z_rows"]) for y in rag["layer"][:2]] == [(1, 0 + 1 + 2 + 4 + 5 + 4 * 14, 0, 300), (1, 0 + 1 + 2 + 4 + 5 + 4 * 12, 0, 300)]
+    assert [y["fill_cols"] for y in rag["layer"]] == [y["fill_cols"] for y in rect["layer"]]
+    one = _hold_pass(pass_harness, 2, 3, 2, 128, 128, 3, 1)   # n = 1: one column per ring, one row per product, no tap inside the stream
+    assert [(y["fill_cols"], y["rows"], y["t0"]) for y in one["layer"][:-1]] == [(1, 1, 0)] * 5
+    equal = _hold_pass(pass_harness, 2, 3, 2, 128, 128, 9, 300, [300] * 9)   # equal lengths through wn_prime_ragged: the rectangle, no tables
+    assert equal["rectangle"] and equal["layer"] == rect["layer"] and equal["ragged"] is None
+
+
+def test_pass_plan_refusals(pass_harness):
+    assert _run_pass(pass_harness, 2, 3, 2, 32, 32, 2, 2 ** 30) == "REFUSED too many rows"                       # the rectangle's text, as wn_prime gives it
+    assert _run_pass(pass_harness, 2, 3, 2, 32, 32, 2, 2 ** 30, [2 ** 30] * 2) == "REFUSED too many rows"        # ... also through wn_prime_ragged
+    assert "2^31" in _run_pass(pass_harness, 2, 3, 2, 32, 32, 3, 2 ** 30, [2 ** 30, 2 ** 30, 5])                 # the row plan's own
+    assert "outside" in _run_pass(pass_harness, 2, 3, 2, 32, 32, 2, 8, [4, 9]) and "outside" in _run_pass(pass_harness, 2, 3, 2, 32, 32, 2, 8, [-1, 8])
+    ok = _run_pass(pass_harness, 2, 3, 2, 32, 32, 3, 2 ** 29)   # 3 * 2^29 rows: below the bound
+    assert ok["total_floats"] == 2 * 3 * (2 ** 29 + 4) * 32 + 3 * 2 ** 29 * 32
+
+
+def test_pass_plan_under_the_sanitizers(tmp_path):
+    exe = _build(tmp_path, ["-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"], "pass_harness_san", PASS_HARNESS)
+    _hold_pass_to_restatement(exe)
+    assert _run_pass(exe, 2, 3, 2, 32, 32, 2, 2 ** 30) == "REFUSED too many rows" and "outside" in _run_pass(exe, 2, 3, 2, 32, 32, 2, 8, [4, 9])
 
 
 def test_the_restatement_finds_rows_like_the_kernels():
