@@ -364,6 +364,29 @@ int wn_prime_shared(wn_handle* h, const int32_t* first_samples, int64_t n_prime,
  * lengths and ends at the n of ALL streams.  (Added without a new WN_ABI_VERSION, like wn_prime_shared.) */
 int wn_prime_ragged(wn_handle* h, const int32_t* first_samples, const int64_t* n_prime, int64_t row_stride, void* hip_stream);
 
+/* The batched pass onto queues that HOLD A HISTORY: appends teacher-forced samples to streams at ANY queue time t0 (wn_info.evals_done; 0 included) --
+ * a checkpoint loaded with wn_state_load, the end of a job, an earlier priming call.
+ *   samples: a DEVICE pointer to int32 [n_streams][row_stride], row s holding stream s's n_append[s] samples from column 0 on.
+ *   n_append: a HOST pointer to n_streams lengths, each in [0, row_stride].
+ *   shared != 0: `samples` is ONE row and `n_append` points to ONE length.  The history is read from stream 0 -- the caller has loaded the same state into
+ *     every stream --, the products run once in the workspace of a 1-stream pass, and the fill writes every stream, every layer-split copy and every
+ *     member of a handle of several rounds, as wn_prime_shared does.
+ * Queue time: afterwards t0 + n, n = max n_append[s].  The streams are right-aligned: stream s's samples stand at the times [t0 + n - n_append[s], t0 + n),
+ * and its existing history moves up against them (the time in between does not exist for that stream, as in wn_prime_ragged).
+ * States: wn_state_save(h, s) afterwards is bit for bit what a one-stream handle returns after wn_state_load of stream s's former state followed by
+ * wn_prime_append of row s alone.  A stream with n_append[s] == 0 keeps its state bit for bit, the dead oldest row included.  On a freshly reset handle
+ * the call is wn_prime_ragged, bit for bit.
+ * Returns: all lengths 0: WN_OK, nothing is launched, the queue time is unchanged.  WN_E_BADARG: a NULL argument, a length outside [0, row_stride].
+ * WN_E_STATE: no weights, a handle whose rounds broke, members of a handle of several rounds at different queue times.  WN_E_UNSUPPORTED: the shape limits
+ * of wn_prime; n_streams * n at or above 2^31; t0 + n at or above 2^62 (the generation kernels keep the queue time in 64 bits and a job adds fewer than
+ * 2^32 evaluations: below that bound none of their time arithmetic overflows).  On every error nothing is written and the queue time is unchanged.
+ * Asynchronous on hip_stream; waits for a pending job as wn_prime does.  Follow with wn_generate(n_given = 1, first_samples = every stream's last appended
+ * sample).  The products are wn_prime_ragged's over the same lengths; per layer one launch more gathers the rings' rows in front of the appended rows,
+ * and the ring fill rewrites all ML_l slots at the new queue time.  On a handle of several rounds every member gets its slice of rows and lengths and the
+ * n of ALL streams.  wn_prime, wn_prime_shared and wn_prime_ragged keep their freshly-reset check.  (Added without a new WN_ABI_VERSION, like
+ * wn_prime_ragged.) */
+int wn_prime_append(wn_handle* h, const int32_t* samples, const int64_t* n_append, int64_t row_stride, int32_t shared, void* hip_stream);
+
 /* ---- a stream's generation state as data ----
  * Between two wn_generate calls a stream IS the input rings of its layers (plus the queue time and the last drawn index, which the caller holds).  The
  * canonical form of those rings is independent of queue time, layer split, channel padding, kernel variant and rounds: for the layers l = 0 .. NL-1 in

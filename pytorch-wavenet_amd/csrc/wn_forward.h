@@ -1799,4 +1799,46 @@ __global__ void wn_fill_ring(const float* x, long long x_batch_stride, float* ri
         *reinterpret_cast<float4*>(ring + (((long long)c * n_streams + s) * ML + (t % ML)) * R + q * 4) = v;
 }
 
+// wn_fill_ring for a pass that starts at the queue time t_base (wn_prime_append): pass time t is queue time t_base + t, so the row goes to slot
+// (t_base + t) mod ML.  `count` may exceed n_time -- the pass rewrites all ML slots, the older ones from the gathered history at negative pass times --
+// and t_base + t may be negative on queues younger than ML: wn_ring_slot (wn_plan.h) does the modulo for either sign.
+__global__ void wn_fill_ring_at(const float* x, long long x_batch_stride, float* ring, int R, int ML, int n_streams, int P, long long n_time,
+                                int count, long long t_base) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int r4 = R / 4;
+    const long long per_stream = (long long)count * r4;
+    if (i >= per_stream * n_streams) return;
+    const int s = (int)(i / per_stream);
+    const long long rem = i % per_stream;
+    const long long t = n_time - count + rem / r4;
+    const int q = (int)(rem % r4);
+    const long long slot = wn_ring_slot(t_base + t, ML);
+    const float4 v = *reinterpret_cast<const float4*>(x + (long long)s * x_batch_stride + t * R + q * 4);
+    for (int c = 0; c < P; ++c)
+        *reinterpret_cast<float4*>(ring + (((long long)c * n_streams + s) * ML + slot) * R + q * 4) = v;
+}
+
+// The history gather of wn_prime_append, ONE launch per layer for all streams: the ML rows a layer's ring holds at the queue time t_base -- row j = 1 .. ML
+// is the layer's input at time t_base - j, slot (t_base - j) mod ML of copy 0 of the layer-split copies -- go in front of the stream's appended rows in
+// the workspace, to the pass time (n_time - n_append[s]) - j; a row below -Lp, the first row of the workspace, is dropped (wn_prime_hist_time, wn_plan.h:
+// the plan shows that nothing reads it).  n_append[s] comes from table 0 of the ragged row tables (rg.start; NULL: every stream appends n_time rows).
+// `ring` is the layer's [P][streams][ML][R]; the first n_streams streams of copy 0 are read (the shared form reads stream 0 alone).  x points at time 0
+// of stream 0, streams x_batch_stride floats apart.
+__global__ void wn_prime_gather_history(const float* ring, int R, int ML, int n_streams, float* x, long long x_batch_stride, long long Lp,
+                                        long long n_time, long long t_base, WnRagged rg) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    const int r4 = R / 4;
+    const long long per_stream = (long long)ML * r4;
+    if (i >= per_stream * n_streams) return;
+    const int s = (int)(i / per_stream);
+    const long long rem = i % per_stream;
+    const long long j = 1 + rem / r4;
+    const int q = (int)(rem % r4);
+    const long long n_append = rg.start ? (long long)rg.start[s + 1] - rg.start[s] : n_time;
+    const long long t = wn_prime_hist_time(n_time, n_append, j, Lp);
+    if (t < -Lp) return;
+    const float4 v = *reinterpret_cast<const float4*>(ring + ((long long)s * ML + wn_ring_slot(t_base - j, ML)) * R + q * 4);
+    *reinterpret_cast<float4*>(x + (long long)s * x_batch_stride + t * R + q * 4) = v;
+}
+
 #endif  // WN_FORWARD_H

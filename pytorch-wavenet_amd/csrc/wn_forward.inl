@@ -370,11 +370,13 @@ extern "C" int wn_score(wn_handle* h, const int32_t* indices, const int64_t* tar
 // outputs) and the newest (k-1)*d+1 columns of every layer are written straight into the queues.  Requires freshly reset queues
 // (queue time 0); activations before the stream start are zero at every layer, like DilatedQueue.reset().
 //
-// Three entry points, one pass.  What a pass does is decided on the host by wn_prime_plan_host (wn_plan.h: WnPrimePlan, plain arithmetic, tested with g++);
+// Four entry points, one pass.  What a pass does is decided on the host by wn_prime_plan_host (wn_plan.h: WnPrimePlan, plain arithmetic, tested with g++);
 // wn_prime_pass carries the plan out.  The forms differ in what they plan and in their checks, which stay with the entry points:
 //   wn_prime         one row of samples per stream, all of one length: the rectangle
 //   wn_prime_shared  ONE row for all streams: the rectangle of one stream, whose result the ring fill hands to every stream and copy of every handle listed
 //   wn_prime_ragged  one row per stream, right-aligned at the queue time n = the longest: the ragged row tables -- or the rectangle where all lengths are n
+//   wn_prime_append  wn_prime_ragged's rows (or one shared row) onto queues that hold a history, at any queue time: the plan's append form -- per layer a
+//                    history gather in front of the fill and the products, and a fill of all ring slots at the new queue time
 static int wn_need_forward_kernels(const wn_handle* h, const char* who) {
     if (!h->w.fwd_ok) return wn_fail(WN_E_UNSUPPORTED, "%s: needs kernel_size 2, 3 or 4 and channel counts that are multiples of 32", who);
     return WN_OK;
@@ -437,12 +439,21 @@ static int wn_prime_pass(const WnPrimePlan& pp, wn_handle* h, const int32_t* sam
     float* xin = xa; float* xout = xb;
     for (int l = 0; l < pp.NL; ++l) {
         const WnPrimeLayer& y = pp.layer[l];
+        if (pp.append) {   // what h's rings hold of layer l's input goes where the other forms read zeros: in front of every stream's rows, ahead of the fill and the products
+            const long long work = (long long)ns * y.hist_rows * (R / 4);
+            hipLaunchKernelGGL(wn_prime_gather_history, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, h->d_rings + h->ring_off[l], R, y.ML, ns, xin + Lp * R,
+                               Lt * R, Lp, n, pp.base_time, ragged ? table(0) : WnRagged{nullptr, 0, 0});
+        }
         for (size_t i = 0; i < n_fill; ++i) {   // queue of layer l <- newest min(k1*d+1, n) columns of its input: zeros where a stream had not started
-            const wn_handle* f = fill[i];
+            const wn_handle* f = fill[i];       // (append: all k1*d+1 columns, the older ones the gathered history, at the slots of the new queue time)
             const int nf = f->plan.n_streams;
             const long long work = (long long)nf * y.fill_cols * (R / 4);
-            hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, shared ? 0 : Lt * R,
-                               f->d_rings + f->ring_off[l], R, y.ML, nf, f->plan.P, n, y.fill_cols);
+            if (pp.append)
+                hipLaunchKernelGGL(wn_fill_ring_at, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, shared ? 0 : Lt * R,
+                                   f->d_rings + f->ring_off[l], R, y.ML, nf, f->plan.P, n, y.fill_cols, pp.base_time);
+            else
+                hipLaunchKernelGGL(wn_fill_ring, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, st, xin + Lp * R, shared ? 0 : Lt * R,
+                                   f->d_rings + f->ring_off[l], R, y.ML, nf, f->plan.P, n, y.fill_cols);
         }
         if (l == pp.NL - 1) break;
         if (y.M > 0) {
@@ -458,9 +469,9 @@ static int wn_prime_pass(const WnPrimePlan& pp, wn_handle* h, const int32_t* sam
         }
         float* t = xin; xin = xout; xout = t;
     }
-    rc = rt_hip(hipGetLastError(), ragged ? "wn_prime_ragged launches" : "wn_prime launches");
+    rc = rt_hip(hipGetLastError(), pp.append ? "wn_prime_append launches" : ragged ? "wn_prime_ragged launches" : "wn_prime launches");
     if (rc) return rc;
-    for (size_t i = 0; i < n_fill; ++i) fill[i]->t_base = n;
+    for (size_t i = 0; i < n_fill; ++i) fill[i]->t_base = pp.base_time + n;
     return WN_OK;
 }
 
@@ -559,6 +570,55 @@ extern "C" int wn_prime_shared(wn_handle* h, const int32_t* first_samples, int64
         return WN_OK;
     }
     return wn_prime_rectangle(h, first_samples, n_prime, n_prime, true, &h, 1, hip_stream, "wn_prime_shared");
+}
+
+// ---- wn_prime_append: the batched pass onto queues that hold a history, at any queue time (include/wn_abi.h has the contract).  The plan's append form
+// (wn_plan.h) gathers every layer's ring rows in front of the appended rows and rewrites all ring slots at the new queue time; the products are the ones
+// wn_prime_ragged runs over the same lengths.  Everything that can refuse -- arguments, every member's state, every member's plan -- is looked at before
+// the first launch, so that an error leaves the queues and the queue time alone.
+extern "C" int wn_prime_append(wn_handle* h, const int32_t* samples, const int64_t* n_append, int64_t row_stride, int32_t shared, void* hip_stream) {
+    g_err[0] = 0;
+    const char* who = "wn_prime_append";
+    if (!h || !samples || !n_append) return wn_fail(WN_E_BADARG, "%s: NULL argument", who);
+    const bool front = !h->chains.empty();
+    const int ns_all = front ? h->chain_first.back() : h->plan.n_streams;
+    long long n = 0;
+    for (int s = 0; s < (shared ? 1 : ns_all); ++s) {
+        if (n_append[s] < 0 || n_append[s] > row_stride) return wn_fail(WN_E_BADARG, "%s: stream %d: length %lld outside [0, row_stride = %lld]", who, s, (long long)n_append[s], (long long)row_stride);
+        n = n_append[s] > n ? n_append[s] : n;
+    }
+    if (h->pending) { int rc = wn_wait(h); if (rc) return rc; }
+    if (front && h->broken) return wn_fail(WN_E_STATE, "%s: an earlier job failed half way through its rounds; call wn_reset", who);
+    std::vector<wn_handle*> members = front ? h->chains : std::vector<wn_handle*>{h};
+    for (wn_handle* c : members) {
+        if (!c->have_weights) return wn_fail(WN_E_STATE, "%s: wn_load_weights has not been called", who);
+        { int rc = wn_need_forward_kernels(c, who); if (rc) return rc; }
+        if (c->pending) { int rc = wn_wait(c); if (rc) return rc; }
+        if (c->t_base != members[0]->t_base) return wn_fail(WN_E_STATE, "%s: the rounds stand at different queue times (%lld, %lld); call wn_reset", who, members[0]->t_base, c->t_base);
+    }
+    if (n == 0) return WN_OK;
+    const long long t0 = members[0]->t_base;
+    std::vector<WnPrimePlan> plans(shared ? 1 : members.size());
+    for (size_t i = 0; i < plans.size(); ++i) {   // shared: ONE stream's rectangle, computed by member 0 for all
+        const wn_handle* c = members[i];
+        const std::string why = wn_prime_plan_host(c->dil.data(), c->plan.NL, c->plan.k, c->plan.R, c->plan.D, shared ? nullptr : n_append + (front ? h->chain_first[i] : 0),
+                                                   shared ? 1 : c->plan.n_streams, n, plans[i], true, t0);
+        if (!why.empty()) return wn_fail(WN_E_UNSUPPORTED, "%s: %s", who, why.c_str());
+    }
+    if (shared) {
+        { int rc = rt_hip(hipSetDevice(members[0]->cfg.device_id), "hipSetDevice"); if (rc) return rc; }
+        int rc = wn_prime_pass(plans[0], members[0], samples, row_stride, true, members.data(), members.size(), hip_stream, who);
+        if (rc) return rc;
+    } else {
+        for (size_t i = 0; i < members.size(); ++i) {   // every member ends at t0 + the n of ALL streams, also one whose own streams are all shorter
+            const size_t s0 = front ? (size_t)h->chain_first[i] : 0;
+            int rc = rt_hip(hipSetDevice(members[i]->cfg.device_id), "hipSetDevice");
+            rc = rc ? rc : wn_prime_pass(plans[i], members[i], samples + s0 * (size_t)row_stride, row_stride, false, &members[i], 1, hip_stream, who);
+            if (rc) { if (i) h->broken = true; return rc; }   // (members before this one have moved on: as after a job that failed between its rounds)
+        }
+    }
+    if (front) h->t_base = h->chains[0]->t_base;
+    return WN_OK;
 }
 
 // Operand precision of wn_forward's / wn_score's GEMMs: 0 = fp32 (default; matches the reference's fp32 forward to rounding),

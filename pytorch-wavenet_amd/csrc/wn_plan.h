@@ -798,24 +798,52 @@ static inline std::string wn_prime_ragged_plan_host(const int32_t* dil, int NL, 
 //       times from first_time on), t0 = 0; z is addressed by (stream, time) like x, n high.
 // Either way every row a product reads or writes lies in [-Lp, n) of its stream, which is what keeps the kernels inside the 2 x + z workspace
 // (tests/ragged_cases.py: check_pass_plan).
+//
+// The APPEND form (wn_prime_append: `append`, the handle's queue time base_time >= 0) runs the same products over the same rows -- rectangle or ragged by the
+// same rule -- on queues that hold a history.  The times of the pass stay [0, n): pass time t is the queue time base_time + t, stream s's samples stand at
+// [n - n_prime[s], n), and where the other forms read the zero prefix this one reads what the stream's rings held:
+//   the history gather of layer l (hist_rows = ML rows per stream, into the buffer that is layer l's input, ahead of layer l's fill and products) copies
+//       the rows j = 1 .. ML from ring slot (base_time - j) mod ML to the pass time (n - n_prime[s]) - j; a row below -Lp is dropped (wn_prime_hist_time);
+//   the fill takes fill_cols = ML columns -- every slot is rewritten at the new queue time -- into slot (base_time + t) mod ML, t in [n - ML, n) (wn_ring_slot:
+//       the modulo of a negative operand done right).
+// INVARIANT of the append form, on top of the bounds above: every row that a product or a fill READS was WRITTEN in this pass -- by the start gather, by a
+// history gather or by a product of the layer below -- into the buffer it is read from (the buffers ping-pong: layer l + 2 re-uses layer l's, with a history
+// region of another size).  The cleared workspace is not what makes an append pass right; the one row the clip at -Lp can drop (j = ML of a layer of the
+// largest dilation, in a stream that appends all n rows) is the stream's dead oldest row, which no fill and no product reads (tests/append_cases.py:
+// check_append_plan).
 struct WnPrimeLayer {
     int ML, fill_cols;
     long long M, entries, rows, t0, z_rows;   // M == 0: no product
+    int hist_rows;                            // append form: rows per stream of the history gather (ML); else 0
 };
 struct WnPrimePlan {
     int ns = 0, NL = 0;
     long long n = 0, Lp = 0, Lt = 0;
     size_t x_floats = 0, z_floats = 0, total_floats = 0;   // one activation buffer, z, and the workspace 2 x + z
     bool rectangle = true;
+    bool append = false;                  // the append form; base_time = the queue time the pass starts at (0 in the other forms)
+    long long base_time = 0;
     long long start_rows = 0;             // rows of the start_conv gather: the rectangle's ns launches of n rows, or the ragged form's one launch of total[0]
     std::vector<long long> need;          // [NL + 1]
     std::vector<WnPrimeLayer> layer;      // [NL]
     WnRaggedPlan ragged;                  // filled iff !rectangle
 };
-// n_prime == NULL: every stream has n samples.  Returns "" and fills p, or why not: the rectangle's "too many rows" (ns * n at / above 2^31), or the ragged
-// row plan's refusal.
-static inline std::string wn_prime_plan_host(const int32_t* dil, int NL, int kernel_size, int R, int D, const int64_t* n_prime, int ns, long long n, WnPrimePlan& p) {
+// The queue time a pass may end at: the generation kernels keep times in 64 bits and a job adds fewer than 2^32 evaluations to them, so below 2^62 nothing
+// in their arithmetic (t mod ML, t - d) can overflow.
+#define WN_PRIME_APPEND_TIME_MAX (1ll << 62)
+// slot of time t (any sign) in a ring of ML rows: the DilatedQueue's t mod ML, mathematically (C's % rounds towards zero)
+static inline WN_HD long long wn_ring_slot(long long t, long long ML) { const long long m = t % ML; return m < 0 ? m + ML : m; }
+// pass time of history row j (1 = the newest) of a stream that appends n_append of the pass's n rows, or -Lp - 1 ("dropped") below the workspace
+static inline WN_HD long long wn_prime_hist_time(long long n, long long n_append, long long j, long long Lp) {
+    const long long t = (n - n_append) - j;
+    return t < -Lp ? -Lp - 1 : t;
+}
+// n_prime == NULL: every stream has n samples.  Returns "" and fills p, or why not: the rectangle's "too many rows" (ns * n at / above 2^31), the ragged
+// row plan's refusal, or (append) a queue time outside [0, WN_PRIME_APPEND_TIME_MAX - n).
+static inline std::string wn_prime_plan_host(const int32_t* dil, int NL, int kernel_size, int R, int D, const int64_t* n_prime, int ns, long long n, WnPrimePlan& p,
+                                             bool append = false, long long base_time = 0) {
     if (NL < 1 || ns < 1 || n < 0) return "no layers, no streams or a negative queue time";
+    if (append && (base_time < 0 || base_time >= WN_PRIME_APPEND_TIME_MAX - n)) return "the queue time behind the call must stay below 2^62";
     p = WnPrimePlan();
     for (int s = 0; n_prime && s < ns; ++s) p.rectangle = p.rectangle && n_prime[s] == n;
     if (p.rectangle) {
@@ -828,6 +856,7 @@ static inline std::string wn_prime_plan_host(const int32_t* dil, int NL, int ker
     long long max_d = 1;
     for (int l = 0; l < NL; ++l) max_d = dil[l] > max_d ? dil[l] : max_d;
     p.ns = ns; p.NL = NL; p.n = n;
+    p.append = append; p.base_time = append ? base_time : 0;
     p.Lp = k1 * max_d; p.Lt = p.Lp + n;
     p.x_floats = (size_t)ns * p.Lt * R; p.z_floats = (size_t)ns * n * D;
     p.total_floats = 2 * p.x_floats + p.z_floats;
@@ -837,7 +866,8 @@ static inline std::string wn_prime_plan_host(const int32_t* dil, int NL, int ker
     for (int l = 0; l < NL; ++l) {
         WnPrimeLayer& y = p.layer[l];
         y.ML = (int)(k1 * dil[l]) + 1;
-        y.fill_cols = (int)(y.ML < n ? y.ML : n);
+        y.fill_cols = append ? y.ML : (int)(y.ML < n ? y.ML : n);
+        y.hist_rows = append ? y.ML : 0;
         if (l == NL - 1) continue;
         if (p.rectangle) {
             y.entries = ns; y.rows = p.need[l + 1] < n ? p.need[l + 1] : n;

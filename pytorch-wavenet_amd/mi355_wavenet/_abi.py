@@ -75,16 +75,17 @@ class wn_train_tensors(ctypes.Structure):
 
 EXPORTS = ["wn_abi_version", "wn_create", "wn_destroy", "wn_load_weights", "wn_reset", "wn_generate", "wn_wait",
            "wn_get_info", "wn_export_queue", "wn_forward", "wn_set_forward_precision", "wn_prime", "wn_train_get_layout", "wn_train_export_params", "wn_train_forward", "wn_train_backward", "wn_train_loss", "wn_train_pack", "wn_train_unpack_grads", "wn_train_set_deterministic", "wn_adam_step", "wn_profile_next", "wn_profile_read", "wn_last_error", "wn_score", "wn_set_sampling",
-           "wn_state_floats", "wn_state_save", "wn_state_load", "wn_prime_shared", "wn_set_logprob_output", "wn_set_forced_samples", "wn_prime_ragged"]
+           "wn_state_floats", "wn_state_save", "wn_state_load", "wn_prime_shared", "wn_set_logprob_output", "wn_set_forced_samples", "wn_prime_ragged", "wn_prime_append"]
 # The generation state as data (wn_state_floats / wn_state_save / wn_state_load) and shared priming (wn_prime_shared): optional and looked up on first use
 STATE_EXPORTS = ("wn_state_floats", "wn_state_save", "wn_state_load", "wn_prime_shared")
 # Functions added to ABI version 5 after its first libraries: a library of that version may lack them (Library.has says; the caller of a missing one raises).
-OPTIONAL_EXPORTS = ("wn_score", "wn_set_sampling") + STATE_EXPORTS + ("wn_set_logprob_output", "wn_set_forced_samples", "wn_prime_ragged")
+OPTIONAL_EXPORTS = ("wn_score", "wn_set_sampling") + STATE_EXPORTS + ("wn_set_logprob_output", "wn_set_forced_samples", "wn_prime_ragged", "wn_prime_append")
 # ... and of those, the ones the binding never looks at when a library is loaded: Library.has resolves them on first use.  A process that never asks for a
 # sampling filter never touches wn_set_sampling, and Library.missing -- what loading found absent -- does not list them.  (Why a third list: the binding's
 # tests pin `missing` on a library of the first generation to exactly ("wn_score",) -- tests/test_score_host.py --, and wn_set_sampling is absent there too.)
 LAZY_EXPORTS = ("wn_set_sampling",) + STATE_EXPORTS + ("wn_set_logprob_output", "wn_set_forced_samples",   # (looked up when a job asks for log-probabilities / forced samples)
-                                                       "wn_prime_ragged")                                   # (... / primes prompts of unequal length: Engine.prime_ragged)
+                                                       "wn_prime_ragged",                                   # (... / primes prompts of unequal length: Engine.prime_ragged)
+                                                       "wn_prime_append")                                   # (... / appends prompts to live queues: Engine.prime_append)
 WN_LOGP_SAMPLING, WN_LOGP_MODEL = 0, 1   # include/wn_abi.h: modes of wn_set_logprob_output
 
 
@@ -154,7 +155,8 @@ class Library:
                       "wn_prime_shared": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p],
                       "wn_set_logprob_output": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_int32],
                       "wn_set_forced_samples": [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64],
-                      "wn_prime_ragged": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_void_p]}
+                      "wn_prime_ragged": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_void_p],
+                      "wn_prime_append": [ctypes.c_void_p, ctypes.c_void_p, ctypes.POINTER(ctypes.c_int64), ctypes.c_int64, ctypes.c_int32, ctypes.c_void_p]}
 
     def has(self, name):
         """False for a function of OPTIONAL_EXPORTS that this library does not export (one of LAZY_EXPORTS is looked up, and bound, here)."""

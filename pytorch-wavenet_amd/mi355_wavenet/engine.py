@@ -363,6 +363,30 @@ class Engine:
         self.lib.check(rc)
         return True
 
+    def prime_append(self, prompts, shared=False):
+        """prime_ragged() onto queues that hold a history, at any queue time (wn_prime_append): ``prompts`` is a list of n_streams 1-D integer
+        sequences (a stream may have none: it keeps its state), all of them teacher-forced inputs that CONTINUE the streams -- after a job, a
+        ``state_load``, an earlier priming call.  The streams are right-aligned at the new queue time, the old one plus the longest length.
+        shared=True: ``prompts`` is ONE sequence for all streams, which hold the same state; the products run once.  Returns False when the library
+        lacks the symbol or the engine cannot (wn_prime's shape limits): the caller appends some other way.  ValueError, before any call: not
+        n_streams rows, a row that is not 1-D, a class index out of range."""
+        rows, lengths = ragged_rows([prompts] if shared else prompts, self.classes, min_length=0)
+        if len(rows) != (1 if shared else self.n_streams):
+            raise ValueError("prompts must hold one row per stream (%d), got %d" % (self.n_streams, len(rows)))
+        if not self.lib.has("wn_prime_append"):
+            return False
+        stride = max(1, int(lengths.max()))
+        fs = np.zeros((len(rows), stride), dtype=np.int32)
+        for s, row in enumerate(rows):
+            fs[s, :row.size] = row
+        dev = self.mem.upload(fs)   # (held until the launches are enqueued: the stream orders the rest)
+        n = (ctypes.c_int64 * len(rows))(*[int(v) for v in lengths])
+        rc = self.lib.dll.wn_prime_append(self._h, self.mem.ptr(dev), n, stride, 1 if shared else 0, self.mem.stream())
+        if rc == _abi.WN_E_UNSUPPORTED:
+            return False
+        self.lib.check(rc)
+        return True
+
     def upload_uniforms(self, u):
         """float64 (n_streams, n) uniforms -> a resident handle ``generate(uniforms=...)`` accepts"""
         u = np.ascontiguousarray(np.asarray(u, dtype=np.float64))

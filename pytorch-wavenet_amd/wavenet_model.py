@@ -438,7 +438,7 @@ class WaveNetModel(nn.Module):
 
     def generate_fast(self, num_samples, first_samples=None, temperature=1., regularize=0.,
                       progress_callback=None, progress_interval=100, *, top_k=0, top_p=0., continue_from=None, return_state=False,
-                      return_logprobs=False, forced=None):
+                      return_logprobs=False, forced=None, append=None):
         """Same contract as wavenet_model.py:237-315; returns float64 ndarray (num_samples,).
         Extension (keyword only): top_k / top_p truncate every sampled draw inside the sampler kernels (include/wn_abi.h: wn_set_sampling); one
         uniform per sample is drawn from the global numpy RNG as without them, and the engine's filter is off again when the call returns or raises.
@@ -462,12 +462,48 @@ class WaveNetModel(nn.Module):
         threshold), the streams right-aligned in time; callbacks, the timing print and the piece cuts are those of a call with num_given = the longest
         prompt whose priming the batched pass covered.  return_state: state s counts evals = len(prompts[s]) - 1 + num_samples.  forced stays
         (streams, num_samples).  Where the batched pass does not apply (kernel_size above 4, the unpadded kernel_size 3 and 4 shapes, an older
-        library) every prompt is primed ALONE on a one-stream engine and its state loaded into the job's engine: correct for every shape, and slow."""
+        library) every prompt is primed ALONE on a one-stream engine and its state loaded into the job's engine: correct for every shape, and slow.
+        append: given audio that CONTINUES the checkpoint, valid only with continue_from (else a ValueError) -- one 1-D sequence of class indices for
+        one state, a list of 1-D sequences for a list of states (any lengths, an empty one included).  The stream's inputs continue
+        state.last_index, append[0], ..., append[-1]: the len(append) evaluations on all but the last of them are teacher-forced in ONE batched pass
+        onto the loaded queues (Engine.prime_append: no uniform is drawn for them), generation starts from append[-1].  Callbacks, piece cuts and the
+        timing print are those of generate_fast(first_samples=[last_index, *append]) with its priming covered by the batched pass; return_state
+        counts evals = state.evals + len(append) + num_samples.  Where the batched pass does not apply the state is loaded and [last_index, *append]
+        primed through the chain -- for a list, stream by stream on a one-stream engine whose state is then loaded: correct for every shape, and slow."""
         logprobs = self._logprob_mode(return_logprobs)
         forced = self._checked_forced(forced, num_samples)
-        states, first_samples = self._continuation("generate_fast", continue_from, first_samples)
+        states, first_samples, appended = self._continuation("generate_fast", continue_from, first_samples, append)
         return self._generate_fast(num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                                   states, return_state, logprobs, forced)
+                                   states, return_state, logprobs, forced, appended=appended)
+
+    def advance_state(self, states, samples):
+        """A state and some given audio -> the state behind that audio: ``generate_fast(0, continue_from=states, append=samples,
+        return_state=True)[1]`` without the timing print.  One GenerationState and one 1-D sequence, or a list of each; nothing is drawn."""
+        states, first_samples, appended = self._continuation("advance_state", states, None, samples, need_append=True)
+        return self._generate_fast(0, first_samples, 1., 0., None, 100, 0, 0., states, True, None, None, timing_print=False, appended=appended)[1]
+
+    # Opt-in piecewise priming: None -- every prompt is primed in ONE batched pass, whose workspace grows with the longest prompt --, or an integer
+    # p >= 1: the first p columns of every stream's prompt are primed as before (Engine.prime_host / prime_ragged / prime_shared), the following ones
+    # in pieces of at most p through Engine.prime_append.  The workspace is then a piece's; states and audio are those of the one pass, bit for bit.
+    prime_piece_samples = None
+
+    def _prime_pieces(self, eng, given, first_pass, shared=False):
+        """``given``: one array per stream (shared: ONE array) of teacher-forced inputs for freshly reset queues.  first_pass(rows) -> bool primes
+        such rows in one batched pass.  Returns its answer: with prime_piece_samples = None for all of ``given`` -- the call as it always was --,
+        else for the first columns, the rest following in prime_append passes."""
+        p = self.prime_piece_samples
+        longest = max(g.size for g in given)
+        if p is None or longest <= p or not eng.lib.has("wn_prime_append"):
+            return first_pass(given)
+        if int(p) != p or p < 1:
+            raise ValueError("prime_piece_samples must be None or an integer >= 1, got %r" % (p,))
+        if not first_pass([g[:p] for g in given]):
+            return False
+        for a in range(p, longest, p):
+            piece = [g[a:a + p] for g in given]
+            if not eng.prime_append(piece[0] if shared else piece, shared=shared):
+                raise RuntimeError("the engine primed the first %d columns in a batched pass and refuses to append the next piece" % p)
+        return True
 
     @staticmethod
     def _logprob_mode(return_logprobs):
@@ -486,11 +522,14 @@ class WaveNetModel(nn.Module):
         from mi355_wavenet import engine
         return engine.checked_forced(forced, num_samples, self.classes, rows)
 
-    def _continuation(self, caller, continue_from, first_samples):
-        """-> (None, first_samples) without continue_from; else (the states as a list, checked against this model; the first_samples that stand for
-        them: 1-D for a single state, else 2-D) -- continue_from and first_samples exclude each other"""
+    def _continuation(self, caller, continue_from, first_samples, append=None, need_append=False):
+        """-> (None, first_samples, None) without continue_from; else (the states as a list, checked against this model; the first_samples that stand
+        for them: 1-D for a single state, else 2-D; None, or -- ``append`` -- every stream's row [last_index, *append] as int64 arrays) --
+        continue_from and first_samples exclude each other, append needs continue_from"""
         if continue_from is None:
-            return None, first_samples
+            if append is not None:
+                raise ValueError("%s: append continues a checkpoint and needs continue_from" % caller)
+            return None, first_samples, None
         if first_samples is not None:
             raise ValueError("%s: continue_from carries the next input (last_index); first_samples must not be given with it" % caller)
         from mi355_wavenet.state import GenerationState
@@ -501,7 +540,16 @@ class WaveNetModel(nn.Module):
         for st in states:
             st.check(self)
         last = np.asarray([[st.last_index] for st in states], dtype=np.int64)
-        return states, torch.from_numpy(last[0] if single else last)
+        appended = None
+        if append is not None or need_append:
+            from mi355_wavenet import engine
+            if append is None or (not single and not isinstance(append, (list, tuple))):
+                raise ValueError("%s: append is one 1-D sequence for one state, a list of them for a list of states" % caller)
+            rows = engine.ragged_rows([append] if single else append, self.classes, min_length=0)[0]
+            if len(rows) != len(states):
+                raise ValueError("%s: append holds %d sequence(s) for %d state(s)" % (caller, len(rows), len(states)))
+            appended = [np.concatenate([last[s], r]) for s, r in enumerate(rows)]
+        return states, torch.from_numpy(last[0] if single else last), appended
 
     def _stream_state(self, eng, stream, last_index, evals):
         from mi355_wavenet.state import GenerationState
@@ -523,7 +571,7 @@ class WaveNetModel(nn.Module):
         every stream's next input."""
         from mi355_wavenet import engine
         eng.reset()
-        batched = eng.prime_ragged([r[:-1] for r in rows])
+        batched = self._prime_pieces(eng, [r[:-1] for r in rows], eng.prime_ragged)
         if not batched:
             states = []
             if any(r.size > 1 for r in rows):
@@ -538,6 +586,31 @@ class WaveNetModel(nn.Module):
             for s, st in enumerate(states):
                 if st is not None:
                     eng.state_load(st, s, 1)
+        self._wn_last_prime_batched = bool(batched)
+        return engine.right_aligned(rows)
+
+    def _prime_append(self, eng, rows, states, shared=False):
+        """``eng`` holds the states (loaded at queue time 0); every stream is teacher-forced through all but the last sample of its row
+        [last_index, *append]: ONE batched pass onto the loaded queues (Engine.prime_append; shared: one row, every stream holds states[0]), or --
+        where the engine cannot -- through the chain: on ``eng`` itself where its streams all take the one row, else stream by stream on a
+        one-stream engine that loads the state, primes and hands its state back.  Returns the right-aligned (streams, longest) matrix of the rows."""
+        from mi355_wavenet import engine
+        given = [r[:-1] for r in rows]
+        batched = eng.prime_append(given[0] if shared else given, shared=shared)
+        if not batched and any(g.size for g in given):
+            if shared or len(rows) == 1:
+                eng.generate(0, rows[0], reset=False)   # (num_samples 0: the priming evaluations alone)
+            else:
+                one = engine.Engine(self._config(), dict(self.state_dict()), n_streams=1, device_index=self._parameters_key()[0])
+                try:
+                    for s, r in enumerate(rows):
+                        if r.size > 1:
+                            one.reset()
+                            one.state_load(states[s].state)
+                            one.generate(0, r[None, :], reset=False)
+                            eng.state_load(one.state_save(0), s, 1)
+                finally:
+                    one.close()
         self._wn_last_prime_batched = bool(batched)
         return engine.right_aligned(rows)
 
@@ -573,16 +646,16 @@ class WaveNetModel(nn.Module):
         return result[0] if len(result) == 1 else tuple(result)
 
     def _generate_fast(self, num_samples, first_samples, temperature, regularize, progress_callback, progress_interval, top_k, top_p,
-                       states=None, return_state=False, logprobs=None, forced=None, timing_print=True):
+                       states=None, return_state=False, logprobs=None, forced=None, timing_print=True, appended=None):
         """normalise, reset, load the states, prime, plan, execute, finish: where the job is cut into pieces and what runs between them is
         mi355_wavenet/generation.py's"""
         from mi355_wavenet import generation
         self.eval()
-        ragged = self._ragged_prompt(first_samples)
-        if ragged is not None and len({r.size for r in ragged}) == 1:   # rows of one length: the 2-D call
+        ragged = appended if appended is not None else self._ragged_prompt(first_samples)
+        if appended is None and ragged is not None and len({r.size for r in ragged}) == 1:   # rows of one length: the 2-D call
             first_samples, ragged = torch.from_numpy(np.stack(ragged)), None
         if ragged is not None:
-            first, batched = None, True
+            first, batched = None, appended is None or first_samples.ndim == 2   # (append onto ONE state: the 1-D result)
             n_streams, num_given = len(ragged), max(r.size for r in ragged)
         else:
             first, batched = self._prompt(first_samples)
@@ -599,10 +672,10 @@ class WaveNetModel(nn.Module):
             # matrix-core GEMMs over all positions, queues filled from the result); shapes it does not cover take the per-sample chain
             n_prime = num_given - 1
             if ragged is not None:   # prompts of unequal length: all of the priming is behind us either way, the job starts from the last column
-                first = self._prime_ragged(eng, ragged)
+                first = self._prime_append(eng, ragged, states) if appended is not None else self._prime_ragged(eng, ragged)
                 primed = n_prime
             else:
-                primed = n_prime if n_prime >= eng.PRIME_BATCH_MIN and eng.prime_host(first[:, :n_prime]) else 0
+                primed = n_prime if n_prime >= eng.PRIME_BATCH_MIN and self._prime_pieces(eng, list(first[:, :n_prime]), lambda g: eng.prime_host(np.stack(g))) else 0
                 self._wn_last_prime_batched = primed > 0
             steps = generation.generation_schedule(num_given, num_samples, progress_interval, progress_callback is not None, primed, temperature > 0)
             idx, logp = generation.run_schedule(steps, eng, first, temperature, regularize, forced, logprobs, progress_callback, timing_print)
@@ -650,7 +723,7 @@ class WaveNetModel(nn.Module):
     SHARED_PRIME = True
 
     def generate_fast_streams(self, num_samples, temperatures, first_samples=None, regularize=0., *, top_k=0, top_p=0., continue_from=None,
-                              return_logprobs=False, forced=None):
+                              return_logprobs=False, forced=None, append=None):
         """Extension: one generate_fast() per entry of ``temperatures`` -- the reference's generate_audio loop
         (wavenet_training.py:115-124) -- as parallel streams of ONE persistent-kernel job.  Returns float64
         (len(temperatures), num_samples), row k equal to ``generate_fast(num_samples, first_samples, temperatures[k])``
@@ -658,6 +731,8 @@ class WaveNetModel(nn.Module):
         sample), greedy rows (temperature <= 0, wavenet_model.py:290-294) consume none.  top_k / top_p as in generate_fast (greedy rows ignore them).
         continue_from: ONE ``GenerationState`` that every temperature continues from (N variations of a checkpoint) -- as first_samples=[last_index]
         with the queues loaded into every stream instead of reset; together with first_samples it is a ValueError.
+        append (with continue_from only): ONE 1-D sequence of given audio that continues the state for all temperatures, as in generate_fast; it is
+        teacher-forced once for all streams (the shared form of Engine.prime_append).
         return_logprobs as in generate_fast: returns (audio, logp), logp float32 (len(temperatures), num_samples); a greedy row holds the log-softmax
         value of its argmax.
         forced as in generate_fast: (num_samples,) shared by all rows, or (len(temperatures), num_samples); -1 is a free position.
@@ -666,7 +741,11 @@ class WaveNetModel(nn.Module):
         last stream's) are as without it."""
         logprobs = self._logprob_mode(return_logprobs)
         self._checked_forced(forced, num_samples, rows=len(temperatures))   # (checked here, before an engine is touched; Engine.generate makes the rows)
-        states, first_samples = self._continuation("generate_fast_streams", continue_from, first_samples)
+        if continue_from is not None and isinstance(continue_from, (list, tuple)) and len(continue_from) != 1:
+            raise ValueError("generate_fast_streams: continue_from is ONE state that all temperatures share")
+        if isinstance(continue_from, (list, tuple)) and append is not None:
+            append = [append]
+        states, first_samples, appended = self._continuation("generate_fast_streams", continue_from, first_samples, append)
         if states is not None and len(states) != 1:
             raise ValueError("generate_fast_streams: continue_from is ONE state that all temperatures share")
         ragged = self._ragged_prompt(first_samples)
@@ -686,20 +765,30 @@ class WaveNetModel(nn.Module):
             if states is not None:
                 eng.reset()
                 eng.state_load(states[0].state)   # one state, every stream
+            if appended is not None:   # the given audio once for all streams, the job starts from its last sample
+                first = np.repeat(self._prime_append(eng, appended, states, shared=True)[:, -1:], len(temps), axis=0)
             if ragged is not None:   # one prompt per temperature: primed here, the job starts from every stream's last given sample
                 first = self._prime_ragged(eng, ragged)[:, -1:]
+            shared_prompt = self.SHARED_PRIME and states is None and ragged is None and eng.lib.has("wn_prime_shared")
+            reset = states is None and ragged is None
+            if shared_prompt and self.prime_piece_samples is not None and first.shape[1] - 1 >= eng.PRIME_BATCH_MIN:   # the shared prompt in pieces
+                eng.reset()
+                if self._prime_pieces(eng, [first[0, :-1]], lambda g: eng.prime_shared(g[0]), shared=True):
+                    first, reset, shared_prompt = first[:, -1:], False, False
             out = eng.generate(num_samples, first, temperature=np.asarray(temps, dtype=np.float32), regularize=regularize,
-                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=states is None and ragged is None, logprobs=logprobs,
-                               forced=forced, shared_prompt=self.SHARED_PRIME and states is None and ragged is None and eng.lib.has("wn_prime_shared"))
+                               uniforms=uniforms if any(t > 0 for t in temps) else None, reset=reset, logprobs=logprobs,
+                               forced=forced, shared_prompt=shared_prompt)
         idx, logp = out if logprobs is not None else (out, None)
         return self._finish(eng, idx, logp, stream=len(temps) - 1)  # sequential calls would leave the LAST temperature's queues
 
-    def score_continuation(self, indices, continue_from=None, first_samples=None, return_state=False):
+    def score_continuation(self, indices, continue_from=None, first_samples=None, return_state=False, *, append=None):
         """The model's log-likelihood of audio that CONTINUES a stream: float32 shaped like ``indices`` (class indices, 1-D or 2-D), entry g being
         log p(indices[g] | the prompt or state, indices[:g]) in nats -- the negative of score_indices' row losses, computed by the generation kernels
         in constant memory: a greedy job (no uniform is drawn: the numpy RNG is left alone) in which every position is forced
         (include/wn_abi.h: wn_set_forced_samples) under return_logprobs="model".  Any length, any kernel_size the generation kernels serve.
         continue_from: a GenerationState (a list of them, one per row, for 2-D indices), or first_samples as in generate_fast (default: classes // 2).
+        append (with continue_from only): given audio between the state and ``indices``, as in generate_fast -- teacher-forced in one batched pass, not
+        scored (its log-probabilities are score_continuation's of that audio as ``indices``).
         return_state=True: returns (logp, state) with the state behind the last sample -- chunked scoring: score a long clip piece by piece, each
         piece continuing from the state the piece before returned, for the same values as the single call."""
         idx = indices.detach().cpu().numpy() if torch.is_tensor(indices) else np.asarray(indices)
@@ -707,7 +796,7 @@ class WaveNetModel(nn.Module):
             raise ValueError("score_continuation: indices must be a non-empty integer array, 1-D or (streams, n); got %s %r" % (idx.dtype, idx.shape))
         if idx.min() < 0 or idx.max() >= self.classes:
             raise ValueError("score_continuation: indices outside [0, classes)")
-        states, first_samples = self._continuation("score_continuation", continue_from, first_samples)
+        states, first_samples, appended = self._continuation("score_continuation", continue_from, first_samples, append)
         if states is not None:
             if first_samples.ndim != idx.ndim or (idx.ndim == 2 and len(states) != idx.shape[0]):
                 raise ValueError("score_continuation: one GenerationState for 1-D indices, a list of one per row for 2-D indices")
@@ -723,7 +812,7 @@ class WaveNetModel(nn.Module):
         elif first_samples is not None and torch.as_tensor(first_samples).ndim != 1:
             raise ValueError("score_continuation: 1-D indices need 1-D first_samples")
         out = self._generate_fast(idx.shape[-1], first_samples, 0., 0., None, 100, 0, 0., states, return_state, "model", idx.astype(np.int32),
-                                  timing_print=False)
+                                  timing_print=False, appended=appended)
         return (out[1], out[2]) if return_state else out[1]
 
     # ------------------------------------------------------------------ bookkeeping
