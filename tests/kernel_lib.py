@@ -51,6 +51,11 @@ _SIGS = {
     "kt_bwd_taps": [_P, _I] + _MAP + [_LL, _LL, _LL, _I, _P, _LL, _I] + _MAP + [_I] + _MAP + [_LL, _I],
     "kt_layer_dx": [_P, _I, _I, _I, _P, _LL, _LL, _LL, _P, _LL, _P, _P, _LL, _LL],
     "kb_taps_bf16": [_P, _I] + _MAP + [_LL, _LL, _I, _P, _I, _P] + _MAP + [_LL, _I] + _MAP + [_I],
+    "kp_nn_ragged": [_P, _I] + _MAP + _MAP + [_I, _I, _P, _I, _P] + _MAP + _MAP + [_LL, _P, _I, _I],
+    "kp_taps_ragged": [_P, _I] + _MAP + [_LL, _LL, _I, _P, _I, _P] + _MAP + [_LL, _P, _I, _I],
+    "kp_fwd_start_ragged": [_P, _P, _LL, _P, _P, _P, _LL, _P, _I, _I, _LL, _I],
+    "kp_fill_ring_at": [_P, _P, _LL, _P, _I, _I, _I, _I, _LL, _I, _LL],
+    "kp_gather_history": [_P, _P, _I, _I, _I, _P, _LL, _LL, _LL, _LL, _P],
 }
 
 
@@ -67,7 +72,7 @@ class Harness:
         self.dll.wn_adam_step.restype = _I
         self.dll.wn_last_error.argtypes = []
         self.dll.wn_last_error.restype = ctypes.c_char_p
-        assert self.dll.kh_version() == 3, "stale kernel harness (tests/kernels/build_harness.py --force)"
+        assert self.dll.kh_version() == 4, "stale kernel harness (tests/kernels/build_harness.py --force)"
 
     def call(self, name, *args):
         rc = self.rc(name, *args)

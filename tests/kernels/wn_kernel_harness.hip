@@ -5,6 +5,8 @@
 //   kst_*  the gather / scatter of a stream's canonical state (tests/test_gpu_state_kernels.py)
 //   kt_*   the k-tap training step's input-gradient product (tests/test_gpu_taps_train_kernels.py)
 //   kb_*   the bf16 filter/gate product of kernel_size 3 / 4 (tests/test_gpu_taps_bf16_kernels.py)
+//   kp_*   the batched-priming kernels: the ragged products, the ragged start gather, the ring fill at a queue time, the history gather
+//          (tests/test_gpu_prime_kernels.py)
 //
 // The product's runtime unit is included as it is, ONCE, so its own static launchers (wn_launch_nn, wn_launch_tn, wn_launch_colsum, wn_launch_layer,
 // wn_launch_bwd_layer, ...) and kernels, with their dispatch conditions, are the code under test: nothing is copied.  The entry points take plain
@@ -82,7 +84,7 @@ static float kf_norm_p(float top_p) { return top_p > 0.f && top_p < 1.f ? top_p 
 
 extern "C" {
 
-int kh_version() { return 3; }
+int kh_version() { return 4; }
 
 // One NN product through wn_launch_nn.  bn != NULL: the bf16 forms (B as bf16 [N][ldb]); else fp32 with B^T = bt [K][N] (bt1: rows k >= k_split).
 int kh_nn(void* stream, int epi, KH_MAP(a0), KH_MAP(a1), int k_split, int K, const float* bt, const float* bt1, int N, const float* bias,
@@ -374,6 +376,74 @@ int kb_taps_bf16(void* stream, int taps, KH_MAP(x), long long tap_rows, long lon
     if (taps != 3 && taps != 4) return -1;
     (void)hipGetLastError();
     wn_launch_taps_bf16((hipStream_t)stream, taps, a, bn);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- batched priming (tests/test_gpu_prime_kernels.py)
+// The kernels wn_prime_pass (csrc/wn_forward.inl) launches for the ragged and the append forms, with the fields and the grid expressions it uses.  A row
+// table is passed as (start, n_streams, t_end): start = the prefix sums of the streams' row counts, a DEVICE array of n_streams + 1 ints.
+
+// wn_launch_nn(st, epi, a, nullptr, nullptr, 0, &rg) -> wn_fwd_gemm_ragged<GATE | PLAIN>: what wn_layer_fg (a0 = x(t - d), a1 = x(t), k_split = R) and
+// wn_layer_res (a0 = a1 = z, cin = x(t)) fill, rows_per_batch = M as one entry of the table's total.  -1: an epilogue the ragged kernels do not have.
+int kp_nn_ragged(void* stream, int epi, KH_MAP(a0), KH_MAP(a1), int k_split, int K, const float* bt, int N, const float* bias, KH_MAP(cin), KH_MAP(c), long long M,
+                 const int32_t* start, int n_streams, int t_end) {
+    WnGemmArgs a;
+    memset(&a, 0, sizeof(a));
+    a.a0 = KH_ROWMAP(a0); a.a1 = KH_ROWMAP(a1); a.k_split = k_split; a.K = K; a.bt = bt; a.N = N; a.bias = bias;
+    a.cin = KH_ROWMAP(cin); a.c = KH_ROWMAP(c); a.M = M; a.rows_per_batch = (int)M;
+    const WnRagged rg{start, n_streams, t_end};
+    if (epi != WN_EPI_GATE && epi != WN_EPI_PLAIN) return -1;
+    (void)hipGetLastError();
+    wn_launch_nn((hipStream_t)stream, epi, a, nullptr, nullptr, 0, &rg);
+    return (int)hipGetLastError();
+}
+
+// wn_launch_taps(st, taps, a, &rg) -> wn_fwd_gemm_taps_ragged<3 | 4>, filled as wn_layer_fg_taps fills it (t_min = the first row in front of a stream's
+// time 0 that exists: -Lp).  -1: not a kernel size of the launcher.
+int kp_taps_ragged(void* stream, int taps, KH_MAP(x), long long tap_rows, long long t_min, int R, const float* bt, int N, const float* bias, KH_MAP(c), long long M,
+                   const int32_t* start, int n_streams, int t_end) {
+    WnTapsArgs a;
+    memset(&a, 0, sizeof(a));
+    a.g.a0 = KH_ROWMAP(x); a.g.a1 = KH_ROWMAP(x); a.g.k_split = R; a.g.K = taps * R; a.g.bt = bt; a.g.N = N; a.g.bias = bias;
+    a.g.c = KH_ROWMAP(c); a.g.M = M; a.g.rows_per_batch = (int)M;
+    a.tap_rows = tap_rows; a.t_min = t_min;
+    const WnRagged rg{start, n_streams, t_end};
+    if (taps != 3 && taps != 4) return -1;
+    (void)hipGetLastError();
+    wn_launch_taps((hipStream_t)stream, taps, a, &rg);
+    return (int)hipGetLastError();
+}
+
+// wn_fwd_start_ragged with the grid of wn_prime_pass: one thread per float4 of the table's `rows` rows (no launch for an empty table)
+int kp_fwd_start_ragged(void* stream, const int32_t* idx, long long idx_stride, const float* start_t, const float* start_b, float* x, long long x_stream_stride,
+                        const int32_t* start, int n_streams, int t_end, long long rows, int R) {
+    const long long work = rows * (R / 4);
+    const WnRagged rg{start, n_streams, t_end};
+    (void)hipGetLastError();
+    if (work > 0)
+        hipLaunchKernelGGL(wn_fwd_start_ragged, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, idx, idx_stride, start_t, start_b, x, x_stream_stride,
+                           rg, rows, R);
+    return (int)hipGetLastError();
+}
+
+// wn_fill_ring_at with the grid of wn_prime_pass: one thread per float4 of the `count` newest rows of every stream (x_batch_stride 0: the shared form)
+int kp_fill_ring_at(void* stream, const float* x, long long x_batch_stride, float* ring, int R, int ML, int n_streams, int P, long long n_time, int count,
+                    long long t_base) {
+    const long long work = (long long)n_streams * count * (R / 4);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_fill_ring_at, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, x, x_batch_stride, ring, R, ML, n_streams, P, n_time, count, t_base);
+    return (int)hipGetLastError();
+}
+
+// wn_prime_gather_history with the grid of wn_prime_pass: one thread per float4 of the ML history rows of every stream.  start == NULL: the rectangle form
+// (every stream appends n_time rows); else table 0 of the row tables, {start, n_streams, n_time}.
+int kp_gather_history(void* stream, const float* ring, int R, int ML, int n_streams, float* x, long long x_batch_stride, long long Lp, long long n_time,
+                      long long t_base, const int32_t* start) {
+    const long long work = (long long)n_streams * ML * (R / 4);
+    const WnRagged rg = start ? WnRagged{start, n_streams, (int)n_time} : WnRagged{nullptr, 0, 0};
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(wn_prime_gather_history, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, (hipStream_t)stream, ring, R, ML, n_streams, x, x_batch_stride, Lp, n_time,
+                       t_base, rg);
     return (int)hipGetLastError();
 }
 

@@ -15,6 +15,7 @@ Branch table: each hipLaunchKernelGGL line reached -> the cases (test ids) that 
   wn_train.inl     wn_cvt_bf16                              test_cvt_bf16
                    wn_cvt_bf16_transposed                   test_transposes[cvt-*]
                    wn_transpose_batched                     test_transposes[f32-*]
+(The batched-priming kernels -- the ragged products, wn_fwd_start_ragged, wn_fill_ring_at, wn_prime_gather_history: tests/test_gpu_prime_kernels.py, with a table of its own.)
 
 What the score kernels can show of their logits: the first argmax (every row), logits[target] and the logsumexp through row_nll, and the counts.  The
 exact cases therefore use integer logits (ties are frequent and planted) and hold row_pred and the counts exactly and row_nll to NLL bound below.
@@ -30,6 +31,7 @@ from kernel_lib import (GATE_ABS, NOMAP, SENT16, SENT32, WALL, Rows, _bounded, _
                         dev, from16, host, rne16)
 from kernel_lib import kh  # noqa: F401  (the session fixture)
 from parity_common import LOGIT_RTOL
+from prime_kernel_cases import start_values as _start_values   # (shared with wn_fwd_start_ragged's cases)
 
 pytestmark = pytest.mark.gpu
 
@@ -547,17 +549,6 @@ def test_fill_ring(kh, ML, n_kind, P, ns, R):
     for t in range(n_time - count, n_time):
         w[:, :, t % ML] = X[:, t].view(np.uint32)[None]
     assert_bits(host(ring[0], np.uint32), want, "fill_ring ML %d n_time %d P %d streams %d R %d" % (ML, n_time, P, ns, R))
-
-
-def _start_values(shape, bias_j, rs):
-    """(start, final): final = start + bias in fp32 exactly, final on, just below and just above bf16 rounding points (bias_j / 128 per channel)"""
-    b = rs.randint(136, 248, shape).astype(np.float64)
-    f = rs.choice([0.5 - 2.0 ** -16, 0.5, 0.5 + 2.0 ** -16, 0.25, 0.75, 0.0], shape)
-    sgn = rs.choice([-1.0, 1.0], shape)
-    final = sgn * (b + f) / 128
-    start = final - bias_j / 128
-    assert np.array_equal(start.astype(np.float32).astype(np.float64), start)
-    return start.astype(np.float32), final.astype(np.float32)
 
 
 @pytest.mark.parametrize("shadow", [False, True], ids=["x", "x+xh"])
