@@ -5,7 +5,8 @@
     (pointer, batch_stride, row_stride, t0).  Built at most once and loaded once per process (build_and_load); the session fixture `kh` hands it out
     and releases it at the end of the session.  A test module imports `kh` into its own namespace, where pytest finds it.
   * the helpers of the tests' method: sentinels, guarded row matrices, bf16 rounding on the host, bit comparison, the bounded families' record
-  * the launch of one sampler on one part of a case family (tests/test_gpu_sampler_kernels.py, tests/test_gpu_sampler_filter_kernels.py)
+  * the launch of one sampler on one part of a case family (tests/test_gpu_sampler_kernels.py, tests/test_gpu_sampler_filter_kernels.py), and of its
+    log-probability / forced form on a list of parts (tests/test_gpu_logp_kernels.py)
 The product package never loads any of it."""
 import ctypes
 import os
@@ -43,6 +44,8 @@ _SIGS = {
     "kh_tn_grid": [_LL, _I, _I, _I, _I, ctypes.POINTER(_LL)],
     "kf_sample_1w": [_P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P],
     "kf_sample_generic": [_P, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
+    "kf_logp_1w": [_P, _I, _I, _F, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "kf_logp_generic": [_P, _I, _I, _I, _F, _I, _P, _LL, _P, _P, _P, _P, _P, _P, _P, _P],
     "kf_smp_floats": [_I],
     "kf_run_bytes": [],
     "kst_gather": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _LL, _P, _LL, _I, _P],
@@ -72,7 +75,7 @@ class Harness:
         self.dll.wn_adam_step.restype = _I
         self.dll.wn_last_error.argtypes = []
         self.dll.wn_last_error.restype = ctypes.c_char_p
-        assert self.dll.kh_version() == 4, "stale kernel harness (tests/kernels/build_harness.py --force)"
+        assert self.dll.kh_version() == 5, "stale kernel harness (tests/kernels/build_harness.py --force)"
 
     def call(self, name, *args):
         rc = self.rc(name, *args)
@@ -348,6 +351,78 @@ def sampler_launch(dll, kernel, part, filter_form=1, filt=None):
         want[GUARD:-GUARD] = SENT32
         assert_bits(t, want, "generic C=%d: the %d floats behind the sampler scratch of %d floats" % (C, TAIL, dll.kf_smp_floats(C)))
     return idx[:, 0].copy()
+
+
+LOGP_AT = 37      # the generic wrapper writes row r's value to out[r + at0]: at0 starts here, so that a wrong index lands in a guard band
+
+
+def logp_launch(dll, kernel, parts, logp_mode, null_out=False):
+    """The log-probability / forced wrappers (kf_logp_1w, kf_logp_generic) on a list of parts of one class count: ONE upload of the parts' rows, one launch
+    per part (the run carries one regulariser and one filter), one synchronisation.  A part has C, reg, top_k, top_p, n, logits, temp, u, greedy and, where
+    it forces classes, forced (int32 per row; absent: every position free).  logp_mode: r.logp's two low bits, 0 .. 2.
+    -> [(indices, the uint32 words of the log-probabilities)] per part, after the checks that need no expectation: guards, uniform lanes, the scratch's
+    tail, and that nothing but the rows' own floats changed -- nothing at all with logp_mode 0 or (generic, null_out) a NULL pointer in the status block."""
+    GUARD, TAIL = SMP_GUARD, SMP_TAIL
+    C = parts[0].C
+    assert all(p.C == C for p in parts)
+    per = 64 if kernel == "one_wave" else 1
+    off = np.concatenate([[0], np.cumsum([p.n for p in parts])]).astype(np.int64)
+    n = int(off[-1])
+    logits = dev(np.concatenate([p.logits for p in parts]))
+    u, greedy, temp = dev(np.concatenate([p.u for p in parts])), dev(np.concatenate([p.greedy for p in parts])), dev(np.concatenate([p.temp for p in parts]))
+    forced = dev(np.concatenate([getattr(p, "forced", None) if getattr(p, "forced", None) is not None else np.full(p.n, -1, np.int32) for p in parts]))
+    regs = {}
+    for p in parts:
+        if p.reg is not None and id(p.reg) not in regs:
+            regs[id(p.reg)] = dev(p.reg)
+    out0 = np.full(GUARD + n * per + GUARD, SENT32, np.uint32)
+    out = dev(out0)
+    stream = _stream()
+    if kernel == "one_wave":
+        assert C == 256
+        lp0 = out0
+        lp = dev(lp0)
+    else:
+        lp0 = np.full(GUARD + LOGP_AT + n + GUARD, SENT32, np.uint32)
+        lp = dev(lp0)
+        tail0 = np.full(GUARD + n * TAIL + GUARD, SMP_OTHER, np.uint32)
+        tail = dev(tail0)
+        status = dev(np.array([0, 0, 0, 0, 0, 0] + ([0, 0] if null_out else [(lp.data_ptr() + 4 * GUARD) & 0xFFFFFFFF, (lp.data_ptr() + 4 * GUARD) >> 32]), np.uint32))
+    for p, o in zip(parts, off[:-1].tolist()):
+        reg = regs[id(p.reg)].data_ptr() if p.reg is not None else None
+        rows = (logits.data_ptr() + 4 * o * C, reg, u.data_ptr() + 8 * o, greedy.data_ptr() + 4 * o, temp.data_ptr() + 4 * o, forced.data_ptr() + 4 * o)
+        if kernel == "one_wave":
+            rc = dll.kf_logp_1w(stream, p.n, p.top_k, p.top_p, logp_mode, *rows, out.data_ptr() + 4 * (GUARD + 64 * o), lp.data_ptr() + 4 * (GUARD + 64 * o))
+        else:
+            rc = dll.kf_logp_generic(stream, p.n, C, p.top_k, p.top_p, logp_mode, status.data_ptr(), LOGP_AT + o, *rows, out.data_ptr() + 4 * (GUARD + o),
+                                     tail.data_ptr() + 4 * (GUARD + TAIL * o))
+        assert rc == 0, "HIP error %d" % rc
+    torch.cuda.synchronize()
+    what = "%s C=%d logp_mode %d" % (kernel, C, logp_mode)
+    got, gl = host(out, np.uint32), host(lp, np.uint32)
+    assert_bits(got[:GUARD], out0[:GUARD], what + ": guard in front of the indices")
+    assert_bits(got[-GUARD:], out0[-GUARD:], what + ": guard behind the indices")
+    idx = got[GUARD:-GUARD].view(np.int32).reshape(n, per)
+    if kernel == "one_wave":
+        assert_bits(gl[:GUARD], lp0[:GUARD], what + ": guard in front of the log-probabilities")
+        assert_bits(gl[-GUARD:], lp0[-GUARD:], what + ": guard behind the log-probabilities")
+        bits = gl[GUARD:-GUARD].reshape(n, 64)
+        assert_bits(idx, np.repeat(idx[:, :1], 64, axis=1), what + ": the lanes of a row disagree on the index")
+        assert_bits(bits, np.repeat(bits[:, :1], 64, axis=1), what + ": the lanes of a row disagree on the log-probability")
+        bits = bits[:, 0].copy()
+    else:
+        lo = GUARD + LOGP_AT
+        assert_bits(gl[:lo], lp0[:lo], what + ": the floats in front of out[at]")
+        assert_bits(gl[lo + n:], lp0[lo + n:], what + ": the floats behind out[at]")
+        bits = gl[lo:lo + n].copy()
+        t = host(tail, np.uint32)
+        want = tail0.copy()
+        want[GUARD:-GUARD] = SENT32
+        assert_bits(t, want, what + ": the %d floats behind the sampler scratch of %d floats" % (TAIL, dll.kf_smp_floats(C)))
+    if logp_mode == 0 or (null_out and kernel != "one_wave"):
+        assert_bits(bits, np.full(n, SENT32, np.uint32), what + ": a log-probability was written")
+    idx = idx[:, 0].copy()
+    return [(idx[a:b], bits[a:b]) for a, b in zip(off[:-1].tolist(), off[1:].tolist())]
 
 
 def sampler_run(dll, kernel, fam, filter_form=1, filt=None):

@@ -1,7 +1,8 @@
 // wn_kernel_harness.hip -- TEST INFRASTRUCTURE ONLY: the product's kernels launched one at a time, every group of kernel-level tests in one library:
 //   kh_*   the training-time matrix-core kernels (tests/test_gpu_kernels.py) and the inference kernels -- tap product, score head, ring fill, the
 //          small layout kernels (tests/test_gpu_infer_kernels.py)
-//   kf_*   the generation chain's two samplers, one draw per workgroup (tests/test_gpu_sampler_kernels.py, tests/test_gpu_sampler_filter_kernels.py)
+//   kf_*   the generation chain's two samplers, one draw per workgroup (tests/test_gpu_sampler_kernels.py, tests/test_gpu_sampler_filter_kernels.py), and
+//          their log-probability and forced forms (kf_logp_*: tests/test_gpu_logp_kernels.py)
 //   kst_*  the gather / scatter of a stream's canonical state (tests/test_gpu_state_kernels.py)
 //   kt_*   the k-tap training step's input-gradient product (tests/test_gpu_taps_train_kernels.py)
 //   kb_*   the bf16 filter/gate product of kernel_size 3 / 4 (tests/test_gpu_taps_bf16_kernels.py)
@@ -78,13 +79,80 @@ __global__ __launch_bounds__(WN_THREADS) void kf_sample_generic_kernel(int C, in
     }
 }
 
+// ---- the samplers' log-probability and forced forms (wrappers: kf_logp_*, below; tests/test_gpu_logp_kernels.py)
+// wn_sample_1w_lp<true, true> as the item loop of wn_kernel_v3.h calls it: `logp_mode` is r.logp's two low bits (0 = off, 1 = sampling, 2 = model: the forced
+// bit does not reach the sampler), `forced` one int32 per row, made wave-uniform and turned into -1 outside [0, 256) as the item loop does.  Every lane
+// stores its index and its logp; logp starts as the sentinel's bits, so a mode that must not write it shows.
+__global__ __launch_bounds__(64) void kf_logp_1w_kernel(int top_k, float top_p, int logp_mode, const float* logits, const float* reg, const double* u, const int* greedy,
+                                                        const float* temp, const int* forced, int* out, uint32_t* logp) {
+    const size_t row = blockIdx.x;
+    const int lane = (int)threadIdx.x;
+    WnRun r;
+    memset(&r, 0, sizeof(r));
+    r.reg = reg;
+    r.top_k = top_k;
+    r.top_p = top_p;
+    r.logp = logp_mode;
+    float logit[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) logit[k] = logits[row * 256 + 4 * lane + k];
+    const int f = __builtin_amdgcn_readfirstlane(forced[row]);
+    float lp = __uint_as_float(KF_SENT);
+    out[row * 64 + lane] = wn_sample_1w_lp<true, true>(r, logit, lane, u[row], greedy[row] != 0, temp[row], lp, (uint32_t)f < 256u ? f : -1);
+    logp[row * 64 + lane] = __float_as_uint(lp);
+}
+
+// wn_sample, the forced fork, wn_sample_logp -- the order of wn_l0_input (wn_kernel.h).  The LDS set-up and the tail sentinel are kf_sample_generic_kernel's.
+// The three lines of the forced fork are RESTATED here, not called (in the product they sit inside wn_l0_input, behind the table's pointer): the product's own
+// copy of them stays covered by tests/test_gpu_forced.py.  `status` is a device status block the test fills as wn_publish_ptr would (words 6..7: the output
+// pointer, NULL = write nothing); the value of row `row` goes to out[row + at0].  logp_mode 0: wn_sample_logp is not called, as in wn_l0_input.
+__global__ __launch_bounds__(WN_THREADS) void kf_logp_generic_kernel(int C, int smp_floats, int top_k, float top_p, int logp_mode, uint32_t* status, long long at0,
+                                                                     const float* logits, const float* reg, const double* u, const int* greedy, const float* temp,
+                                                                     const int* forced, int* out, uint32_t* tail) {
+    extern __shared__ __attribute__((aligned(16))) float kf_lds[];
+    const size_t row = blockIdx.x;
+    WnPlan pl;
+    memset(&pl, 0, sizeof(pl));
+    pl.C = C;
+    pl.l_smp = 0;
+    pl.status = status;
+    WnRun r;
+    memset(&r, 0, sizeof(r));
+    r.reg = reg;
+    r.top_k = top_k;
+    r.top_p = top_p;
+    r.logp = logp_mode;
+    WnCtx cx{&pl, &r, kf_lds, 0, 0, 0};
+    const WnSmp sm = wn_smp_carve(pl, kf_lds);
+    WN_PHASE {
+        if (tid < KF_TAIL) reinterpret_cast<uint32_t*>(kf_lds)[smp_floats + tid] = KF_SENT;
+        for (int i = tid; i < C; i += WN_THREADS) sm.lgt[i] = logits[row * C + i];
+    }
+    WN_SYNC();
+    const bool is_greedy = greedy[row] != 0;
+    wn_sample(cx, sm, u[row], is_greedy, temp[row]);
+    WN_PHASE {
+        if (tid == 0) {
+            const int32_t f = forced[row];
+            if ((uint32_t)f < (uint32_t)C) sm.iscal[0] = f;
+        }
+    }
+    WN_SYNC();
+    if (logp_mode) wn_sample_logp(cx, sm, is_greedy, row + (size_t)at0);
+    WN_SYNC();
+    WN_PHASE {
+        if (tid == 0) out[row] = sm.iscal[0];
+        if (tid < KF_TAIL) tail[row * KF_TAIL + tid] = reinterpret_cast<const uint32_t*>(kf_lds)[smp_floats + tid];
+    }
+}
+
 // what wn_generate puts into the run: the off values are 0
 static int kf_norm_k(int top_k, int C) { return top_k > 0 && top_k < C ? top_k : 0; }
 static float kf_norm_p(float top_p) { return top_p > 0.f && top_p < 1.f ? top_p : 0.f; }
 
 extern "C" {
 
-int kh_version() { return 4; }
+int kh_version() { return 5; }
 
 // One NN product through wn_launch_nn.  bn != NULL: the bf16 forms (B as bf16 [N][ldb]); else fp32 with B^T = bt [K][N] (bt1: rows k >= k_split).
 int kh_nn(void* stream, int epi, KH_MAP(a0), KH_MAP(a1), int k_split, int K, const float* bt, const float* bt1, int N, const float* bias,
@@ -295,6 +363,28 @@ int kf_sample_generic(void* stream, int rows, int C, int top_k, float top_p, con
     (void)hipGetLastError();
     hipLaunchKernelGGL(kf_sample_generic_kernel, dim3(rows), dim3(WN_THREADS), (size_t)(smp_floats + KF_TAIL) * sizeof(float), (hipStream_t)stream, C, smp_floats,
                        kf_norm_k(top_k, C), kf_norm_p(top_p), logits, reg, u, greedy, temp, out, tail);
+    return (int)hipGetLastError();
+}
+
+// ---------------------------------------------------------------- the samplers' log-probability and forced forms (tests/test_gpu_logp_kernels.py)
+// out: rows * 64 indices, logp: rows * 64 words (one of each per lane).  logp_mode: r.logp & WN_RUN_LOGP_MASK, 0 .. 2; forced: one int32 per row
+int kf_logp_1w(void* stream, int rows, int top_k, float top_p, int logp_mode, const float* logits, const float* reg, const double* u, const int* greedy,
+               const float* temp, const int* forced, int* out, uint32_t* logp) {
+    if (rows < 1 || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f) || logp_mode < 0 || logp_mode > 2) return -1;
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kf_logp_1w_kernel, dim3(rows), dim3(64), 0, (hipStream_t)stream, kf_norm_k(top_k, 256), kf_norm_p(top_p), logp_mode, logits, reg, u, greedy, temp,
+                       forced, out, logp);
+    return (int)hipGetLastError();
+}
+
+// out: rows indices; tail: as kf_sample_generic; status: 8 device words, 6..7 the pointer the values go to (row `row` to element row + at0), or NULL
+int kf_logp_generic(void* stream, int rows, int C, int top_k, float top_p, int logp_mode, uint32_t* status, long long at0, const float* logits, const float* reg,
+                    const double* u, const int* greedy, const float* temp, const int* forced, int* out, uint32_t* tail) {
+    if (rows < 1 || C < 1 || C > 4096 || top_k < 0 || !(top_p >= 0.f && top_p <= 1.f) || logp_mode < 0 || logp_mode > 2 || at0 < 0 || !status) return -1;
+    const int smp_floats = wn_smp_floats(C);
+    (void)hipGetLastError();
+    hipLaunchKernelGGL(kf_logp_generic_kernel, dim3(rows), dim3(WN_THREADS), (size_t)(smp_floats + KF_TAIL) * sizeof(float), (hipStream_t)stream, C, smp_floats,
+                       kf_norm_k(top_k, C), kf_norm_p(top_p), logp_mode, status, at0, logits, reg, u, greedy, temp, forced, out, tail);
     return (int)hipGetLastError();
 }
 
